@@ -2,13 +2,20 @@
 """
 bench.py -- facet -> subgrid throughput of the MI355X SwiFTly path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-verify] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+                    [--no-verify] [--no-cpu-baseline]
 
 One "step" = one complete forward pass of the workload with the facets already
 resident in HBM: the full-facet transform of every facet (K1), then for every
 subgrid wave the per-wave facet transform (K2), the window extraction (K3), the
 per-subgrid accumulation (K4) and finish (K5).  Nothing is cached across
 steps.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, ...).  Everything
+else -- the oracle parity of the timed objects, the axis-1-first and float64 legs, per-stage and K1 timings, the
+roofline / kernel tables, the backward pass or round trip, the other workloads and the CPU baseline -- runs only
+with --full.  --dump-outputs DIR writes a fixed, seeded sample of the finished subgrids of the LAST timed step as
+DIR/subgrids.npy (float32, [k, xA, xA, 2] = real, imaginary) with their offsets in DIR/subgrid_offsets.npy.
 
 Workloads (BASELINE.json configs; `--workload`): the default is the one the metric is
 quoted on; "32k-8x8" (configs[2]), "128k" / "128k-8x8" (configs[4], forward + backward round trip; one rank holds
@@ -247,6 +254,33 @@ def verify_facets(p, facet_cfgs, sg_cfgs, sg_vectors, facets_out, rows_per_facet
         tol_rel_rmse=tol,
         ok=bool(max(rels) < tol),
     )
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: at most this many bytes of float32 subgrid data
+DUMP_SEED = 20240611
+
+
+def dump_sample(n_subgrids, xA):
+    """Indices of the subgrids --dump-outputs writes: a fixed, seeded sample that fits DUMP_BYTES (float32 pairs)."""
+    k = min(n_subgrids, max(1, DUMP_BYTES // (xA * xA * 8)))
+    rng = numpy.random.default_rng(DUMP_SEED)
+    return sorted(int(i) for i in rng.choice(n_subgrids, size=k, replace=False))
+
+
+def write_outputs(out_dir, sg_cfgs, dumped):
+    """DIR/subgrids.npy (float32 [k, xA, xA, 2]: real, imaginary) and DIR/subgrid_offsets.npy (float64 [k, 2]: off0,
+    off1) from {index into sg_cfgs: complex64 array}"""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = sorted(dumped)
+    data = numpy.stack([dumped[i] for i in idx]).astype(numpy.complex64)
+    if data.nbytes > DUMP_BYTES:  # one subgrid alone above the budget: a seeded sample of its rows
+        n_rows = DUMP_BYTES // (data.shape[0] * data.shape[2] * 8)
+        rows = numpy.sort(numpy.random.default_rng(DUMP_SEED).choice(data.shape[1], n_rows, replace=False))
+        data = data[:, rows]
+        numpy.save(os.path.join(out_dir, "subgrid_rows.npy"), rows.astype(numpy.float64))
+    numpy.save(os.path.join(out_dir, "subgrids.npy"), numpy.ascontiguousarray(data).view(numpy.float32).reshape(data.shape + (2,)))
+    numpy.save(os.path.join(out_dir, "subgrid_offsets.npy"),
+               numpy.array([[sg_cfgs[i].off0, sg_cfgs[i].off1] for i in idx], dtype=numpy.float64))
 
 
 class StageTimer:
@@ -747,7 +781,14 @@ def main():
                          "workload's measurement")
     ap.add_argument("--wave-axis", type=int, default=None, choices=[0, 1],
                     help="force the forward pipeline: 0 = strided axis first (waves by off0), 1 = contiguous axis first")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline measurement: oracle parity, the axis-1-first and float64 "
+                         "legs, stage / K1 timings and roofline, backward / round trip, other workloads, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the finished subgrids of the last timed step to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher: start one rank per GPU ourselves (one process per GPU over RCCL)
@@ -830,8 +871,10 @@ def main():
     for j in sorted(set(local) | set(shared)):
         facet_data[j] = separable_facet(torch, vectors[j], facet_cfgs[j])
 
-    picks = sep.pick_subgrids(sg_cfgs, 6) if not args.no_verify else []
+    picks = sep.pick_subgrids(sg_cfgs, 6) if args.full and not args.no_verify else []
     kept = {}
+    dump_set = set(dump_sample(S, p["xA_size"])) if args.dump_outputs else set()
+    dumped = {}
 
     if single:
 
@@ -841,7 +884,7 @@ def main():
                 wave_axis=wave_axis,
             )
 
-        def one_pass(timer=None, keep=None):
+        def one_pass(timer=None, keep=None, dump=None):
             fwd = factory()
             if timer is not None:
                 t0 = timer.start()
@@ -856,6 +899,10 @@ def main():
                     for k, i in enumerate(widx):
                         if i in picks:
                             keep[i] = res[k].cpu().numpy()
+                if dump is not None:  # device copies, stream-ordered: no synchronisation inside the timed step
+                    for k, i in enumerate(widx):
+                        if i in dump_set:
+                            dump[i] = res[k].clone()
             return count
 
     else:
@@ -863,7 +910,7 @@ def main():
         grouped = args.exchange == "group" and wave_axis == 1 and (world > 1 or args.rccl_dry)
         index_of = {(c.off0, c.off1): i for i, c in enumerate(sg_cfgs)}
 
-        def one_pass(timer=None, keep=None):  # pylint: disable=unused-argument
+        def one_pass(timer=None, keep=None, dump=None):  # pylint: disable=unused-argument
             dfw = DistributedForward(
                 cfg, facet_cfgs, facet_data, lru_forward=1, subgrid_configs=sg_cfgs, wave_axis=wave_axis,
                 dtype=torch.complex64, whole_waves=grouped,
@@ -884,6 +931,10 @@ def main():
                         for k, c in enumerate(sgs):
                             if index_of[(c.off0, c.off1)] in picks:
                                 keep[index_of[(c.off0, c.off1)]] = res[k].cpu().numpy()
+                    if dump is not None:
+                        for k, c in enumerate(sgs):
+                            if index_of[(c.off0, c.off1)] in dump_set:
+                                dump[index_of[(c.off0, c.off1)]] = res[k].clone()
                     return len(sgs)
 
                 for group in dfw.sharding.wave_groups:
@@ -903,6 +954,10 @@ def main():
                     for k, pos in enumerate(mine):
                         if widx[pos] in picks:
                             keep[widx[pos]] = res[k].cpu().numpy()
+                if dump is not None and res is not None:
+                    for k, pos in enumerate(mine):
+                        if widx[pos] in dump_set:
+                            dump[widx[pos]] = res[k].clone()
                 return len(mine)
 
             for widx, wave in zip(wave_idx, waves):
@@ -927,7 +982,7 @@ def main():
     t0 = time.perf_counter()
     step_events[0].record()
     for i in range(args.steps):
-        one_pass()
+        one_pass(dump=dumped if dump_set and i == args.steps - 1 else None)
         step_events[i + 1].record()
     fence()
     elapsed = time.perf_counter() - t0
@@ -936,7 +991,17 @@ def main():
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
-    ms_per_step = 1e3 * elapsed / max(args.steps, 1)
+    ms_per_step = 1e3 * elapsed / args.steps
+
+    if dump_set:  # what the last timed step handed out, outside the timed region
+        dumped = {i: t.cpu().numpy() for i, t in dumped.items()}
+        if world > 1:
+            gathered = [None] * world
+            torch.distributed.all_gather_object(gathered, dumped)
+            dumped = {k: v for d in gathered for k, v in d.items()}
+        if rank == 0:
+            write_outputs(args.dump_outputs, sg_cfgs, dumped)
+        dumped = None
 
     # parity of the timed objects (same factory, same facets, same waves), outside the timed region
     parity = None
@@ -1026,7 +1091,7 @@ def main():
     stages = {}
     roofline = None
     total_bytes, parts = algorithmic_bytes(p, F, S, C)
-    if single:
+    if single and args.full:
         timer = StageTimer(torch)
         one_pass(timer)
         torch.cuda.synchronize()
@@ -1072,7 +1137,7 @@ def main():
             avg_launch_ms=k1["avg_ms"],
         )
 
-    if roofline is None and local:
+    if roofline is None and local and args.full:
         # multi-GPU: time K1 of one local facet on this rank (outside the timed region) for the roofline object
         core = cfg.core
         j0 = local[0]
@@ -1130,7 +1195,7 @@ def main():
         del out
         return par
 
-    if single and not args.no_backward and not streaming:
+    if single and args.full and not args.no_backward and not streaming:
         fwd = factory()
         fwd.prepare_all_facets()
         produced = [fwd.get_wave(wave).clone() for wave in waves]
@@ -1200,7 +1265,7 @@ def main():
             backward = dict(skipped=str(err))
         del produced, lookup
 
-    if not args.no_backward and streaming:
+    if args.full and not args.no_backward and streaming:
         # forward + backward ROUND TRIP, streaming (facet -> subgrid wave -> folded straight back into the facet sums,
         # the flow of the reference's scripts/demo_api.py): the finished subgrids of a big cover (20164 x 6.9 MB for
         # N = 131072) are never all alive
@@ -1316,7 +1381,7 @@ def main():
         algorithmic_bytes=dict(total=total_bytes, **parts),
         stages=stages,
         roofline=roofline,
-        kernels=kernel_table(args.workload, F, C, parts) if world == 1 else None,
+        kernels=kernel_table(args.workload, F, C, parts) if world == 1 and args.full else None,
         parity=parity,
         accurate=accurate,
         high_precision=high_precision,
@@ -1353,7 +1418,7 @@ def main():
         )
     if len(facet_cfgs) < len(all_facet_cfgs):
         line["scaling"] = "weak (a rank holds at most %d facets: the facet subset grows with the ranks)" % cap
-    if single and rank == 0 and args.workload == "64k-sparse" and not args.no_other_workloads and not args.no_verify:
+    if single and rank == 0 and args.full and args.workload == "64k-sparse" and not args.no_other_workloads and not args.no_verify:
         # BASELINE configs 2, 3 and 5 in the driver's line (r4 review): three timed forward passes each, after the headline
         # measurement and outside its timed region; the default workload's facets go back to the allocator first
         del facet_data[:]
@@ -1371,7 +1436,7 @@ def main():
         torch.distributed.destroy_process_group()
         _flush_c_stdio()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(p, F, S, C)
             line["cpu_baseline"]["value"] = round(line["cpu_baseline"]["value"], 3)
             line["speedup_vs_cpu_host"] = round(line["value"] / line["cpu_baseline"]["value"], 1)

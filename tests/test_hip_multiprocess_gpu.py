@@ -59,7 +59,7 @@ def test_one_rank_rccl_rehearsal_of_the_bench_path():
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
         out = subprocess.run(
             [sys.executable, os.path.join(root, "bench.py"), "--workload", "8k", "--rccl-dry", "--exchange", exchange, "--steps", "1",
-             "--warmup", "0", "--no-cpu-baseline", "--no-backward"],
+             "--warmup", "0", "--full", "--no-cpu-baseline", "--no-backward"],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, check=False,
         )
         assert out.returncode == 0, out.stderr[-3000:]

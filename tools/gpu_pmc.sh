@@ -10,7 +10,7 @@ here=$(pwd)
 # the collection, so that a launch is one kernel of one wave and its duration is not shared with a concurrent kernel; the
 # production pass overlaps them (bench.py's ms_per_step) -- byte counts per kernel do not depend on the schedule
 export SWIFTLY_PREFETCH=0 SWIFTLY_K2_CHUNK=0
-cmd="python $here/bench.py --workload $wl --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-backward"
+cmd="python $here/bench.py --workload $wl --steps 1 --warmup 0 --full --no-cpu-baseline --no-verify --no-backward"
 [ "$dir" = backward ] && cmd="python $here/tools/run_backward.py $wl 2"
 [ -f "$here/profiles/r6_pmc_kernels.json" ] && cp "$here/profiles/r6_pmc_kernels.json" "$out/pmc_kernels.json"
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace -d "$here/$out/kt" -o kt -- $cmd > "$here/$out/kt.log" 2>&1 )

@@ -7,7 +7,7 @@
 # STEPs (executed in the order given; ENV=V words apply to the following steps' processes, `--` forgets them):
 #   tests[:EXPR]         pytest -m gpu (-k EXPR), -x                     -> pytest.log
 #   smoke                __graft_entry__.smoke()                          -> smoke.log
-#   bench[:WORKLOAD]     bench.py --steps 10 --warmup 3 --no-cpu-baseline -> bench_WORKLOAD.json (+ one summary line)
+#   bench[:WORKLOAD]     bench.py --steps 10 --warmup 3 --full --no-cpu-baseline -> bench_WORKLOAD.json (+ one summary line)
 #   driver               the driver's command: python bench.py            -> bench_driver.json
 #   ab:NAME              the same short forward bench under the current ENV words -> bench_NAME.json (for A/B runs; use
 #                        SWIFTLY_HIP_LIB=$PWD/variants/X.so to compare build variants, tools/build_variant.sh)
@@ -50,18 +50,18 @@ for step in "$@"; do
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee "$out/smoke.log" ;;
     bench)
       wl=${arg:-64k-sparse}
-      env "${envs[@]}" timeout 600 python bench.py --workload "$wl" --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > "$out/bench_$wl.json" 2> "$out/bench_$wl.err"
+      env "${envs[@]}" timeout 600 python bench.py --workload "$wl" --steps 10 --warmup 3 --full --no-cpu-baseline ${BENCH_ARGS:-} > "$out/bench_$wl.json" 2> "$out/bench_$wl.err"
       summary "$out/bench_$wl.json" ;;
     driver)
-      env "${envs[@]}" timeout 900 python bench.py > "$out/bench_driver.json" 2> "$out/bench_driver.err"; summary "$out/bench_driver.json" ;;
+      env "${envs[@]}" timeout 900 python bench.py --full > "$out/bench_driver.json" 2> "$out/bench_driver.err"; summary "$out/bench_driver.json" ;;
     ab)
-      env "${envs[@]}" timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-backward --no-other-workloads ${BENCH_ARGS:-} > "$out/bench_$arg.json" 2> "$out/bench_$arg.err"
+      env "${envs[@]}" timeout 300 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-backward --no-other-workloads ${BENCH_ARGS:-} > "$out/bench_$arg.json" 2> "$out/bench_$arg.err"
       summary "$out/bench_$arg.json" ;;
     k1)
       env "${envs[@]}" timeout 300 python tools/time_k1_band.py 2>&1 | grep "ms per facet" | sed "s/^/${arg:-default}: /" | tee -a "$out/k1.txt" ;;
     trace)
       wl=${arg:-64k-sparse}
-      ( cd /tmp && env "${envs[@]}" timeout 300 rocprofv3 --kernel-trace -d "$here/$out/kt" -o kt -- python "$here/bench.py" --workload "$wl" --steps 2 --warmup 1 --no-cpu-baseline --no-verify --no-backward ${BENCH_ARGS:-} > "$here/$out/kt.log" 2>&1 )
+      ( cd "$TMPDIR" && env "${envs[@]}" timeout 300 rocprofv3 --kernel-trace -d "$here/$out/kt" -o kt -- python "$here/bench.py" --workload "$wl" --steps 2 --warmup 1 --full --no-cpu-baseline --no-verify --no-backward ${BENCH_ARGS:-} > "$here/$out/kt.log" 2>&1 )
       db=$(find "$out/kt" -name '*.db' | head -1)
       if [ -n "$db" ]; then
         python tools/rocpd_stats.py "$db" > "$out/kernel_stats_$wl.txt" 2>&1
@@ -76,11 +76,11 @@ for step in "$@"; do
       cat "$out/pmc/pmc_kernels_${arg:-forward}.txt" ;;
     others)
       for w in 8k 12k 24k 32k-8x8 64k-sparse-4x4 128k 128k-8x8; do
-        env "${envs[@]}" timeout 500 python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline > "$out/bench_$w.json" 2> "$out/bench_$w.err"
+        env "${envs[@]}" timeout 500 python bench.py --workload $w --steps 5 --warmup 2 --full --no-cpu-baseline > "$out/bench_$w.json" 2> "$out/bench_$w.err"
         summary "$out/bench_$w.json"
       done ;;
     f64)
-      timeout 500 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-workloads --column-precision 64 > "$out/bench_64k_sparse_f64.json" 2> "$out/bench_64k_sparse_f64.err"
+      timeout 500 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-other-workloads --column-precision 64 > "$out/bench_64k_sparse_f64.json" 2> "$out/bench_64k_sparse_f64.err"
       summary "$out/bench_64k_sparse_f64.json" ;;
     vranks)
       timeout 600 python tools/virtual_rank_time.py 64k-sparse "$out/virtual_ranks_64k-sparse.json" > "$out/virtual_ranks.log" 2>&1; tail -4 "$out/virtual_ranks.log"

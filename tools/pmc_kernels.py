@@ -1,5 +1,5 @@
 """Per-kernel roofline table of the forward pass from three rocprofv3 runs of the SAME build and command
-(`bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-verify --no-backward`):
+(`bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-verify --no-backward`):
 
     python tools/pmc_kernels.py <kernel_trace.db> <pmc_fetch.db> <pmc_write.db> [out.json] [workload]
 
@@ -120,7 +120,7 @@ def main():
                       "no forward pass in the process, one kernel at a time")
     else:
         key = workload
-        note = how % ("SWIFTLY_PREFETCH=0 SWIFTLY_K2_CHUNK=0 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-verify "
+        note = how % ("SWIFTLY_PREFETCH=0 SWIFTLY_K2_CHUNK=0 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-verify "
                       "--no-backward", "every kernel alone on the chip; the production pass overlaps K2 of the next wave with "
                       "K3-K5 and the two K2 passes of different chunks")
     rec[key] = dict(build=_lib.build_info(), kernels=table, note=note)
