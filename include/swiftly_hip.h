@@ -84,6 +84,13 @@ int swiftly_hip_create(swiftly_hip_t** out, int64_t N, int64_t yN_size, int64_t 
                        const double* pswf, int device);
 void swiftly_hip_destroy(swiftly_hip_t* h);
 int64_t swiftly_hip_contribution_size(const swiftly_hip_t* h); /* xM*yN/N, core.py:48 */
+/* 1 when every transform length of the handle's configuration (yN_size, xM_size, contribution size) has a kernel in
+ * `dtype` (SWIFTLY_C64 | SWIFTLY_C128), by the same gates the primitives apply: powers of two 8 .. 65536 in complex64 and
+ * 8 .. 32768 in complex128; other lengths through Bluestein / Q * 2^k where their tables exist (complex128: convolution
+ * and power-of-two sub-transform up to 8192).  0 otherwise (or for a null handle / unknown dtype).  Lets a caller pick
+ * the precision before a pass instead of meeting SWIFTLY_ERR_UNSUPPORTED halfway through.  (complex64 at 65536 is
+ * limited to the prepare_* / finish_* forms named by that error.) */
+int swiftly_hip_supports_dtype(const swiftly_hip_t* h, int dtype);
 /* Arithmetic of the column passes of the band pipelines on complex64 data (K2 = prepare_facet along the strided axis of
  * a wave, K3 = the m-point transform of add_to_subgrid behind it, and their backward mirrors): 32 (default) = float32
  * throughout; 64 = loads and stores in complex64, windows / butterflies / exchanges / four-step twiddles in float64.

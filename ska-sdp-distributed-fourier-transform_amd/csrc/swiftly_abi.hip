@@ -229,6 +229,7 @@ int swiftly_hip_create(swiftly_hip_t** out, int64_t N, int64_t yN, int64_t xM, d
     if (!g_device_inited[device]) {
         if (int rc = init_fft_rows_f32()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (f32): %d", rc);
         if (int rc = init_fft_rows_f64()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (f64): %d", rc);
+        if (int rc = init_fft_long_a()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (f64 long rows): %d", rc);
         if (int rc = init_col_pass()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (col pass): %d", rc);
         if (int rc = init_row_pass()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (row pass): %d", rc);
         if (int rc = init_sum_finish_rows()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (sum finish): %d", rc);
@@ -846,6 +847,85 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
 }
 
 
+// complex128 transform of 2^14 / 2^15 points along the CONTIGUOUS axis (swiftly_rowslong.h): pass A (mapped load, n1 =
+// 128 points per column, lanes along y2, twiddle on store) into a stream-ordered scratch [rows][k1][y2], pass B =
+// fft_rows_kernel at log2(n2) with raw load from the scratch and the primitive's store map (plain index k1 + n1*k2).  Rows
+// run in chunks whose scratch stays under kLongChunkBytes (a whole 128k[1]-n32k-1k facet would need 14 GB), all chunks
+// reuse one allocation.  SWIFTLY_LONG_ROWS_CHUNK_MB (read per call) lowers the bound (tests: many chunk boundaries).
+static const size_t kLongChunkBytes = size_t(1) << 30;
+static int run_rows_long(swiftly_hip* h, int logn, RowsArgs<double>& a, const OffTab& tab, hipStream_t st) {
+    const int l1 = kLongLogN1, l2 = logn - l1;
+    const int n1 = 1 << l1, n2 = 1 << l2;
+    const long long n = 1ll << logn;
+    if (n2 % LongAGeo::RB) return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: no pass A tiling for 2^%d points", logn);
+    const cx<double>* tw_full = twiddles<double>(h, logn);
+    const cx<double>* tw1 = twiddles<double>(h, l1);
+    const cx<double>* tw2 = twiddles<double>(h, l2);
+    if (!tw_full || !tw1 || !tw2) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables for 2^%d = 2^%d * 2^%d", logn, l1, l2);
+    const int nb = a.nbatch > 0 ? a.nbatch : 1;
+    size_t budget = kLongChunkBytes;
+    if (const char* e = getenv("SWIFTLY_LONG_ROWS_CHUNK_MB")) {
+        const long long mb = atoll(e);
+        if (mb > 0) budget = std::min(budget, (size_t)mb << 20);
+    }
+    const size_t row_bytes = (size_t)nb * (size_t)n * sizeof(cx<double>);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)a.nrows, budget / row_bytes));
+    void* scratch = nullptr;
+    HIP_TRY(hipMallocAsync(&scratch, (size_t)chunk * row_bytes, st));
+    RowsArgs<double> A = a;
+    A.tw = tw1;
+    A.full_logn = logn;
+    A.full_n = 0;
+    LongArgs<double> L;
+    L.scratch = (cx<double>*)scratch;
+    L.s_bs = (long long)chunk * n;
+    L.log_n2 = l2;
+    L.tw_full = tw_full;
+    // pass B: rows of the chunk x outer index k1 = n1 sub-transforms of length n2 per row; the n1 workgroups of a row block
+    // are enumerated next to each other on one XCD (outer_group), whose L2 merges their interleaved output elements
+    RowsArgs<double> B = a;
+    B.tw = tw2;
+    B.in = (const cx<double>*)scratch;
+    B.raw_ld = 1;
+    B.conj_ld = 0;  // applied by pass A
+    B.in_rs = n;
+    B.in_cs = 1;
+    B.in_os = n2;
+    B.in_bs = (long long)chunk * n;
+    B.rm_mod = 0;
+    B.in_rowmap = nullptr;
+    B.outer = n1;
+    B.outer_group = 1;
+    B.full_logn = logn;
+    B.full_n = 0;
+    B.ld_mul = 1;
+    B.ld_addmul = 0;
+    B.st_mul = n1;
+    B.st_addmul = 1;
+    B.st_add0 = 0;
+    B.tw_full = nullptr;
+    B.tw_on_store = 0;
+    B.raw_st = 0;
+    int rc = 0;
+    for (int row0 = 0; row0 < a.nrows && !rc; row0 += chunk) {
+        const int rows = std::min(chunk, a.nrows - row0);
+        L.row0 = row0;
+        L.nrows = rows;
+        int e = launch_fft_long_a(A, tab, L, st);
+        if (e) {
+            rc = fail(SWIFTLY_ERR_HIP, "kernel launch failed (long-row pass A): %s", hipGetErrorString((hipError_t)e));
+            break;
+        }
+        B.nrows = rows;
+        B.out = a.out + (long long)row0 * a.out_rs;
+        B.row_win = a.row_win ? a.row_win + row0 : nullptr;
+        rc = launch_checked(l2, B, tab, st);
+    }
+    hipError_t e = hipFreeAsync(scratch, st);
+    if (!rc && e != hipSuccess) return fail(SWIFTLY_ERR_HIP, "hipFreeAsync: %s", hipGetErrorString(e));
+    return rc;
+}
+
 // Launch the mapped row FFT for `a` (batch of a.nbatch <= kMaxBatch items with
 // per-item offsets in `tab`).  Transforms of length >= 2^kTwoPassMinLog along
 // a strided axis are decomposed (four-step) through a stream-ordered scratch.
@@ -884,6 +964,14 @@ static int run_rows_chunk(swiftly_hip* h, int logn, RowsArgs<R>& a, const OffTab
     if (logn > kMaxLogNFloat && sizeof(R) == 4)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "transform length 65536 is only supported for complex64 prepare_* / finish_* "
                     "calls with unit stride along the transform axis or along a strided axis of contiguous rows");
+    if constexpr (sizeof(R) == 8) {
+        if (!a.rowfast && logn > kMaxLogNDouble) {  // 16384 / 32768 complex128 points along the contiguous axis
+            if (sub || a.raw_ld)
+                return fail(SWIFTLY_ERR_UNSUPPORTED, "complex128 transform length %d along the contiguous axis: only the "
+                            "mapped-load form of the primitives is supported (no raw / sub-transform input)", 1 << logn);
+            return run_rows_long(h, logn, a, tab, st);
+        }
+    }
     if (!(a.rowfast && logn >= kTwoPassMinLog)) return launch_checked(logn, a, tab, st);
 
     // ---- four-step: N = n1 * n2, input index y = y1*n2 + y2, output index k = k1 + n1*k2
@@ -974,7 +1062,8 @@ static int run_rows_bluestein(swiftly_hip* h, int64_t n, RowsArgs<R>& a, const O
     if (!chirp || !spec)
         return fail(SWIFTLY_ERR_UNSUPPORTED,
                     "transform length %lld (not a power of two) needs a convolution of length >= %lld, beyond the %s kernels",
-                    (long long)n, (long long)(2 * n - 1), sizeof(R) == 8 ? "complex128 (8192)" : "complex64 (65536)");
+                    (long long)n, (long long)(2 * n - 1),
+                    sizeof(R) == 8 ? "complex128 (8192; Q * 2^k lengths up to Q * 8192)" : "complex64 (65536)");
     const int64_t L = int64_t(1) << logL;
     const int nb = a.nbatch > 0 ? a.nbatch : 1;
     const int64_t rows_total = (int64_t)nb * a.nrows;
@@ -1087,17 +1176,40 @@ static int run_rows_mixed(swiftly_hip* h, int64_t n, const swiftly_hip::Mixed& m
     return rc;
 }
 
+// The gates of run_rows, shared with swiftly_hip_supports_dtype: largest power-of-two length, and whether a length
+// (power of two: logn >= 0) has a route in precision R -- for other lengths the radix-Q tables (as run_rows picks them)
+// or the Bluestein tables of the handle, which exist only where their kernels do.
+template <typename R>
+static constexpr int max_log_rows() {
+    return sizeof(R) == 8 ? kMaxLogNDoubleRows : kMaxLogNFloat + 1;  // 2^16: lean complex64 kernels only
+}
+static bool use_mixed(const swiftly_hip* h, int64_t n, bool dbl) {
+    const char* no_mixed = getenv("SWIFTLY_NO_MIXED");  // read per call: Bluestein for every such length (A/B, tests)
+    auto it = h->mixed.find(n);
+    const bool have = it != h->mixed.end() && (dbl ? it->second.tw_d != nullptr : it->second.tw_f != nullptr);
+    return have && !(no_mixed && atoi(no_mixed));
+}
+template <typename R>
+static bool rows_length_supported(const swiftly_hip* h, int64_t n, int logn) {
+    constexpr bool dbl = sizeof(R) == 8;
+    if (logn >= 0) return logn >= kMinLogN && logn <= max_log_rows<R>();
+    if (use_mixed(h, n, dbl)) return true;
+    auto it = h->blu.find(n);
+    return it != h->blu.end() && (dbl ? it->second.chirp_d != nullptr : it->second.chirp_f != nullptr);
+}
+
 // `fill(b, tab_index)` sets the per-item offsets of batch item b into the
 // OffTab; called once per item per chunk.  `nlen` = transform length, `logn` = its log2 or -1.
 template <typename R, class Fill>
 static int run_rows(swiftly_hip* h, int64_t nlen, int logn, RowsArgs<R>& a, const Batch& bt, int use_bits, Fill&& fill,
                     hipStream_t st) {
-    constexpr int maxlog = sizeof(R) == 8 ? kMaxLogNDouble : kMaxLogNFloat + 1;  // 2^16: lean complex64 kernels only
-    if (logn >= 0 && (logn < kMinLogN || logn > maxlog))
+    constexpr int maxlog = max_log_rows<R>();
+    if (logn >= 0 && !rows_length_supported<R>(h, nlen, logn))
         return fail(SWIFTLY_ERR_UNSUPPORTED,
                     "transform length %lld is not supported by the HIP backend (power of two in [8, %d], or a length "
-                    "whose Bluestein convolution fits, for %s)",
-                    (long long)nlen, 1 << maxlog, sizeof(R) == 8 ? "complex128" : "complex64");
+                    "whose Bluestein convolution or Q * 2^k sub-transform fits, for %s)",
+                    (long long)nlen, 1 << maxlog, sizeof(R) == 8 ? "complex128: Bluestein and Q * 2^k up to 8192"
+                                                                  : "complex64");
     const uint64_t n = (uint64_t)nlen;
     if (n * (uint64_t)a.in_cs >= (uint64_t(1) << 32) || n * (uint64_t)a.out_cs >= (uint64_t(1) << 32))
         return fail(SWIFTLY_ERR_PARAM, "transform length * column stride must be < 2^32");
@@ -1123,12 +1235,8 @@ static int run_rows(swiftly_hip* h, int64_t nlen, int logn, RowsArgs<R>& a, cons
         if (logn >= 0) {
             rc = run_rows_chunk(h, logn, c, tab, st);
         } else {
-            // SWIFTLY_NO_MIXED=1 (read per call): Bluestein for every length that is not a power of two (A/B, tests)
-            const char* no_mixed = getenv("SWIFTLY_NO_MIXED");
-            auto it = h->mixed.find(nlen);
-            const bool have = it != h->mixed.end() && (sizeof(R) == 4 ? it->second.tw_f != nullptr : it->second.tw_d != nullptr);
-            rc = (have && !(no_mixed && atoi(no_mixed))) ? run_rows_mixed(h, nlen, it->second, c, tab, st)
-                                                          : run_rows_bluestein(h, nlen, c, tab, st);
+            rc = use_mixed(h, nlen, sizeof(R) == 8) ? run_rows_mixed(h, nlen, h->mixed.find(nlen)->second, c, tab, st)
+                                                     : run_rows_bluestein(h, nlen, c, tab, st);
         }
         if (rc) return rc;
     }
@@ -1271,6 +1379,15 @@ static int do_finish_facet(swiftly_hip* h, const void* in, int64_t rows, int64_t
 }
 
 extern "C" {
+
+int swiftly_hip_supports_dtype(const swiftly_hip_t* h, int dtype) {
+    if (!h || (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128)) return 0;
+    for (const auto& [n, logn] : {std::pair<int64_t, int>{h->yN, h->log_yN}, {h->xM, h->log_xM}, {h->m, h->log_m}}) {
+        const bool ok = dtype == SWIFTLY_C64 ? rows_length_supported<float>(h, n, logn) : rows_length_supported<double>(h, n, logn);
+        if (!ok) return 0;
+    }
+    return 1;
+}
 
 int swiftly_hip_prepare_facet(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                               int64_t in_rs, int64_t in_cs, void* out, int64_t out_rs, int64_t out_cs,

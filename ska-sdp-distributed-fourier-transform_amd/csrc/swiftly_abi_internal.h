@@ -22,6 +22,7 @@
 #include "swiftly_rowpass.h"
 #include "swiftly_sumfinish.h"
 #include "swiftly_rows.h"
+#include "swiftly_rowslong.h"
 #include "swiftly_bluestein.h"
 #include "swiftly_mixed.h"
 #include <complex>

@@ -266,7 +266,10 @@ struct GeoFor {
 
 constexpr int kMinLogN = 3;
 constexpr int kMaxLogNFloat = 15;
-constexpr int kMaxLogNDouble = 13;
+constexpr int kMaxLogNDouble = 13;  // single-workgroup double kernels, Bluestein and radix-Q double tables
+// power-of-two complex128 transforms of the primitives (run_rows): 2^14 / 2^15 as four-steps -- along a strided axis
+// through two fft_rows_kernel passes, along the contiguous axis through swiftly_rowslong.h
+constexpr int kMaxLogNDoubleRows = 15;
 
 // implemented in fft_rows_f32.hip / fft_rows_f64.hip
 int launch_fft_rows(int logn, const RowsArgs<float>& a, const OffTab& tab, hipStream_t s);

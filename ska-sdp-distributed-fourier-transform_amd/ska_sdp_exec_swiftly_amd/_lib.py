@@ -35,6 +35,8 @@ def _declare(lib):
     lib.swiftly_hip_destroy.argtypes = [vp]
     lib.swiftly_hip_contribution_size.restype = i64
     lib.swiftly_hip_contribution_size.argtypes = [vp]
+    lib.swiftly_hip_supports_dtype.restype = c_int
+    lib.swiftly_hip_supports_dtype.argtypes = [vp, c_int]
     lib.swiftly_hip_build_id.restype = ctypes.c_char_p
     lib.swiftly_hip_build_id.argtypes = []
     lib.swiftly_hip_chain_chunk_streams.restype = None

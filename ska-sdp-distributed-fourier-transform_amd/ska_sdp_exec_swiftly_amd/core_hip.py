@@ -537,6 +537,22 @@ class SwiftlyCoreHip:
         """``(Q, k)`` when ``yN_size = Q * 2^k`` with Q in {3, 5, 7, 9} (:py:func:`mixed_factor`), else None"""
         return mixed_factor(self.yN_size)
 
+    def supports_dtype(self, dtype):
+        """True when every transform length of this configuration (``yN_size``, ``xM_size``, ``xM_yN_size``) has a
+        kernel in ``dtype`` (numpy or torch complex64 / complex128): the native library's own gates
+        (``swiftly_hip_supports_dtype``).  Pick the precision with it before a pass instead of catching
+        ``NotImplementedError`` from its first primitive."""
+        torch = _torch()
+        if isinstance(dtype, torch.dtype):
+            code = {torch.complex64: _lib.C64, torch.complex128: _lib.C128}.get(dtype)
+        else:
+            code = {numpy.dtype(numpy.complex64): _lib.C64, numpy.dtype(numpy.complex128): _lib.C128}.get(
+                numpy.dtype(dtype)
+            )
+        if code is None:
+            raise ValueError(f"dtype must be complex64 or complex128, not {dtype}")
+        return bool(self._lib.swiftly_hip_supports_dtype(self._handle, code))
+
     MAX_FUSED_FACETS = 64  # kSumFinishMaxFacets (csrc/swiftly_sumfinish.h): facets summed by one sum_finish_facets call
 
     def supports_fused_subgrid(self, dtype=None, n_facets=None):
