@@ -1,4 +1,4 @@
-// instantiations + dispatch of the lean column-tile pass (complex64)
+// instantiations + dispatch of the lean column-tile pass (complex64; complex128 storage with float64 arithmetic)
 #include <cstdlib>
 
 #include "swiftly_colpass.h"
@@ -101,8 +101,59 @@ static int init_mode_f64() {
     }
 }
 
+// complex128 storage (ColPassArgs::c128): the float64-arithmetic geometries with cx<double> loads and stores; the LDS
+// exchange already holds doubles, so the tiles and LDS sizes are those of launch_mode_f64 -- except 256 points, whose
+// 64-column tile (1024 threads: 128 VGPRs at most) spills with 16-byte points: 32-column tiles, 512 threads, 64 KiB, and
+// room for 256 VGPRs
+template <int LOGN>
+struct CGeoC128 : CGeoFor<LOGN, double>::type {};
+template <>
+struct CGeoC128<8> : CGeo<8, 4, true, 32, 8> {
+    static constexpr int MINW = 2;
+};
+template <int LOGN, int MODE>
+static int launch_mode_c128(const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
+    if constexpr (LOGN < kColF64MinLog || LOGN > kColPassMaxLogF64) {
+        return (int)hipErrorInvalidConfiguration;
+    } else {
+        using G = CGeoC128<LOGN>;
+        if (!a.twd || (MODE == 0 && !a.twd_full) || a.gs) return (int)hipErrorInvalidValue;
+        const cx<double>* in = reinterpret_cast<const cx<double>*>(a.in);
+        cx<double>* out = reinterpret_cast<cx<double>*>(a.out);
+        dim3 grid((unsigned)((a.ncols + G::COLS - 1) / G::COLS), (unsigned)outer, (unsigned)nbatch);
+        if (MODE == 2 || a.scratch_nt)
+            hipLaunchKernelGGL((col_pass_kernel<G, MODE, true, false, double, double>), grid, dim3(G::NT), G::LDS_BYTES, s, a,
+                               in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
+        else
+            hipLaunchKernelGGL((col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double, double>), grid, dim3(G::NT),
+                               G::LDS_BYTES, s, a, in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd,
+                               a.twd_full, cz);
+        return (int)hipGetLastError();
+    }
+}
+template <int LOGN, int MODE>
+static int init_mode_c128() {
+    if constexpr (LOGN < kColF64MinLog || LOGN > kColPassMaxLogF64) {
+        return 0;
+    } else {
+        using G = CGeoC128<LOGN>;
+        int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<G, MODE, true, false, double, double>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
+        if (!rc && MODE != 2)
+            rc = (int)hipFuncSetAttribute(
+                reinterpret_cast<const void*>(&col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double, double>),
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
+        return rc;
+    }
+}
+
 template <int LOGN>
 static int launch_one(int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
+    if (a.c128) {
+        if (mode == 0) return launch_mode_c128<LOGN, 0>(a, cz, outer, nbatch, s);
+        if (mode == 1) return launch_mode_c128<LOGN, 1>(a, cz, outer, nbatch, s);
+        return launch_mode_c128<LOGN, 2>(a, cz, outer, nbatch, s);
+    }
     if (a.f64) {
         if (mode == 0) return launch_mode_f64<LOGN, 0>(a, cz, outer, nbatch, s);
         if (mode == 1) return launch_mode_f64<LOGN, 1>(a, cz, outer, nbatch, s);
@@ -136,6 +187,9 @@ static int init_one() {
     if (!rc) rc = init_mode_f64<LOGN, 0>();
     if (!rc) rc = init_mode_f64<LOGN, 1>();
     if (!rc) rc = init_mode_f64<LOGN, 2>();
+    if (!rc) rc = init_mode_c128<LOGN, 0>();
+    if (!rc) rc = init_mode_c128<LOGN, 1>();
+    if (!rc) rc = init_mode_c128<LOGN, 2>();
     return rc;
 }
 

@@ -17,18 +17,18 @@ static int init_one() {
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES);
 }
 
-template <int LOGM, int LOGX>
+template <int LOGM, int LOGX, typename R = float>
 static int launch_one_f(const SumFinishFacetArgs& a, int nbatch, hipStream_t s) {
-    using S = SFGeo<LOGM, LOGX>;
+    using S = SFGeo<LOGM, LOGX, R>;
     dim3 grid((unsigned)((a.nrows + S::RB - 1) / S::RB), (unsigned)nbatch);
-    constexpr size_t lds = sum_finish_facets_kernel_lds<LOGM, LOGX>();
-    hipLaunchKernelGGL((sum_finish_facets_kernel<LOGM, LOGX>), grid, dim3(S::NT), lds, s, a);
+    constexpr size_t lds = sum_finish_facets_kernel_lds<LOGM, LOGX, R>();
+    hipLaunchKernelGGL((sum_finish_facets_kernel<LOGM, LOGX, R>), grid, dim3(S::NT), lds, s, a);
     return (int)hipGetLastError();
 }
-template <int LOGM, int LOGX>
+template <int LOGM, int LOGX, typename R = float>
 static int init_one_f() {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&sum_finish_facets_kernel<LOGM, LOGX>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sum_finish_facets_kernel_lds<LOGM, LOGX>()));
+    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&sum_finish_facets_kernel<LOGM, LOGX, R>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sum_finish_facets_kernel_lds<LOGM, LOGX, R>()));
 }
 template <int LOGM, int LOGX>
 static int launch_one_s(const SplitFacetArgs& a, int nbatch, hipStream_t s) {
@@ -62,6 +62,9 @@ int launch_axis1_rows(int logm, const Axis1RowsArgs& a, int nfacets, hipStream_t
 }
 
 #define SF_PAIRS(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10) X(9, 11) X(10, 11) X(10, 12)
+// complex128 sum_finish_facets (register form, m-point transform of K3 in one column pass: m <= 512; (9, 11) would keep 32
+// complex128 accumulator values per lane and spills even at 256 VGPRs)
+#define SF_PAIRS_C128(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10)
 
 int launch_sum_finish_rows(int logm, int logx, const SumFinishArgs& a, int nbatch, hipStream_t s) {
 #define SF_CASE(M, XX) \
@@ -75,6 +78,13 @@ int launch_sum_finish_facets(int logm, int logx, const SumFinishFacetArgs& a, in
     if (logm == M && logx == XX) return launch_one_f<M, XX>(a, nbatch, s);
     SF_PAIRS(SF_CASE_F)
 #undef SF_CASE_F
+    return -1;
+}
+int launch_sum_finish_facets_c128(int logm, int logx, const SumFinishFacetArgs& a, int nbatch, hipStream_t s) {
+#define SF_CASE_D(M, XX) \
+    if (logm == M && logx == XX) return launch_one_f<M, XX, double>(a, nbatch, s);
+    SF_PAIRS_C128(SF_CASE_D)
+#undef SF_CASE_D
     return -1;
 }
 int launch_split_prepare_facets(int logm, int logx, const SplitFacetArgs& a, int nbatch, hipStream_t s) {
@@ -92,12 +102,20 @@ int init_sum_finish_rows() {
     if (!rc) rc = init_one_s<M, XX>();
     SF_PAIRS(SF_INIT)
 #undef SF_INIT
+#define SF_INIT_D(M, XX) \
+    if (!rc) rc = init_one_f<M, XX, double>();
+    SF_PAIRS_C128(SF_INIT_D)
+#undef SF_INIT_D
     return rc;
 }
 bool sum_finish_supported(int logm, int logx) {
 #define SF_HAS(M, XX) \
     if (logm == M && logx == XX) return true;
     SF_PAIRS(SF_HAS)
+    return false;
+}
+bool sum_finish_c128_supported(int logm, int logx) {
+    SF_PAIRS_C128(SF_HAS)
 #undef SF_HAS
     return false;
 }

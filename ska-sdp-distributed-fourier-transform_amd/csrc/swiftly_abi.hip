@@ -457,19 +457,24 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
     // single pass up to 1024 points; the gather-sum load (c.gs, backward pass) exists for 64-column tiles only, i.e. up to
     // 512 points: longer gather-sum transforms go through the four-step, whose pass A carries the load (r3 bug: a
     // 1024-point gather-sum transform ran the plain 32-column kernel, which read the encoded table as a row map)
-    const bool two = logn > (c.gs ? 9 : kColPassMaxLog);
+    // complex128 storage (c.c128): float64 arithmetic in every pass, single pass up to 512 points
+    const bool c128 = c.c128 != 0;
+    const size_t esz = c128 ? sizeof(cx<double>) : sizeof(cx<float>);
+    if (c128 && c.gs) return -1;
+    const bool two = logn > (c.gs ? 9 : c128 ? kColPassMaxLogF64 : kColPassMaxLog);
     const int l1 = two ? logn / 2 : logn, l2 = logn - l1;  // (32768 = 128 x 256; 256 x 128 and 64 x 512 measured slower, r4)
     if (l1 < kColPassMinLog || l1 > kColPassMaxLog || (two && (l2 < kColPassMinLog || l2 > kColPassMaxLog))) return -1;
     const uint64_t n = uint64_t(1) << logn;
     // float64 arithmetic where the caller asks for it and the instances exist (else float32, silently: same results to
     // float32 rounding)
-    const bool f64 = c.f64 && (two ? (col_pass_f64_supported(l1) && col_pass_f64_supported(l2))
-                                   : (col_pass_f64_supported(logn) && !(c.gs && logn > 8)));
+    const bool f64 = (c.f64 || c128) && (two ? (col_pass_f64_supported(l1) && col_pass_f64_supported(l2))
+                                             : (col_pass_f64_supported(logn) && !(c.gs && logn > 8)));
+    if (c128 && !f64) return -1;
     if (!two) {
         ColPassArgs one = c;
         one.tw = twiddles<float>(h, logn);
         if (!one.tw) return -1;
-        one.f64 = (f64 && (h->col_f64_stages & 4)) ? 1 : 0;
+        one.f64 = (f64 && (c128 || (h->col_f64_stages & 4))) ? 1 : 0;
         one.twd = f64 ? twiddles<double>(h, logn) : nullptr;
         one.twd_full = one.twd;
         if (f64 && !one.twd) return -1;
@@ -491,7 +496,8 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
     if (n * (uint64_t)W >= (uint64_t(1) << 32)) return -1;
     const bool gathered = (cz.flags & kZColGather) != 0;
     const long long Ws = (long long)W;  // scratch row width (column slabs that keep the intermediate cache-sized: no gain, r2-r4)
-    const size_t scratch_bytes = (size_t)nb * n * (size_t)Ws * sizeof(cx<float>);
+    const size_t scratch_bytes = (size_t)nb * n * (size_t)Ws * esz;
+    auto elem = [esz](const cx<float>* p, long long k) { return (cx<float>*)((const char*)p + k * (long long)esz); };
     void* scratch = nullptr;
     hipError_t he = hipSuccess;
     // caller-provided workspace (deterministic; the stream-ordered pool reuses memory across STREAMS only
@@ -530,7 +536,7 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
         chunk_cols = 0;
         if (scratch_bytes > (size_t(256) << 20) && W >= 256) {
             chunk_cols = 256;
-            chunk_items = (int)std::max<uint64_t>(1, (uint64_t(128) << 20) / (n * 256 * sizeof(cx<float>)));
+            chunk_items = (int)std::max<uint64_t>(1, (uint64_t(128) << 20) / (n * 256 * esz));
         }
     }
     // (r5: three or four chunk streams instead of two -- 41.4-42.1 ms per pass against 38.9-39.8 with the default chunks,
@@ -539,7 +545,7 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
         (nb > chunk_items || W > chunk_cols) && !own) {
         const int Wc = std::min<int>((chunk_cols / 64) * 64, W), zc = std::min(chunk_items, nb);
         const size_t slot_elems = (size_t)n * (size_t)Wc * (size_t)zc;
-        if (2 * slot_elems * sizeof(cx<float>) <= ws_bytes) {
+        if (2 * slot_elems * esz <= ws_bytes) {
             {
                 std::lock_guard<std::mutex> lock(h->chunk_mu);
                 for (hipStream_t& s2 : h->chunk_st)
@@ -590,7 +596,7 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
                     hipStream_t s2 = h->chunk_st[i & 1];
                     // item z of the launch sits at slot + (z - z0) * n * Wc (raw_z0: the kernels address the scratch
                     // with the item index relative to the launch's first item)
-                    cx<float>* slot = (cx<float>*)scratch + (size_t)(i & 1) * slot_elems;
+                    cx<float>* slot = elem((const cx<float>*)scratch, (long long)((size_t)(i & 1) * slot_elems));
                     ColPassArgs A = c;
                     A.scratch_nt = 0;
                     A.ncols = wc; A.col0 = c0; A.z0 = z0; A.raw_z0 = z0;
@@ -599,7 +605,7 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
                     A.ld_mul = n2;
                     A.out_i_rows = a_i_rows; A.out_o_rows = a_o_rows;
                     A.tw = tw1; A.tw_full = twf;
-                    A.f64 = (f64 && (h->col_f64_stages & 1)) ? 1 : 0; A.twd = twd1; A.twd_full = twdf;
+                    A.f64 = (f64 && (c128 || (h->col_f64_stages & 1))) ? 1 : 0; A.twd = twd1; A.twd_full = twdf;
                     A.conj_st = 0; A.accumulate = 0; A.scale = 1.f;
                     A.col_win = nullptr; A.st_rowmap = nullptr; A.st_win = nullptr; A.st_win2 = nullptr;
                     rc = launch_col_checked(l1, 0, A, cz, n2, nz, s2);
@@ -613,12 +619,12 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
                     B.in_bdiv = 0; B.in_bs_hi = 0;
                     B.in_i_rows = b_i_rows; B.in_o_rows = b_o_rows;
                     B.ld_rowmap = nullptr; B.ld_win = nullptr; B.ld_win2 = nullptr; B.gs = 0;
-                    B.out = c.out + c0;
+                    B.out = elem(c.out, c0);
                     B.st_mul = n1;
                     B.tw = tw2; B.tw_full = twf;
-                    B.f64 = (f64 && (h->col_f64_stages & 2)) ? 1 : 0; B.twd = twd2; B.twd_full = twdf;
+                    B.f64 = (f64 && (c128 || (h->col_f64_stages & 2))) ? 1 : 0; B.twd = twd2; B.twd_full = twdf;
                     B.conj_ld = 0;
-                    if (B.col_win) B.col_win += c0;
+                    if (B.col_win) B.col_win += c128 ? 2 * c0 : c0;  // (double table with complex128 storage)
                     rc = launch_col_checked(l2, 1, B, zb, n1, nz, s2);
                 }
             }
@@ -647,13 +653,13 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
         ColPassArgs A = c;
         A.scratch_nt = scratch_nt;
         A.ncols = wc;
-        A.in = c.in + c0;
+        A.in = elem(c.in, c0);
         A.out = (cx<float>*)scratch; A.out_pitch = (unsigned)Ws; A.out_bs = (long long)(n * Ws);
         A.out_bdiv = 0; A.out_bs_hi = 0;
         A.ld_mul = n2;
         A.out_i_rows = a_i_rows; A.out_o_rows = a_o_rows;
         A.tw = tw1; A.tw_full = twf;
-        A.f64 = (f64 && (h->col_f64_stages & 1)) ? 1 : 0; A.twd = twd1; A.twd_full = twdf;
+        A.f64 = (f64 && (c128 || (h->col_f64_stages & 1))) ? 1 : 0; A.twd = twd1; A.twd_full = twdf;
         if (qmul > 0) {
             A.full_logn = logn; A.full_n = 0; A.ld_plain = 1; A.st_qmul = 0;
         }
@@ -673,15 +679,15 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
         B.in_bdiv = 0; B.in_bs_hi = 0;
         B.in_i_rows = b_i_rows; B.in_o_rows = b_o_rows;
         B.ld_rowmap = nullptr; B.ld_win = nullptr; B.ld_win2 = nullptr; B.gs = 0;
-        B.out = c.out + c0;
+        B.out = elem(c.out, c0);
         B.st_mul = n1;
         B.tw = tw2; B.tw_full = twf;
-        B.f64 = (f64 && (h->col_f64_stages & 2)) ? 1 : 0; B.twd = twd2; B.twd_full = twdf;
+        B.f64 = (f64 && (c128 || (h->col_f64_stages & 2))) ? 1 : 0; B.twd = twd2; B.twd_full = twdf;
         if (qmul > 0) {
             B.full_logn = logn; B.full_n = full_n; B.st_qmul = qmul; B.st_qadd = qadd;
         }
         B.conj_ld = 0;
-        if (B.col_win) B.col_win += c0;
+        if (B.col_win) B.col_win += c128 ? 2 * c0 : c0;
         rc = launch_col_checked(l2, 1, B, zb, n1, nb, st);
     }
     if (own) {
@@ -1616,9 +1622,24 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
         return fail(SWIFTLY_ERR_PARAM, "rows [%lld, +%lld) are not inside a facet of %lld rows", (long long)other_axis_row0,
                     (long long)rows, (long long)other_axis_size);
     DeviceGuard device_guard_(h->device);
-    if (dtype != SWIFTLY_C64) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: complex64 only");
+    if (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
     CHECK_FACET_SIZE();
     const int yN = (int)h->yN;
+    if (dtype == SWIFTLY_C128) {
+        // complex128: the plain band layout that keeps the whole padded axis, through the complex128 row transforms (one
+        // workgroup per row up to 8192 points, the two-kernel long-row form for 16384 / 32768)
+        if (h->log_yN < 3 || h->log_yN > 15)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: complex128 needs a power-of-two yN_size of 8 .. 32768, got %d", yN);
+        if (band_start != 0 || band_len != yN)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: complex128 keeps the whole padded axis (band must be (0, yN_size))");
+        if (win_d) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_window_rows: complex64 only");
+        if (rows < 0 || rows > 0x7fffffff) return fail(SWIFTLY_ERR_PARAM, "bad row count");
+        if (fold_other_axis_window && (other_axis_row0 != 0 || other_axis_size != rows))
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rows: complex128 has no row blocks");
+        if (rows == 0) return 0;
+        return do_prepare_facet<double>(h, in, rows, facet_size, in_row_stride, 1, out, out_row_stride, 1, facet_off, INT64_MIN,
+                                        nullptr, nullptr, fold_other_axis_window, 0, (hipStream_t)stream);
+    }
     const bool mixed_yN = h->log_yN < 0 && h->mixed.count(h->yN) && h->mixed.at(h->yN).tw_f;
     if (!mixed_yN && (h->log_yN < 3 || h->log_yN > 16))
         return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: padded facet size %d not supported (power of two 8 .. 65536, or Q * 2^k with Q = 3, 5, 7, 9)", yN);

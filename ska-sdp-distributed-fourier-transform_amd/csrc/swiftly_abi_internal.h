@@ -152,6 +152,18 @@ struct DeviceGuard {
 // two passes of short transforms so that every access is >= 128 B contiguous.
 static const int kTwoPassMinLog = 9;
 
+// element k of a complex array of either storage type (complex128 arrays travel through the cx<float> pointers of the
+// column-pass and sum_finish argument blocks)
+static inline const cx<float>* cx_at(const void* p, int64_t k, bool c128) {
+    return (const cx<float>*)((const char*)p + k * (int64_t)(c128 ? sizeof(cx<double>) : sizeof(cx<float>)));
+}
+static inline cx<float>* cx_at(void* p, int64_t k, bool c128) {
+    return (cx<float>*)((char*)p + k * (int64_t)(c128 ? sizeof(cx<double>) : sizeof(cx<float>)));
+}
+// complex128 band pipeline (K2, K3, sum_finish_facets): power-of-two padded facets up to 32768 points in the plain band
+// layout, m-point transforms in one column pass (m <= 512) and a complex128 sum_finish_facets instance for (m, xM)
+bool band_pipeline_c128_supported(const swiftly_hip* h);
+
 // column-tile passes (swiftly_abi.hip)
 ColZ plain_colz();
 // single-pass launch of length 2^logn: float64 arithmetic when the handle asks for it and the instance exists

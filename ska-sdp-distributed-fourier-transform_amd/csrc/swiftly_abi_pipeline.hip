@@ -24,6 +24,11 @@ __global__ void zero_untouched_kernel(cx<float>* __restrict__ band, const unsign
 }
 
 
+bool band_pipeline_c128_supported(const swiftly_hip* h) {
+    return h->log_yN >= 6 && h->log_yN <= 15 && col_pass_f64_supported(h->log_m) &&
+           sum_finish_c128_supported(h->log_m, h->log_xM);
+}
+
 extern "C" {
 
 int swiftly_hip_sum_finish_rows(swiftly_hip_t* h, int dtype, const void* in, int64_t ngroups, int64_t in_group_stride,
@@ -245,7 +250,12 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
                                       int64_t out_wave_stride, const int32_t* rowmaps, int64_t rowmap_stride,
                                       void* stream, void* ws = nullptr, size_t ws_bytes = 0) {
     if (!h || !in || !out || !facet_off0s || !wave_off1s) return fail(SWIFTLY_ERR_PARAM, "null argument");
-    if (dtype != SWIFTLY_C64) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: complex64 only");
+    const bool c128 = dtype == SWIFTLY_C128;
+    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    if (c128 && !band_pipeline_c128_supported(h))
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: complex128 needs a power-of-two yN_size of 64 .. 32768 and "
+                    "(m, xM) with a complex128 sum_finish_facets instance, got yN_size %lld, m %lld, xM %lld",
+                    (long long)h->yN, (long long)h->m, (long long)h->xM);
     const int yN = (int)h->yN, m = (int)h->m;
     if (h->log_m < 6) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: sizes not supported");
     if (rows <= 0 || rows >= yN) return fail(SWIFTLY_ERR_PARAM, "facet size %lld must be in [1, yN_size - 1]", (long long)rows);
@@ -271,12 +281,15 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
     c.scale = (float)(1.0 / yN);
     c.conj_ld = c.conj_st = 1;
     c.cg_mod = m; c.cg_full = yN;
-    c.cg_band_start = (int)band_start; c.cg_band_len = (int)band_len; c.cg_band_half = band_half_of(h, band_len);
+    // (complex128: plain band layout -- its K1 keeps the whole padded axis in plain column order)
+    c.cg_band_start = (int)band_start; c.cg_band_len = (int)band_len; c.cg_band_half = c128 ? 0 : band_half_of(h, band_len);
     c.f64 = h->col_f64;  // (col_transform falls back to float32 where the instances do not exist)
+    c.c128 = c128 ? 1 : 0;
+    const int esz = c128 ? 16 : 8;
     const int per_f = kColZF;  // facets per launch group (smaller groups: no gain, r4)
     // keep the four-step scratch of one launch group below ~4 GB
     const int64_t group_cap = ws ? (int64_t)ws_bytes : (int64_t(4) << 30);
-    const int64_t per_w_cap = std::max<int64_t>(1, group_cap / ((int64_t)yN * m * 8) / std::min<int64_t>(per_f, nfacets));
+    const int64_t per_w_cap = std::max<int64_t>(1, group_cap / ((int64_t)yN * m * esz) / std::min<int64_t>(per_f, nfacets));
     const int per_w = (int)std::min<int64_t>(kColZB, per_w_cap);
     for (int64_t f0 = 0; f0 < nfacets; f0 += per_f) {
         const int nf = (int)std::min<int64_t>(per_f, nfacets - f0);
@@ -292,9 +305,9 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
             }
             for (int f = 0; f < nf; f++) cz.f_lda[f] = pmod(-(facet_off0s[f0 + f] + lo), yN);
             // item z = f*nw + w reads band buffer f, writes out[f][w]
-            c.in = (const cx<float>*)in + f0 * in_facet_stride;
+            c.in = cx_at(in, f0 * in_facet_stride, c128);
             c.in_bdiv = nw; c.in_bs_hi = in_facet_stride; c.in_bs = 0;
-            c.out = (cx<float>*)out + f0 * out_facet_stride + w0 * out_wave_stride;
+            c.out = cx_at(out, f0 * out_facet_stride + w0 * out_wave_stride, c128);
             c.out_bdiv = nw; c.out_bs_hi = out_facet_stride; c.out_bs = out_wave_stride;
             c.st_rowmap = rowmaps ? rowmaps + w0 * rowmap_stride : nullptr;
             c.st_rowmap_bs = rowmaps ? rowmap_stride : 0;
@@ -344,8 +357,14 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
                                         void* out, int64_t out_facet_stride, int64_t out_sub_stride,
                                         const int64_t* out_offs, const int64_t* out_fstrides, void* stream) {
     if (!h || !in || !out || !facet_off0s) return fail(SWIFTLY_ERR_PARAM, "null argument");
-    if (dtype != SWIFTLY_C64) return fail(SWIFTLY_ERR_UNSUPPORTED, "transform_contributions: complex64 only");
+    const bool c128 = dtype == SWIFTLY_C128;
+    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
     if (layout < 0 || layout > 2) return fail(SWIFTLY_ERR_PARAM, "bad layout %d", layout);
+    // complex128: the row-window layouts of the band pipeline (layout 0 gathers from the complex64-only column buffers)
+    if (c128 && (layout == 0 || !band_pipeline_c128_supported(h)))
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "transform_contributions: complex128 takes layouts 1 and 2 and m = 32 .. 512 with a "
+                    "complex128 sum_finish_facets instance, got layout %d, m %lld, xM %lld", layout, (long long)h->m,
+                    (long long)h->xM);
     if (layout != 2 && !subgrid_offs) return fail(SWIFTLY_ERR_PARAM, "null argument");
     const int m = (int)h->m, yN = (int)h->yN;
     // (layout 0 gathers columns with masks of the padded facet size; the row-window layouts take any yN)
@@ -363,7 +382,7 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
     c.ld_mul = c.st_mul = 1;
     c.ld_a = 0; c.ld_len = m; c.ld_c = 0; c.ld_mod = m;
     c.st_a = 0; c.st_len = m; c.st_c = 0; c.st_mod = m;   // no placement: out[k] = Fn[k] * F[(k + s') mod m]
-    c.st_win = h->fn_f;
+    c.st_win = c128 ? (const float*)h->fn_d : h->fn_f;  // (complex128: the double table)
     c.scale = 1.f;
     c.tw = twiddles<float>(h, h->log_m);
     if (!c.tw) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle table");
@@ -396,19 +415,25 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
             if (layout == 0) cz.flags |= kZColGather;
             if (layout == 1) cz.flags |= kZLoadB;
             // item z = f*nb + b reads in + f*in_facet_stride (+ b*in_sub_stride for layout 2), writes out[f][b]
-            c.in = (const cx<float>*)in + f0 * in_facet_stride + (layout == 2 ? b0 * in_sub_stride : 0);
+            c.in = cx_at(in, f0 * in_facet_stride + (layout == 2 ? b0 * in_sub_stride : 0), c128);
             c.in_bdiv = nb; c.in_bs_hi = in_facet_stride; c.in_bs = layout == 2 ? in_sub_stride : 0;
-            c.out = (cx<float>*)out + f0 * out_facet_stride + b0 * out_sub_stride;
+            c.out = cx_at(out, f0 * out_facet_stride + b0 * out_sub_stride, c128);
             c.out_bdiv = nb; c.out_bs_hi = out_facet_stride; c.out_bs = out_sub_stride;
             if (out_offs) {
                 cz.flags |= kZOutB;
-                c.out = (cx<float>*)out;
+                c.out = cx_at(out, 0, c128);
                 for (int b = 0; b < nb; b++) {
                     cz.b_out_fs[b] = out_fstrides[b0 + b];
                     cz.b_out_off[b] = out_offs[b0 + b] + f0 * out_fstrides[b0 + b];
                 }
             }
             set_col_precision(h, c, h->log_m);
+            if (c128) {  // complex128 storage: always the float64-arithmetic instance
+                c.c128 = 1;
+                c.f64 = 1;
+                c.twd = c.twd_full = twiddles<double>(h, h->log_m);
+                if (!c.twd) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle table");
+            }
             if (int rc = launch_col_checked(h->log_m, 2, c, cz, 1, nf * nb, (hipStream_t)stream)) return rc;
         }
     }
@@ -436,9 +461,13 @@ static int sum_finish_facets_impl(swiftly_hip_t* h, int dtype, const void* in, i
     if (!h || !in || !out || !facet_off0s || !facet_off1s || !subgrid_off1s) return fail(SWIFTLY_ERR_PARAM, "null argument");
     DeviceGuard device_guard_(h->device);
     CHECK_SUBGRID_SIZE();
-    if (dtype != SWIFTLY_C64) return fail(SWIFTLY_ERR_UNSUPPORTED, "sum_finish_facets: complex64 only");
+    const bool c128 = dtype == SWIFTLY_C128;
+    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
     if (nfacets <= 0 || nfacets > kSumFinishMaxFacets)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "sum_finish_facets: 1..%d facets supported", kSumFinishMaxFacets);
+    if (c128 && (placed || !sum_finish_c128_supported(h->log_m, h->log_xM)))
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "sum_finish_facets: complex128 %s", placed ? "has no placed mode (axis-1-first pipeline)"
+                    : "instances exist for (m, xM) = (128, 256), (128, 1024), (256, 512), (256, 1024), (512, 1024)");
     if (!sum_finish_supported(h->log_m, h->log_xM))
         return fail(SWIFTLY_ERR_UNSUPPORTED, "sum_finish_facets: (m, xM) = (%lld, %lld) not instantiated", (long long)h->m,
                     (long long)h->xM);
@@ -466,13 +495,21 @@ static int sum_finish_facets_impl(swiftly_hip_t* h, int dtype, const void* in, i
     a.twc_m = compact_twiddles(h, h->log_m, h->log_m - 6);
     a.twc_x = compact_twiddles(h, h->log_xM, h->log_xM - (h->log_xM >= 12 ? 8 : 6));
     if (!a.twc_m || !a.twc_x) return fail(SWIFTLY_ERR_HIP, "internal: missing compact twiddle tables");
+    if (c128) {  // double Fn and plain double twiddle tables (the complex128 instances read no compact copies)
+        a.fn = (const float*)h->fn_d;
+        a.tw_m = (const cx<float>*)twiddles<double>(h, h->log_m);
+        a.tw_x = (const cx<float>*)twiddles<double>(h, h->log_xM);
+        if (!a.fn || !a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing double tables");
+    }
     for (int64_t b0 = 0; b0 < nsub; b0 += kSumFinishMaxBatch) {
         const int nb = (int)std::min<int64_t>(kSumFinishMaxBatch, nsub - b0);
-        a.in = (const cx<float>*)in + b0 * in_sub_stride;
-        a.out = (cx<float>*)out + b0 * out_sub_stride;
-        a.mask = mask ? (const float*)mask + b0 * mask_batch_stride : nullptr;
+        a.in = cx_at(in, b0 * in_sub_stride, c128);
+        a.out = cx_at(out, b0 * out_sub_stride, c128);
+        // (mask: float, or double with complex128 data)
+        a.mask = mask ? (const float*)((const char*)mask + b0 * mask_batch_stride * (c128 ? 8 : 4)) : nullptr;
         for (int b = 0; b < nb; b++) a.st_a[b] = pmod(-(xM / 2 - xA / 2 + subgrid_off1s[b0 + b]), xM);
-        int e = launch_sum_finish_facets(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
+        int e = c128 ? launch_sum_finish_facets_c128(h->log_m, h->log_xM, a, nb, (hipStream_t)stream)
+                     : launch_sum_finish_facets(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
         if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     }
     return 0;

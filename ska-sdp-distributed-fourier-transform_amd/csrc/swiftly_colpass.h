@@ -36,6 +36,27 @@ __device__ __forceinline__ void cp_store(cx<float>* p, cx<float> v) {
     }
 }
 
+// complex128 storage (ColPassArgs::c128): the same passes with 16-byte points, always with float64 arithmetic
+typedef double cp_f64x2 __attribute__((ext_vector_type(2)));
+template <bool NT>
+__device__ __forceinline__ cx<double> cp_load(const cx<double>* p) {
+    if constexpr (NT) {
+        const cp_f64x2 v = __builtin_nontemporal_load(reinterpret_cast<const cp_f64x2*>(p));
+        return {v.x, v.y};
+    } else {
+        return *p;
+    }
+}
+template <bool NT>
+__device__ __forceinline__ void cp_store(cx<double>* p, cx<double> v) {
+    if constexpr (NT) {
+        const cp_f64x2 w = {v.x, v.y};
+        __builtin_nontemporal_store(w, reinterpret_cast<cp_f64x2*>(p));
+    } else {
+        *p = v;
+    }
+}
+
 struct ColPassArgs {
     const cx<float>* in;
     cx<float>* out;
@@ -111,6 +132,9 @@ struct ColPassArgs {
     // workgroups of another kernel) instead of 64-column tiles (1024 threads, 128 KiB: the CU to itself); set by the
     // callers for which it was measured -- K3 of the forward wave loop, which runs next to K2 of the following waves (r5)
     int tile32;
+    // complex128 STORAGE (in, out and the four-step scratch hold cx<double>; the pointers above are then reinterpreted):
+    // the float64-arithmetic geometries with 16-byte loads and stores.  Lengths 32 .. 512 per pass, no gather-sum load.
+    int c128;
 };
 
 // Per-batch-item parameters (by value).  Batch item z = f * nb + b  (f: facet index, b: subgrid index of the
@@ -219,9 +243,9 @@ __device__ __forceinline__ double slot_bcast_f(double val, int v, int hw) {
 // coalesced vector load per table instead of P dependent scalar loads), and
 // the main loops fetch the values with v_readlane.  The output-side
 // bookkeeping is issued before the butterflies so its latency hides under them.
-template <class G, int MODE, bool SNT, bool GS, class CZ, typename RC = float>
-__device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<float>* __restrict__ gin,
-                                              cx<float>* __restrict__ gout, const float* __restrict__ ld_win,
+template <class G, int MODE, bool SNT, bool GS, class CZ, typename RC = float, typename ST = float>
+__device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>* __restrict__ gin,
+                                              cx<ST>* __restrict__ gout, const float* __restrict__ ld_win,
                                               const float* __restrict__ ld_win2, const float* __restrict__ st_win,
                                               const float* __restrict__ st_win2, const int* __restrict__ st_rowmap,
                                               const cx<RC>* __restrict__ tw, const cx<RC>* __restrict__ tw_full,
@@ -274,15 +298,21 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<flo
     const long long in_off =
         A.in_bdiv > 0 ? (long long)(z / A.in_bdiv) * A.in_bs_hi + (long long)(z % A.in_bdiv) * A.in_bs
                       : (long long)(RAW_LD ? z - A.raw_z0 : z) * A.in_bs;
-    const cx<float>* __restrict__ in = gin + (GS ? 0ll : in_off) + lcol;
+    static_assert(sizeof(ST) <= sizeof(RC), "complex128 storage computes in double");
+    const cx<ST>* __restrict__ in = gin + (GS ? 0ll : in_off) + lcol;
     const long long out_off =
         (cz.flags & kZOutB) ? cz.b_out_off[zb] + (long long)zf * cz.b_out_fs[zb]
         : A.out_bdiv > 0 ? (long long)(z / A.out_bdiv) * A.out_bs_hi + (long long)(z % A.out_bdiv) * A.out_bs
                          : (long long)(RAW_ST ? z - A.raw_z0 : z) * A.out_bs;
-    cx<float>* __restrict__ out = gout + out_off + ocol;
+    cx<ST>* __restrict__ out = gout + out_off + ocol;
     const RC sg_ld = A.conj_ld ? (RC)-1 : (RC)1;
     const RC sg_st = A.conj_st ? (RC)-1 : (RC)1;
-    const RC col_w = (A.col_win && live) ? (RC)A.col_win[col] : (RC)1;
+    // real tables (windows, masks): float, or double with complex128 storage (the pointers are then reinterpreted)
+    auto win_at = [](const float* w, long long i) -> RC {
+        if constexpr (sizeof(ST) == 8) return reinterpret_cast<const double*>(w)[i];
+        else return (RC)w[i];
+    };
+    const RC col_w = (A.col_win && live) ? win_at(A.col_win, col) : (RC)1;
     bool rmw = A.accumulate != 0;
     if (!RAW_ST && A.accumulate && A.touched && live) rmw = A.touched[ocol] != 0;
     const int slot = lane & (P - 1);
@@ -322,8 +352,8 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<flo
                 in_row = ok ? idx : -1;
             }
             const int qs = ok ? q : 0;
-            if (ld_win) in_w *= (RC)ld_win[qs];
-            if (ld_win2) in_w *= (RC)ld_win2[qs];
+            if (ld_win) in_w *= win_at(ld_win, qs);
+            if (ld_win2) in_w *= win_at(ld_win2, qs);
         }
     }
     // ---- output rows: lane `slot` describes the output the scatter calls slot (u, r)
@@ -347,8 +377,8 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<flo
             if (idx >= A.st_mod) idx -= A.st_mod;
             const bool ok = d < A.st_len;
             const int ds = ok ? d : 0;
-            if (st_win) out_w *= (RC)st_win[(long long)z * A.st_win_bs + ds];
-            if (st_win2) out_w *= (RC)st_win2[ds];
+            if (st_win) out_w *= win_at(st_win, (long long)z * A.st_win_bs + ds);
+            if (st_win2) out_w *= win_at(st_win2, ds);
             int row = idx;
             if (st_rowmap) row = st_rowmap[(long long)zb * A.st_rowmap_bs + (ok ? idx : 0)];
             out_row = ok ? row : -1;
@@ -361,7 +391,7 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<flo
     static_for<0, P>([&](auto vI) {
         constexpr int v = decltype(vI)::value;
         const int row = slot_bcast<HALF>(in_row, v, hw);
-        cx<float> val = {0.f, 0.f};
+        cx<ST> val = {(ST)0, (ST)0};
         if constexpr (GS) {
             const int lo1 = __builtin_amdgcn_readlane((int)gs_off1, v), hi1 = __builtin_amdgcn_readlane((int)(gs_off1 >> 32), v);
             if (hi1 >= 0) {  // uniform
@@ -372,7 +402,7 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<flo
             if (hi2 >= 0) {  // uniform
                 const long long o2 = ((long long)hi2 << 32) | (unsigned)lo2;
                 if (live) {
-                    const cx<float> w2 = cp_load<NT_LD>(in + o2);
+                    const cx<ST> w2 = cp_load<NT_LD>(in + o2);
                     if constexpr (sizeof(RC) == 8) {  // the sum of the two source rows in double
                         x[v] = cx<RC>{(RC)val.x + (RC)w2.x, (RC)val.y + (RC)w2.y};
                         return;
@@ -409,29 +439,29 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<flo
             w.y = slot_bcast_f<HALF>(out_tw.y, s, hw);
             v = cmul(v, w);
             v.y *= sg_st;
-            if (live) cp_store<NT_ST>(out + (unsigned)row * A.out_pitch, cx<float>{(float)v.x, (float)v.y});
+            if (live) cp_store<NT_ST>(out + (unsigned)row * A.out_pitch, cx<ST>{(ST)v.x, (ST)v.y});
         } else {
             const RC w = slot_bcast_f<HALF>(out_w, s, hw) * col_w;
             v.x *= w;
             v.y *= w * sg_st;
-            cx<float>* p = out + (unsigned)row * A.out_pitch;
+            cx<ST>* p = out + (unsigned)row * A.out_pitch;
             if (A.accumulate) {
                 if (live && rmw) {
-                    const cx<float> old = *p;
+                    const cx<ST> old = *p;
                     v.x += (RC)old.x;
                     v.y += (RC)old.y;
                 }
             }
-            if (live) cp_store<NT_ST>(p, cx<float>{(float)v.x, (float)v.y});
+            if (live) cp_store<NT_ST>(p, cx<ST>{(ST)v.x, (ST)v.y});
         }
     });
 }
 
 // (wave = workgroup-uniform wave index, lane; bx / o / z = column tile, outer index, batch item: the grid of the plain
 // kernel; tools/experiments/swiftly_fourstep.h calls the body with a schedule of its own)
-template <class G, int MODE, bool SNT, bool GS = false, typename RC = float>
-__global__ __launch_bounds__(G::NT, G::MINW) void col_pass_kernel(const ColPassArgs A, const cx<float>* __restrict__ gin,
-                                                         cx<float>* __restrict__ gout,
+template <class G, int MODE, bool SNT, bool GS = false, typename RC = float, typename ST = float>
+__global__ __launch_bounds__(G::NT, G::MINW) void col_pass_kernel(const ColPassArgs A, const cx<ST>* __restrict__ gin,
+                                                         cx<ST>* __restrict__ gout,
                                                          const float* __restrict__ ld_win,
                                                          const float* __restrict__ ld_win2,
                                                          const float* __restrict__ st_win,
@@ -440,7 +470,7 @@ __global__ __launch_bounds__(G::NT, G::MINW) void col_pass_kernel(const ColPassA
                                                          const cx<RC>* __restrict__ tw,
                                                          const cx<RC>* __restrict__ tw_full, const ColZ cz) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    col_pass_body<G, MODE, SNT, GS, ColZ, RC>(A, gin, gout, ld_win, ld_win2, st_win, st_win2, st_rowmap, tw, tw_full, cz,
+    col_pass_body<G, MODE, SNT, GS, ColZ, RC, ST>(A, gin, gout, ld_win, ld_win2, st_win, st_win2, st_rowmap, tw, tw_full, cz,
                                     __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63, blockIdx.x,
                                     blockIdx.y, blockIdx.z + A.z0, smem);
 }
@@ -450,6 +480,6 @@ constexpr int kColPassMaxLog = 10;  // 1024 points: 32-column tiles
 
 int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s);
 int init_col_pass();
-bool col_pass_f64_supported(int logn);  // float64-arithmetic instances (ColPassArgs::f64)
+bool col_pass_f64_supported(int logn);  // float64-arithmetic instances (ColPassArgs::f64; also the complex128 ones)
 
 }  // namespace swf

@@ -44,7 +44,7 @@ struct SumFinishArgs {
     const cx<float>* tw_x;
 };
 
-template <int LOGM, int LOGX>
+template <int LOGM, int LOGX, typename R = float>
 struct SFGeo {
     // threads per row: one wave up to 2048-point rows (rows are wave-private: no workgroup barriers); FOUR waves for
     // 4096-point rows: the 35 KB accumulator row limits a CU to 3 rows, so the waves have to come from within the row
@@ -57,13 +57,13 @@ struct SFGeo {
     // a CU (four rows per workgroup = 87 KB = one workgroup of four waves per CU: measured r3 on the N = 8192
     // workload, 485 us per wave of 8 subgrids); 4096-point rows: the row IS the workgroup (four waves)
     static constexpr int NT = LOGX >= 12 ? 256 : (LOGX == 11 ? 64 : kSumFinishThreads);
-    using GM = Geo<float, LOGM, LOGM - LOGTR, NT, false>;
-    using GX = Geo<float, LOGX, LOGX - LOGTR, NT, false>;
+    using GM = Geo<R, LOGM, LOGM - LOGTR, NT, false>;
+    using GX = Geo<R, LOGX, LOGX - LOGTR, NT, false>;
     static_assert(LOGM - LOGTR >= 1, "at least two points per lane");
     static_assert(GM::T == TR && GX::T == TR, "TR threads per row");
     static constexpr int RB = NT / TR;
-    static constexpr size_t LDS_M = (size_t)RB * GM::PITCH * 8;
-    static constexpr size_t LDS_X = (size_t)RB * GX::PITCH * 8;
+    static constexpr size_t LDS_M = (size_t)RB * GM::PITCH * 2 * sizeof(R);
+    static constexpr size_t LDS_X = (size_t)RB * GX::PITCH * 2 * sizeof(R);
     static constexpr size_t LDS_BYTES = LDS_M + LDS_X;
 };
 
@@ -94,14 +94,14 @@ constexpr size_t sum_finish_facets_lds() {
 // buffer and would admit 32 instead of 16 waves per CU, but the <9,10> instance needs 113 VGPRs: at 5 waves per SIMD
 // (96 VGPRs, 64 B of scratch per lane) the subgrid side takes 9.58 instead of 8.98 ms per pass, at 8 waves per SIMD (64
 // VGPRs, 184 B of scratch) 14.1 ms; not kept)
-template <int LOGM, int LOGX>
+template <int LOGM, int LOGX, typename R = float>
 constexpr size_t sum_finish_facets_reg_lds() {
-    using S = SFGeo<LOGM, LOGX>;
-    return (S::LDS_X > S::LDS_M ? S::LDS_X : S::LDS_M) + ((size_t)4 << LOGM);
+    using S = SFGeo<LOGM, LOGX, R>;
+    return (S::LDS_X > S::LDS_M ? S::LDS_X : S::LDS_M) + (sizeof(R) << LOGM);
 }
-template <int LOGM, int LOGX>
+template <int LOGM, int LOGX, typename R = float>
 constexpr size_t sum_finish_facets_kernel_lds() {
-    return SFWide<LOGM, LOGX>::ON ? SFWide<LOGM, LOGX>::LDS_BYTES : sum_finish_facets_reg_lds<LOGM, LOGX>();
+    return SFWide<LOGM, LOGX>::ON ? SFWide<LOGM, LOGX>::LDS_BYTES : sum_finish_facets_reg_lds<LOGM, LOGX, R>();
 }
 
 template <int LOGM, int LOGX>
@@ -223,29 +223,44 @@ struct SumFinishFacetArgs {
 };
 
 // (register form, 1024-point rows: 4 waves per SIMD = 16 rows per CU, which the 8.7 KB of LDS per row now allow)
-template <int LOGM, int LOGX>
-__global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void sum_finish_facets_kernel(const SumFinishFacetArgs A) {
-    using S = SFGeo<LOGM, LOGX>;
+// R = double: complex128 G / out, double Fn / mask / twiddle tables (the pointers of SumFinishFacetArgs reinterpreted), plain
+// (not compact) twiddle tables; register form only
+// (complex128: at least two waves per SIMD, i.e. up to 256 VGPRs -- the accumulator row of doubles spills at 128)
+template <int LOGM, int LOGX, typename R = float>
+__global__ __launch_bounds__((SFGeo<LOGM, LOGX, R>::NT), (!std::is_same_v<R, float> ? 2 : LOGX <= 10 ? 4 : 1)) void sum_finish_facets_kernel(const SumFinishFacetArgs A) {
+    using S = SFGeo<LOGM, LOGX, R>;
     using GX = typename S::GX;
     using W = SFWide<LOGM, LOGX>;
     using GM = std::conditional_t<W::ON, typename W::GM, typename S::GM>;
+    static_assert(std::is_same_v<R, float> || !W::ON, "complex128: register form only");
+    constexpr bool F32 = std::is_same_v<R, float>;
+    using GMC = std::conditional_t<F32, SFCompact<GM>, GM>;
+    using GXC = std::conditional_t<F32, SFCompact<GX>, GX>;
+    const cx<R>* g_in = reinterpret_cast<const cx<R>*>(A.in);
+    cx<R>* g_out = reinterpret_cast<cx<R>*>(A.out);
+    const R* g_fn = reinterpret_cast<const R*>(A.fn);
+    const R* g_mask = reinterpret_cast<const R*>(A.mask);
+    const cx<R>* tw_m = reinterpret_cast<const cx<R>*>(A.tw_m);
+    const cx<R>* tw_x = reinterpret_cast<const cx<R>*>(A.tw_x);
+    const cx<R>* twc_m = F32 ? reinterpret_cast<const cx<R>*>(A.twc_m) : nullptr;
+    const cx<R>* twc_x = F32 ? reinterpret_cast<const cx<R>*>(A.twc_x) : nullptr;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    cx<float>* ex_m = reinterpret_cast<cx<float>*>(smem);
+    cx<R>* ex_m = reinterpret_cast<cx<R>*>(smem);
     // (wave-parallel form: accumulator row in LDS behind the m-point exchange buffers; register form: one exchange
     // buffer per row shared by both transforms, then the Fn table)
-    cx<float>* acc = reinterpret_cast<cx<float>*>(smem + (W::ON ? W::LDS_M : 0));
+    cx<R>* acc = reinterpret_cast<cx<R>*>(smem + (W::ON ? W::LDS_M : 0));
     constexpr int M = GM::N, X = GX::N, PM = GM::P, PX = GX::P, TR = S::TR;
     const int t = threadIdx.x % TR, rb = threadIdx.x / TR;
     const int b = blockIdx.y;
     const int row0 = blockIdx.x * S::RB;
     const int row = row0 + rb;
     const bool live = row < A.nrows;
-    cx<float> y[PX];  // register form: the lane's part of the accumulator row, y[v] = row[t + v * TR]
+    cx<R> y[PX];  // register form: the lane's part of the accumulator row, y[v] = row[t + v * TR]
 
     if constexpr (W::ON) {
         static_for<0, PX>([&](auto vI) {
             constexpr int v = decltype(vI)::value;
-            acc[lds_pos<GX>(rb, t + v * TR, false)] = cx<float>{0.f, 0.f};
+            acc[lds_pos<GX>(rb, t + v * TR, false)] = cx<R>{(R)0, (R)0};
         });
         row_sync<GX>(false);
     }
@@ -261,8 +276,8 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
                 const int i = i0 + wv;  // wave-uniform
                 if (i < A.rstart[r + 1]) {
                     const int g = A.rgroup[i];
-                    cx<float> xs[PM];
-                    static_for<0, PM>([&](auto vI) { xs[decltype(vI)::value] = cx<float>{0.f, 0.f}; });
+                    cx<R> xs[PM];
+                    static_for<0, PM>([&](auto vI) { xs[decltype(vI)::value] = cx<R>{(R)0, (R)0}; });
                     bool anyg = false;
                     int n = A.gstart[g];
                     const int ne = A.gstart[g + 1];
@@ -275,13 +290,13 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
                         }
                         if (cnt == 0) break;
                         anyg = true;
-                        cx<float> x[NBW][PM];
+                        cx<R> x[NBW][PM];
                         static_for<0, NBW>([&](auto sI) {
                             constexpr int sl = decltype(sI)::value;
                             if (sl < cnt) {  // wave-uniform
                                 const int nn = fs[sl];
                                 const int k = (row - A.base0[nn]) & (X - 1);
-                                const cx<float>* __restrict__ in = A.in + (long long)A.fidx[nn] * A.in_fs +
+                                const cx<R>* __restrict__ in = g_in + (long long)A.fidx[nn] * A.in_fs +
                                                                    (long long)b * A.in_bs + (long long)(live ? k : 0) * A.in_rs;
                                 static_for<0, PM>([&](auto vI) {
                                     constexpr int v = decltype(vI)::value;
@@ -289,7 +304,7 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
                                 });
                             }
                         });
-                        const float lw = live ? 1.f : 0.f;
+                        const R lw = live ? (R)1 : (R)0;
                         static_for<0, NBW>([&](auto sI) {
                             constexpr int sl = decltype(sI)::value;
                             if (sl < cnt) {
@@ -303,17 +318,17 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
                     }
                     if (anyg) {
                         const int sp = A.gsp1[g];
-                        fft_phases<SFCompact<GM>, float, 0>(xs, lane, wv, false, ex_m, A.tw_m, [&](int e, cx<float> v) {
+                        fft_phases<GMC, R, 0>(xs, lane, wv, false, ex_m, tw_m, [&](int e, cx<R> v) {
                             const int ck = e ^ (M >> 1);
                             const int kk = (ck - sp) & (M - 1);
                             const int dest = (kk + (X >> 1) - (M >> 1) + sp) & (X - 1);
-                            const float w = A.fn[kk];
-                            cx<float>* p = acc + lds_pos<GX>(0, dest ^ (X >> 1), false);
-                            cx<float> o = *p;
+                            const R w = g_fn[kk];
+                            cx<R>* p = acc + lds_pos<GX>(0, dest ^ (X >> 1), false);
+                            cx<R> o = *p;
                             o.x += v.x * w;
                             o.y += v.y * w;
                             *p = o;
-                        }, nullptr, A.twc_m);
+                        }, nullptr, twc_m);
                     }
                 }
             }
@@ -338,16 +353,16 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
     static_assert(S::LDS_X >= S::LDS_M, "one exchange buffer per row, sized by the longer transform");
     constexpr int RATIO = X / M;
     static_assert(PX == PM * RATIO, "accumulator slots");
-    cx<float>* ex_row = reinterpret_cast<cx<float>*>(smem) + (size_t)rb * GX::PITCH;  // this row's exchange buffer (rb = 0 addressing)
-    float* fn_l = reinterpret_cast<float*>(smem + (S::LDS_X > S::LDS_M ? S::LDS_X : S::LDS_M));
-    for (int i = threadIdx.x; i < M; i += S::NT) fn_l[i] = A.fn[i];
-    static_for<0, PX>([&](auto vI) { y[decltype(vI)::value] = cx<float>{0.f, 0.f}; });
+    cx<R>* ex_row = reinterpret_cast<cx<R>*>(smem) + (size_t)rb * GX::PITCH;  // this row's exchange buffer (rb = 0 addressing)
+    R* fn_l = reinterpret_cast<R*>(smem + (S::LDS_X > S::LDS_M ? S::LDS_X : S::LDS_M));
+    for (int i = threadIdx.x; i < M; i += S::NT) fn_l[i] = g_fn[i];
+    static_for<0, PX>([&](auto vI) { y[decltype(vI)::value] = cx<R>{(R)0, (R)0}; });
     __syncthreads();
     // (8 points per lane and 1024-point rows: two facets in flight keep the kernel at 128 VGPRs without spills)
     constexpr int NB = (PM >= 8 && LOGX <= 10 && kSumFinishInFlight > 2) ? 2 : kSumFinishInFlight;
     for (int g = 0; g < A.ngroups; g++) {  // workgroup-uniform
-        cx<float> xs[PM];
-        static_for<0, PM>([&](auto vI) { xs[decltype(vI)::value] = cx<float>{0.f, 0.f}; });
+        cx<R> xs[PM];
+        static_for<0, PM>([&](auto vI) { xs[decltype(vI)::value] = cx<R>{(R)0, (R)0}; });
         bool anyg = false;
         int n = A.gstart[g];
         const int ne = A.gstart[g + 1];
@@ -362,17 +377,17 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
             }
             if (cnt == 0) break;
             anyg = true;
-            cx<float> x[NB][PM];
-            float wgt[NB];
+            cx<R> x[NB][PM];
+            R wgt[NB];
             static_for<0, NB>([&](auto sI) {
                 constexpr int sl = decltype(sI)::value;
                 if (sl < cnt) {  // uniform
                     const int nn = fs[sl];
                     const int k = (row - A.base0[nn]) & (X - 1);
                     const bool on = live && k < M;
-                    const cx<float>* __restrict__ in =
-                        A.in + (long long)A.fidx[nn] * A.in_fs + (long long)b * A.in_bs + (long long)(on ? k : 0) * A.in_rs;
-                    wgt[sl] = on ? 1.f : 0.f;
+                    const cx<R>* __restrict__ in =
+                        g_in + (long long)A.fidx[nn] * A.in_fs + (long long)b * A.in_bs + (long long)(on ? k : 0) * A.in_rs;
+                    wgt[sl] = on ? (R)1 : (R)0;
                     // placed rows are indexed by kk = (centred output index - s'1) mod m of the slot the value lands in
                     const int rot = A.placed ? A.gsp1[g] : 0;
                     static_for<0, PM>([&](auto vI) {
@@ -403,14 +418,14 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
                 const int c = p >> LOGM;
                 static_for<0, RATIO>([&](auto cI) {
                     constexpr int cc = decltype(cI)::value;
-                    const float wc = c == cc ? 1.f : 0.f;
+                    const R wc = c == cc ? (R)1 : (R)0;
                     y[v + PM * cc].x += xs[v].x * wc;
                     y[v + PM * cc].y += xs[v].y * wc;
                 });
             });
             continue;
         }
-        fft_phases<SFCompact<GM>, float, 0>(xs, t, 0, false, ex_row, A.tw_m, [&](int e, cx<float> v, auto sI) {
+        fft_phases<GMC, R, 0>(xs, t, 0, false, ex_row, tw_m, [&](int e, cx<R> v, auto sI) {
             // slot = u * RAD + r of the last phase (radix RAD = 2^LR, NB = PM / RAD blocks): e = t + TR * (u + NB * r)
             constexpr int LR = GM::LOGN % GM::LOGP == 0 ? GM::LOGP : GM::LOGN % GM::LOGP, RAD = 1 << LR, NBL = PM / RAD;
             constexpr int slot = (decltype(sI)::value / RAD) + NBL * (decltype(sI)::value % RAD);
@@ -418,14 +433,14 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
             const int kk = (ck - sp) & (M - 1);
             const int p = (kk - (M >> 1) + sp) & (X - 1);  // plain inverse-transform index of the placed element
             const int c = p >> LOGM;
-            const float w = fn_l[kk];
+            const R w = fn_l[kk];
             static_for<0, RATIO>([&](auto cI) {
                 constexpr int cc = decltype(cI)::value;
-                const float wc = c == cc ? w : 0.f;
+                const R wc = c == cc ? w : (R)0;
                 y[slot + PM * cc].x += v.x * wc;
                 y[slot + PM * cc].y += v.y * wc;
             });
-        }, nullptr, A.twc_m);
+        }, nullptr, twc_m);
         row_sync<GX>(false);  // the exchange buffer is reused by the next group
     }
     static_for<0, PX>([&](auto vI) { y[decltype(vI)::value].y = -y[decltype(vI)::value].y; });  // inverse = conj(FFT(conj(.)))
@@ -436,47 +451,47 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT), (LOGX <= 10 ? 4 : 1)) void
     if constexpr (W::ON) {
         static_for<0, PX>([&](auto vI) {
             constexpr int v = decltype(vI)::value;
-            cx<float> val = acc[lds_pos<GX>(rb, t + v * TR, false)];
+            cx<R> val = acc[lds_pos<GX>(rb, t + v * TR, false)];
             val.y = -val.y;  // inverse transform = conj(FFT(conj(.)))
             y[v] = val;
         });
         row_sync<GX>(false);
     }
-    cx<float>* __restrict__ out = A.out + (long long)b * A.out_bs + (long long)(live ? row : 0) * A.out_rs;
-    const float* __restrict__ mask = A.mask ? A.mask + (long long)b * A.mask_bs : nullptr;
+    cx<R>* __restrict__ out = g_out + (long long)b * A.out_bs + (long long)(live ? row : 0) * A.out_rs;
+    const R* __restrict__ mask = A.mask ? g_mask + (long long)b * A.mask_bs : nullptr;
     const int st_a = A.st_a[b];
-    const float scale = 1.f / (float)X;
+    const R scale = (R)1 / (R)X;
     if constexpr (!W::ON) {
         // r4: the mask values of the lane's PX outputs are requested together BEFORE the transform (output slot s of the
         // last phase is element e = t + TR * (u + NB r)) instead of inside the store loop (fewer branches; measured r4,
         // same box: 251.9 vs 253.7 us per wave for sum_finish + K5b, i.e. no difference)
         constexpr int LRX = GX::LOGN % GX::LOGP == 0 ? GX::LOGP : GX::LOGN % GX::LOGP, RADX = 1 << LRX, NBX = PX / RADX;
-        float mw[PX];
+        R mw[PX];
         static_for<0, PX>([&](auto sI) {
             constexpr int sl = decltype(sI)::value;
             constexpr int vi = (sl / RADX) + NBX * (sl % RADX);
             const int d = (((t + TR * vi) ^ (X >> 1)) + st_a) & (X - 1);
             const bool ok = d < A.xA && live;
-            mw[sl] = mask ? mask[ok ? d : 0] : 1.f;
+            mw[sl] = mask ? mask[ok ? d : 0] : (R)1;
         });
-        fft_phases<SFCompact<GX>, float, 0>(y, t, rb, false, acc, A.tw_x, [&](int e, cx<float> v, auto sI) {
+        fft_phases<GXC, R, 0>(y, t, rb, false, acc, tw_x, [&](int e, cx<R> v, auto sI) {
             constexpr int sl = decltype(sI)::value;
             const int ck = e ^ (X >> 1);
             const int d = (ck + st_a) & (X - 1);
-            const float w = scale * mw[sl];
-            if (d < A.xA && live) out[d] = cx<float>{v.x * w, -v.y * w};
-        }, nullptr, A.twc_x);
+            const R w = scale * mw[sl];
+            if (d < A.xA && live) out[d] = cx<R>{v.x * w, -v.y * w};
+        }, nullptr, twc_x);
         return;
     }
-    fft_phases<SFCompact<GX>, float, 0>(y, t, rb, false, acc, A.tw_x, [&](int e, cx<float> v) {
+    fft_phases<GXC, R, 0>(y, t, rb, false, acc, tw_x, [&](int e, cx<R> v) {
         const int ck = e ^ (X >> 1);
         const int d = (ck + st_a) & (X - 1);
         if (d < A.xA && live) {
-            float w = scale;
+            R w = scale;
             if (mask) w *= mask[d];
-            out[d] = cx<float>{v.x * w, -v.y * w};
+            out[d] = cx<R>{v.x * w, -v.y * w};
         }
-    }, nullptr, A.twc_x);
+    }, nullptr, twc_x);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -704,9 +719,11 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT)) void split_prepare_facets_
 
 int launch_split_prepare_facets(int logm, int logx, const SplitFacetArgs& a, int nbatch, hipStream_t s);
 int launch_sum_finish_facets(int logm, int logx, const SumFinishFacetArgs& a, int nbatch, hipStream_t s);
+int launch_sum_finish_facets_c128(int logm, int logx, const SumFinishFacetArgs& a, int nbatch, hipStream_t s);
 int launch_sum_finish_rows(int logm, int logx, const SumFinishArgs& a, int nbatch, hipStream_t s);
 int init_sum_finish_rows();
 bool sum_finish_supported(int logm, int logx);
+bool sum_finish_c128_supported(int logm, int logx);  // complex128 sum_finish_facets_kernel instances
 int launch_axis1_rows(int logm, const Axis1RowsArgs& a, int nfacets, hipStream_t s);
 
 }  // namespace swf

@@ -567,8 +567,22 @@ class SwiftlyCoreHip:
         pairs = {(7, 8), (7, 10), (8, 9), (8, 10), (9, 10), (9, 11), (10, 11), (10, 12)}  # sum_finish instances
         return logs["m"] <= 10 and (logs["m"], logs["xM"]) in pairs  # m: single-pass column transform
 
-    def supports_band_pipeline(self, dtype=None, n_facets=None):
-        """True when the contiguous-axis-first forward kernels (include/swiftly_hip.h) exist for these sizes."""
+    #: (m, xM) pairs of the complex128 sum_finish_facets instances (csrc/sum_finish.hip, SF_PAIRS_C128)
+    C128_FUSED_PAIRS = frozenset({(7, 8), (7, 10), (8, 9), (8, 10), (9, 10)})
+
+    def supports_band_pipeline(self, dtype=None, n_facets=None, explicit=False):
+        """True when the contiguous-axis-first forward kernels (include/swiftly_hip.h) exist for these sizes.
+
+        ``explicit=True`` also answers for complex128, whose pipeline runs only when asked for (``SwiftlyForward(...,
+        wave_axis=1)``): power-of-two ``yN_size`` of 64 .. 32768 in the plain band layout (whole padded axis kept),
+        ``m`` of 64 .. 512 and an (m, xM) pair with a complex128 ``sum_finish_facets`` instance.  With the default the
+        answer for complex128 is False: nothing picks that pipeline on its own."""
+        torch = _torch()
+        if explicit and dtype == torch.complex128:
+            logs = self._logs()
+            if logs is None or (n_facets is not None and n_facets > self.MAX_FUSED_FACETS):
+                return False
+            return 6 <= logs["yN"] <= 15 and 6 <= logs["m"] <= 9 and (logs["m"], logs["xM"]) in self.C128_FUSED_PAIRS
         # K1: the two-workgroup band kernel for yN = 16384 .. 65536 (band-pruned output), the generic contiguous-axis
         # transform below that (whole padded axis kept)
         # yN = Q * 2^k (r3): the radix-Q pass in front of the same kernels, whole padded axis kept, forward only
@@ -700,7 +714,7 @@ class SwiftlyCoreHip:
             out = torch.empty((F, n_rows, m), dtype=bands.dtype, device=self._device)
         # one wave through the multi-wave entry point: it takes the caller-owned four-step scratch (a stream-ordered
         # allocation per call costs host time, see swiftly_hip.h)
-        scr = self.scratch("k2", self._k2_scratch_bytes(F))
+        scr = self.scratch("k2", self._k2_scratch_bytes(F, bands.element_size()))
         cvp = ctypes.c_void_p
         _lib.check(
             self._lib.swiftly_hip_prepare_facet_columns_waves(
@@ -755,9 +769,10 @@ class SwiftlyCoreHip:
             arr = cls._I64_CACHE[key] = (ctypes.c_int64 * len(key))(*[int(v) for v in key])
         return arr
 
-    def _k2_scratch_bytes(self, F):
-        """four-step scratch of K2 for F facets; yN = Q * 2^k also holds the output of the radix-Q pass"""
-        n = F * self.yN_size * self.xM_yN_size * 8
+    def _k2_scratch_bytes(self, F, element_size=8):
+        """four-step scratch of K2 for F facets (``element_size``: 8 = complex64, 16 = complex128); yN = Q * 2^k also holds
+        the output of the radix-Q pass"""
+        n = F * self.yN_size * self.xM_yN_size * int(element_size)
         return n if self._mixed_yN() is None else 2 * n + 4096
 
     SCRATCH_TAIL_BYTES = 1 << 16
@@ -784,7 +799,7 @@ class SwiftlyCoreHip:
         ``[F, S, m, m]`` tensor, or a flat send buffer with ``g_layout = (offsets[S], facet_strides[S])``."""
         F, S = Q.shape[0], len(sub_off0s)
         cvp = ctypes.c_void_p
-        scr = self.scratch("k2", self._k2_scratch_bytes(F)) if compute_q else None
+        scr = self.scratch("k2", self._k2_scratch_bytes(F, Q.element_size())) if compute_q else None
         if g_layout is None:
             fs, ss, offs, fstr = g_out.stride(0), g_out.stride(1), None, None
         else:
@@ -850,7 +865,7 @@ class SwiftlyCoreHip:
         (``finish_axis1_rows`` ran before K2): their rows already are ``Fn * cfft_m`` along the contiguous axis."""
         F, S = G.shape[0], G.shape[1]
         cvp = ctypes.c_void_p
-        scr = self.scratch("k5b", min(S, 64) * self.xM_size * int(subgrid_size) * 8)
+        scr = self.scratch("k5b", min(S, 64) * self.xM_size * int(subgrid_size) * G.element_size())
         # axis-1-first pipeline: the rows of G already are Fn * cfft_m along the contiguous axis (finish_axis1_rows)
         entry = self._lib.swiftly_hip_wave_subgrid_side_placed if placed else self._lib.swiftly_hip_wave_subgrid_side
         _lib.check(

@@ -394,7 +394,13 @@ class SwiftlyForward(WavePrefetch):
     # -- contiguous-axis-first pipeline (wave_axis == 1) ---------------------------
     def _check_band_pipeline(self):
         torch = _torch()
-        if not self.core.supports_band_pipeline(self.dtype):
+        if not self.core.supports_band_pipeline(self.dtype, explicit=True):
+            if self.dtype == torch.complex128:
+                raise ValueError(
+                    "wave_axis=1 is not available for complex128 facets of this configuration (power-of-two yN_size up to "
+                    "32768, contribution size 64 .. 512 and a complex128 sum_finish_facets instance for (m, xM): see "
+                    "core.supports_band_pipeline(torch.complex128, explicit=True))"
+                )
             raise ValueError("wave_axis=1 is not available for this configuration / dtype (see preferred_wave_axis)")
         if len(self.facet_configs) > self.core.MAX_FUSED_FACETS:
             raise ValueError(
@@ -402,8 +408,9 @@ class SwiftlyForward(WavePrefetch):
                 f"got {len(self.facet_configs)}; use wave_axis=0 (preferred_wave_axis(config, dtype, n_facets=...))"
             )
         sizes = {info[1] for info in self._facet_info}
-        if len(sizes) != 1 or not all(info[2] for info in self._facet_info) or self.dtype != torch.complex64:
-            raise ValueError("wave_axis=1 needs equally sized row-major complex64 facets")
+        if len(sizes) != 1 or not all(info[2] for info in self._facet_info) or self.dtype not in (torch.complex64,
+                                                                                                  torch.complex128):
+            raise ValueError("wave_axis=1 needs equally sized row-major complex64 or complex128 facets")
 
     def _prepare_all_bands(self, timer=None):
         """K1: band buffers ``[F, yB, band columns]`` -- prepare_facet along axis 1 of every facet row, only the
@@ -416,8 +423,10 @@ class SwiftlyForward(WavePrefetch):
             self._check_band_pipeline()
             torch = _torch()
             core = self.core
+            # (complex128: K1 keeps the whole padded axis in the plain band layout)
             self._band = (
-                core.band_for_offsets([sg.off1 for sg in self._plan]) if self._plan is not None else (0, core.yN_size)
+                core.band_for_offsets([sg.off1 for sg in self._plan])
+                if self._plan is not None and self.dtype == torch.complex64 else (0, core.yN_size)
             )
             F, yB = len(self._facet_info), self._facet_info[0][1][0]
             mode = self.__dict__["_axis1_mode"] = self._choose_axis1_mode()
@@ -471,6 +480,8 @@ class SwiftlyForward(WavePrefetch):
         ``True`` where 2 is not available); 2: axis-1-first with the finish in the epilogue of K1 (``axis1_first=True``;
         needs a plan -- the windows are the plan's waves -- and a configuration with core.supports_window_rows)."""
         if not (self.wave_axis == 1 and bool(getattr(self.core, "axis1_first", False))):
+            return 0
+        if self.dtype != _torch().complex64:  # (a float32 accuracy mode: complex128 runs the default order)
             return 0
         if (self.core.axis1_first is True and self.axis1_fused and self._plan is not None and self._band is not None and
                 self.core.supports_window_rows(self._band, self._facet_info[0][1][1], [cfg.off1 for cfg in self.facet_configs],
@@ -587,7 +598,8 @@ def _finish_from_columns(core, src, layout, facet_configs, sgs, window_offs, row
     torch = _torch()
     xM, xA, S = core.xM_size, sgs[0].size, len(sgs)
     dt, dev = src.dtype, core.device
-    if dt != torch.complex64:
+    # (complex128: the row-window layout of the band pipeline only; the column-buffer layout 0 stays complex64)
+    if dt != torch.complex64 and not (dt == torch.complex128 and layout == 1):
         raise NotImplementedError("fused subgrid path is complex64 only")
     off0s = [cfg.off0 for cfg in facet_configs]
     off1s = [cfg.off1 for cfg in facet_configs]
