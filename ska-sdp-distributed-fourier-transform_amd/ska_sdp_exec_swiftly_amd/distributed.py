@@ -483,6 +483,9 @@ class DistributedForward:
         yB = self.facet_configs[j].size
         fwd.BF_Fs_persist = recv.view(1, yB, 2 * h)
         fwd._band = b  # pylint: disable=protected-access
+        # the band buffer did not come from the object's own K1, which is where it would have chosen its axis-1-first mode:
+        # choose it here (axis1_fused is off: a row pass per wave in front of K2, or 0), as the receiver's placed mode expects
+        fwd.__dict__["_axis1_mode"] = fwd._choose_axis1_mode()  # pylint: disable=protected-access
 
     def prepare_all_facets(self):
         """K1 for the local facets; cooperative facets: K1 on this rank's rows and the exchange of the band rows"""
@@ -493,6 +496,13 @@ class DistributedForward:
             for j in self.sharding.coop:
                 send, in_counts, out_counts = self.pack_coop(j)
                 self.unpack_coop(j, exchange_blocks(send, in_counts, out_counts, self.group).wait())
+
+    def _senders_placed(self):
+        """the ``placed`` argument of the subgrid side for received blocks: what the senders did -- every rank's forward
+        objects (local and cooperative) choose their axis-1-first mode from the same core, wave axis and dtype"""
+        from .forward import axis1_first_active  # pylint: disable=import-outside-toplevel
+
+        return axis1_first_active(self.core, self.wave_axis, self.dtype)
 
     def wave_key(self, sgs):
         """key of the wave ``sgs`` (``off1``, or ``off0`` in the reference schedule)"""
@@ -564,7 +574,7 @@ class DistributedForward:
         cfgs = self._arrival_cfgs(key)
         blocks = recv.view(len(cfgs), len(mine), m, m)  # facets in arrival order
         res = finish_from_blocks(self.core, blocks, cfgs, [sgs[i] for i in mine], transformed=self.fused,
-                                 placed=int(self.wave_axis == 1 and bool(getattr(self.core, "axis1_first", False))))
+                                 placed=self._senders_placed())
         return mine, res
 
     def start_wave(self, sgs):

@@ -479,9 +479,7 @@ class SwiftlyForward(WavePrefetch):
         """0: default order; 1: axis-1-first with a row pass per wave (core.finish_axis1_rows; ``axis1_first="rows"``, or
         ``True`` where 2 is not available); 2: axis-1-first with the finish in the epilogue of K1 (``axis1_first=True``;
         needs a plan -- the windows are the plan's waves -- and a configuration with core.supports_window_rows)."""
-        if not (self.wave_axis == 1 and bool(getattr(self.core, "axis1_first", False))):
-            return 0
-        if self.dtype != _torch().complex64:  # (a float32 accuracy mode: complex128 runs the default order)
+        if not axis1_first_active(self.core, self.wave_axis, self.dtype):
             return 0
         if (self.core.axis1_first is True and self.axis1_fused and self._plan is not None and self._band is not None and
                 self.core.supports_window_rows(self._band, self._facet_info[0][1][1], [cfg.off1 for cfg in self.facet_configs],
@@ -590,6 +588,14 @@ class SwiftlyForward(WavePrefetch):
         if compute:  # (this wave's own K2 was enqueued on the current stream just now: the next one goes behind it)
             self._prefetch_waves(nxt)
         return _finish_from_G(core, G, self.facet_configs, sgs, placed=self._placed())
+
+
+def axis1_first_active(core, wave_axis, dtype):
+    """does a forward object of this core, wave axis and dtype send blocks finished along axis 1 (axis-1-first pipeline,
+    either form)?  One rule for the senders (``_choose_axis1_mode``) and for whoever finishes their blocks (``placed``)."""
+    if not (wave_axis == 1 and bool(getattr(core, "axis1_first", False))):
+        return False
+    return dtype == _torch().complex64  # (a float32 accuracy mode: complex128 runs the default order)
 
 
 def _finish_from_columns(core, src, layout, facet_configs, sgs, window_offs, rowmap=None, band=None, placed=False):

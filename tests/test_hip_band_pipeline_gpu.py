@@ -835,6 +835,71 @@ def test_cooperative_facets_virtual_ranks(world, whole_waves):
         assert float((done[j] - w).abs().pow(2).mean().sqrt()) <= 3e-6 * float(w.abs().pow(2).mean().sqrt()), j
 
 
+@pytest.mark.parametrize("world", [2, 8])
+def test_axis1_first_with_cooperative_facets_virtual_ranks(world):
+    """``SwiftlyConfig(axis1_first=True)`` with the default ``cooperative=True``: 3 facets on 2 ranks (facet 2 worked on by
+    both) and on 8 ranks (all three cooperative), forward only.  A cooperative facet's band buffer arrives through the
+    band-row exchange instead of the object's own K1; its blocks must still be finished along axis 1 in front of K2
+    (row pass per wave), because the receiver finishes every block in placed mode.  Expected: the single-process
+    ``SwiftlyForward`` of the same configuration (bound of test_axis1_first_through_the_multi_gpu_classes) and the
+    separable oracle (the module's end-to-end 2e-5).
+
+    Before the cooperative objects chose their axis-1-first mode in ``unpack_coop`` they sent default-order blocks to a
+    placed-mode receiver: max|got - want| / max|want| = 0.69 against the single-process object and relative RMSE 0.64
+    against the oracle at world 2, 1.02 and 1.00 at world 8 (measured on an MI355X; 2.2e-7 and 4.5e-7 now)."""
+    import torch
+
+    import ska_sdp_exec_swiftly_amd as sw
+    from ska_sdp_exec_swiftly_amd.distributed import DistributedForward
+
+    _, _, cfg0, facet_cfgs, facets, sg_cfgs = _small_rows_problem(seed=95)
+    if not cfg0.core.supports_band_pipeline(torch.complex64):
+        pytest.skip("band pipeline not available")
+    P = dict(W=W64, fov=1.0, N=N64, yB_size=352, yN_size=yN64, xA_size=928, xM_size=xM64)
+    cfg = sw.SwiftlyConfig(backend="hip", axis1_first=True, **P)
+    so = sep.SeparableOracle(core64()[1], [orc.CoverItem(c.off0, c.off1, c.size) for c in facet_cfgs],
+                             [sep.facet_vectors(95 + j, 352, rank=2) for j in range(3)])
+    ref = sw.SwiftlyForward(cfg, list(zip(facet_cfgs, facets)), subgrid_configs=sg_cfgs, wave_axis=1)
+    fwds = [DistributedForward(cfg, facet_cfgs, facets, subgrid_configs=sg_cfgs, wave_axis=1, dtype=torch.complex64,
+                               rank_world=(r, world)) for r in range(world)]
+    sh = fwds[0].sharding
+    assert sh.coop == ([2] if world == 2 else [0, 1, 2])
+    for f in fwds:
+        f.prepare_all_facets()
+    for j in sh.coop:
+        packed = [f.pack_coop(j) for f in fwds]
+        recvs = _virtual_all_to_all([p[0] for p in packed], [p[1] for p in packed])
+        for r, f in enumerate(fwds):
+            assert recvs[r].numel() == sum(packed[r][2])
+            f.unpack_coop(j, recvs[r])
+    waves = {}
+    for c in sg_cfgs:
+        waves.setdefault(c.off1, []).append(c)
+    worst_ref = worst_orc = 0.0
+    failures = []
+    for key, wave in waves.items():
+        want = ref.get_wave(wave)
+        packed = [f.pack_wave(wave) for f in fwds]
+        recvs = _virtual_all_to_all([p[0] for p in packed], [p[1] for p in packed])
+        got = {}
+        for r, f in enumerate(fwds):
+            assert recvs[r].numel() == sum(packed[r][2])
+            mine, res = f.unpack_wave(wave, recvs[r])
+            for k, i in enumerate(mine):
+                got[i] = res[k]
+        assert sorted(got) == list(range(len(wave)))
+        scale = float(want.abs().max())
+        for i, c in enumerate(wave):
+            e_ref = float((got[i] - want[i]).abs().max()) / scale
+            e_orc = relrms(got[i].cpu().numpy(), so.subgrid(orc.CoverItem(c.off0, c.off1, c.size)))
+            worst_ref, worst_orc = max(worst_ref, e_ref), max(worst_orc, e_orc)
+            if not (e_ref <= 5e-6 and e_orc < 2e-5):
+                failures.append((key, i, e_ref, e_orc))
+    print(f"axis1_first cooperative world {world}: max|err|/max|want| vs single process {worst_ref:.3e}, "
+          f"relative RMSE vs separable oracle {worst_orc:.3e}")
+    assert not failures, failures[:4]
+
+
 _K1_PROBE = r"""
 import hashlib, sys
 import numpy, torch
