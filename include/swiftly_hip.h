@@ -91,6 +91,28 @@ int64_t swiftly_hip_contribution_size(const swiftly_hip_t* h); /* xM*yN/N, core.
  * the precision before a pass instead of meeting SWIFTLY_ERR_UNSUPPORTED halfway through.  (complex64 at 65536 is
  * limited to the prepare_* / finish_* forms named by that error.) */
 int swiftly_hip_supports_dtype(const swiftly_hip_t* h, int dtype);
+/* Which pipelines exist for a configuration: the library's own capability table (csrc/swiftly_caps.h, the functions the
+ * entry points refuse through), answered from the sizes alone -- no handle, no device.  1 = supported; 0 = not, and
+ * swiftly_hip_last_error() says why (also for sizes swiftly_hip_create would reject).  `n_facets` <= 0: not given;
+ * features that do not depend on `dtype` or `n_facets` ignore them. */
+enum {
+    SWIFTLY_FEATURE_FUSED_SUBGRID = 0,          /* transform_contributions + sum_finish_facets (dtype, n_facets) */
+    SWIFTLY_FEATURE_BAND_PIPELINE = 1,          /* contiguous-axis-first forward kernels (dtype, n_facets) */
+    SWIFTLY_FEATURE_BAND_PIPELINE_EXPLICIT = 2, /* ... when the caller asks for them: also answers for complex128 */
+    SWIFTLY_FEATURE_BACKWARD_BAND = 3,          /* accumulate_facet_columns + finish_facet_band (dtype) */
+    SWIFTLY_FEATURE_SPLIT_BAND = 4,             /* band buffers are parity-split and band-pruned (else whole axis, plain) */
+    SWIFTLY_FEATURE_WINDOW_ROWS = 5             /* prepare_facet_window_rows, size part (band / facets / windows: per call) */
+};
+int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
+enum {
+    SWIFTLY_LIMIT_FUSED_FACETS = 0,              /* facets one sum_finish_facets call sums */
+    SWIFTLY_LIMIT_WINDOW_ROWS_STAGE_COLUMNS = 1, /* physical band columns prepare_facet_window_rows can stage */
+    SWIFTLY_LIMIT_WINDOW_ROWS_WINDOWS = 2        /* windows per prepare_facet_window_rows call */
+};
+int64_t swiftly_hip_limit(int which); /* -1 for an unknown limit */
+/* 1 and (Q, k) when n = Q * 2^k with Q in {3, 5, 7, 9} and 2^k >= 8 (one radix-Q pass in front of the power-of-two
+ * kernels), else 0 (powers of two included: they need no pass). */
+int swiftly_hip_mixed_factor(int64_t n, int* Q, int* log2_rest);
 /* Arithmetic of the column passes of the band pipelines on complex64 data (K2 = prepare_facet along the strided axis of
  * a wave, K3 = the m-point transform of add_to_subgrid behind it, and their backward mirrors): 32 (default) = float32
  * throughout; 64 = loads and stores in complex64, windows / butterflies / exchanges / four-step twiddles in float64.

@@ -61,10 +61,7 @@ int launch_axis1_rows(int logm, const Axis1RowsArgs& a, int nfacets, hipStream_t
     }
 }
 
-#define SF_PAIRS(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10) X(9, 11) X(10, 11) X(10, 12)
-// complex128 sum_finish_facets (register form, m-point transform of K3 in one column pass: m <= 512; (9, 11) would keep 32
-// complex128 accumulator values per lane and spills even at 256 VGPRs)
-#define SF_PAIRS_C128(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10)
+// one instance per pair of SF_PAIRS / SF_PAIRS_C128 (swiftly_caps.h, where the gates read the same tables)
 
 int launch_sum_finish_rows(int logm, int logx, const SumFinishArgs& a, int nbatch, hipStream_t s) {
 #define SF_CASE(M, XX) \
@@ -107,17 +104,6 @@ int init_sum_finish_rows() {
     SF_PAIRS_C128(SF_INIT_D)
 #undef SF_INIT_D
     return rc;
-}
-bool sum_finish_supported(int logm, int logx) {
-#define SF_HAS(M, XX) \
-    if (logm == M && logx == XX) return true;
-    SF_PAIRS(SF_HAS)
-    return false;
-}
-bool sum_finish_c128_supported(int logm, int logx) {
-    SF_PAIRS_C128(SF_HAS)
-#undef SF_HAS
-    return false;
 }
 
 }  // namespace swf

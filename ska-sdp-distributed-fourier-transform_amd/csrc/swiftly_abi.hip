@@ -147,21 +147,6 @@ static int make_bluestein(swiftly_hip* h, int64_t n) {
     return rc;
 }
 
-// n = Q * 2^k with Q in {3, 5, 7, 9} and 2^k a length the power-of-two kernels take: Q and k, else false
-bool mixed_factor(int64_t n, int* Q, int* logM) {
-    if (n <= 0) return false;
-    for (int q : {3, 5, 7, 9}) {
-        if (n % q) continue;
-        const int l = ilog2_exact(n / q);
-        if (l >= kMinLogN) {
-            *Q = q;
-            *logM = l;
-            return true;
-        }
-    }
-    return false;
-}
-
 // Tables for a length n = Q * 2^k (swiftly_mixed.h): the full-length twiddles and the power-of-two tables of the
 // sub-transforms (with the halves their strided four-step form uses).
 static int make_mixed(swiftly_hip* h, int64_t n) {
@@ -212,13 +197,7 @@ int swiftly_hip_create(swiftly_hip_t** out, int64_t N, int64_t yN, int64_t xM, d
                        int device) {
     if (!out || !pswf) return fail(SWIFTLY_ERR_PARAM, "null argument");
     *out = nullptr;
-    // parameter checks of core.py:55-74
-    if (N <= 0 || yN <= 0 || xM <= 0) return fail(SWIFTLY_ERR_PARAM, "sizes must be positive");
-    if (N % yN != 0) return fail(SWIFTLY_ERR_PARAM, "Image size %lld not divisible by facet size %lld!", (long long)N, (long long)yN);
-    if (N % xM != 0) return fail(SWIFTLY_ERR_PARAM, "Image size %lld not divisible by subgrid size %lld!", (long long)N, (long long)xM);
-    if ((xM * yN) % N != 0)
-        return fail(SWIFTLY_ERR_PARAM, "Contribution size not integer with image size %lld, subgrid size %lld and facet size %lld!",
-                    (long long)N, (long long)xM, (long long)yN);
+    if (const std::string bad = check_sizes(N, yN, xM); !bad.empty()) return fail(SWIFTLY_ERR_PARAM, "%s", bad.c_str());
     int ndev = swiftly_hip_device_count();
     if (ndev <= 0) return fail(SWIFTLY_ERR_HIP, "no HIP device visible: the SwiFTly HIP backend has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(SWIFTLY_ERR_PARAM, "invalid device %d", device);
@@ -245,15 +224,9 @@ int swiftly_hip_create(swiftly_hip_t** out, int64_t N, int64_t yN, int64_t xM, d
     }
     swiftly_hip* h = new (std::nothrow) swiftly_hip();
     if (!h) return fail(SWIFTLY_ERR_HIP, "out of host memory");
-    h->N = N;
-    h->yN = yN;
-    h->xM = xM;
-    h->m = xM * yN / N;
+    static_cast<Sizes&>(*h) = make_sizes(N, yN, xM);
     h->W = W;
     h->device = device;
-    h->log_yN = ilog2_exact(yN);
-    h->log_xM = ilog2_exact(xM);
-    h->log_m = ilog2_exact(h->m);
     if (const char* e = getenv("SWIFTLY_COL_F64")) h->col_f64 = atoi(e) != 0;
     if (const char* e = getenv("SWIFTLY_COL_F64_STAGES")) h->col_f64_stages = atoi(e) & 7;
     // windows: 1/pswf (Fb, core.py:104-108) and Fn (core.py:110-117)
@@ -1628,7 +1601,7 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
     if (dtype == SWIFTLY_C128) {
         // complex128: the plain band layout that keeps the whole padded axis, through the complex128 row transforms (one
         // workgroup per row up to 8192 points, the two-kernel long-row form for 16384 / 32768)
-        if (h->log_yN < 3 || h->log_yN > 15)
+        if (h->log_yN < kMinLogN || h->log_yN > kBandMaxLogYNC128)
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: complex128 needs a power-of-two yN_size of 8 .. 32768, got %d", yN);
         if (band_start != 0 || band_len != yN)
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: complex128 keeps the whole padded axis (band must be (0, yN_size))");
@@ -1641,7 +1614,7 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
                                         nullptr, nullptr, fold_other_axis_window, 0, (hipStream_t)stream);
     }
     const bool mixed_yN = h->log_yN < 0 && h->mixed.count(h->yN) && h->mixed.at(h->yN).tw_f;
-    if (!mixed_yN && (h->log_yN < 3 || h->log_yN > 16))
+    if (!mixed_yN && (h->log_yN < kMinLogN || h->log_yN > kBandMaxLogYN))
         return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: padded facet size %d not supported (power of two 8 .. 65536, or Q * 2^k with Q = 3, 5, 7, 9)", yN);
     if (rows < 0 || rows > 0x7fffffff) return fail(SWIFTLY_ERR_PARAM, "bad row count");
     if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN)

@@ -29,6 +29,8 @@
 
 using namespace swf;
 
+static_assert(kFusedMaxLogM == kColPassMaxLog && kBackwardBandMinLogYN == kColPassMinLog, "swiftly_caps.h names the column-pass limits");
+
 // ---------------------------------------------------------------------------
 // error state: integer status + thread-local message (swiftly_hip_last_error)
 int fail(int code, const char* fmt, ...);
@@ -48,18 +50,10 @@ static inline int pmod(int64_t a, int64_t n) {
     if (r < 0) r += n;
     return (int)r;
 }
-static inline int ilog2_exact(int64_t n) {
-    if (n <= 0 || (n & (n - 1))) return -1;
-    int l = 0;
-    while ((int64_t(1) << l) < n) l++;
-    return l;
-}
 
-struct swiftly_hip {
-    int64_t N, yN, xM, m;
+struct swiftly_hip : Sizes {  // N, yN, xM, m and log_yN, log_xM, log_m (swiftly_caps.h)
     double W;
     int device;
-    int log_yN, log_xM, log_m;  // -1 when not a power of two
     float* invp_f = nullptr;    // 1/pswf[k] (k = 0 -> 0)
     double* invp_d = nullptr;
     float* fn_f = nullptr;  // Fn[k], k < m
@@ -160,10 +154,6 @@ static inline const cx<float>* cx_at(const void* p, int64_t k, bool c128) {
 static inline cx<float>* cx_at(void* p, int64_t k, bool c128) {
     return (cx<float>*)((char*)p + k * (int64_t)(c128 ? sizeof(cx<double>) : sizeof(cx<float>)));
 }
-// complex128 band pipeline (K2, K3, sum_finish_facets): power-of-two padded facets up to 32768 points in the plain band
-// layout, m-point transforms in one column pass (m <= 512) and a complex128 sum_finish_facets instance for (m, xM)
-bool band_pipeline_c128_supported(const swiftly_hip* h);
-
 // column-tile passes (swiftly_abi.hip)
 ColZ plain_colz();
 // single-pass launch of length 2^logn: float64 arithmetic when the handle asks for it and the instance exists
@@ -186,8 +176,6 @@ struct CallWorkspace {
 };
 int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz, int W, int nb, hipStream_t st,
                   void* ws = nullptr, size_t ws_bytes = 0, int qmul = 0, int qadd = 0, int full_n = 0);
-// rows kernels / radix-Q pass (swiftly_abi.hip)
-bool mixed_factor(int64_t n, int* Q, int* logM);
 
 // Facet tables of the row-wise fused kernels (swiftly_sumfinish.h), grouped by off1: entries of one group are adjacent.
 template <class Args>
@@ -275,10 +263,7 @@ static inline void fill_group_rounds(SumFinishFacetArgs& a, const swiftly_hip* h
 // tile of the column pass start on a cache line (r2: (band_len + 1) / 2 = 5736 left every odd run 64 bytes off a line:
 // 5 lines fetched per 4 lines' worth, FETCH_SIZE of K2 pass A 1.04 GB per wave against 0.83 GB)
 static inline int64_t band_half_columns(int64_t band_len) { return (((band_len + 1) / 2) + 15) & ~int64_t(15); }
-// Band layout of a handle: parity-split where the two-workgroup long-row kernel produces the band (yN >= 16384), else
-// PLAIN (half = 0: logical column d of the band at physical column d; K1 is the generic contiguous-axis transform and
-// keeps the whole padded axis).
-static inline bool band_is_split(const swiftly_hip* h) { return h->log_yN >= 14 && h->log_yN <= 16; }
+// (half = 0 in the plain band layout: band_is_split, swiftly_caps.h)
 static inline int band_half_of(const swiftly_hip* h, int64_t band_len) {
     return band_is_split(h) ? (int)band_half_columns(band_len) : 0;
 }

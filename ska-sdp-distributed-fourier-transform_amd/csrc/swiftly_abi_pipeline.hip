@@ -24,11 +24,6 @@ __global__ void zero_untouched_kernel(cx<float>* __restrict__ band, const unsign
 }
 
 
-bool band_pipeline_c128_supported(const swiftly_hip* h) {
-    return h->log_yN >= 6 && h->log_yN <= 15 && col_pass_f64_supported(h->log_m) &&
-           sum_finish_c128_supported(h->log_m, h->log_xM);
-}
-
 extern "C" {
 
 int swiftly_hip_sum_finish_rows(swiftly_hip_t* h, int dtype, const void* in, int64_t ngroups, int64_t in_group_stride,
@@ -257,7 +252,7 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
                     "(m, xM) with a complex128 sum_finish_facets instance, got yN_size %lld, m %lld, xM %lld",
                     (long long)h->yN, (long long)h->m, (long long)h->xM);
     const int yN = (int)h->yN, m = (int)h->m;
-    if (h->log_m < 6) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: sizes not supported");
+    if (h->log_m < kBandMinLog) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: sizes not supported");
     if (rows <= 0 || rows >= yN) return fail(SWIFTLY_ERR_PARAM, "facet size %lld must be in [1, yN_size - 1]", (long long)rows);
     if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN) return fail(SWIFTLY_ERR_PARAM, "bad band");
     if (nfacets <= 0 || nwaves <= 0) return 0;
@@ -467,7 +462,7 @@ static int sum_finish_facets_impl(swiftly_hip_t* h, int dtype, const void* in, i
         return fail(SWIFTLY_ERR_UNSUPPORTED, "sum_finish_facets: 1..%d facets supported", kSumFinishMaxFacets);
     if (c128 && (placed || !sum_finish_c128_supported(h->log_m, h->log_xM)))
         return fail(SWIFTLY_ERR_UNSUPPORTED, "sum_finish_facets: complex128 %s", placed ? "has no placed mode (axis-1-first pipeline)"
-                    : "instances exist for (m, xM) = (128, 256), (128, 1024), (256, 512), (256, 1024), (512, 1024)");
+                    : ("instances exist for (m, xM) = " + sum_finish_c128_sizes()).c_str());
     if (!sum_finish_supported(h->log_m, h->log_xM))
         return fail(SWIFTLY_ERR_UNSUPPORTED, "sum_finish_facets: (m, xM) = (%lld, %lld) not instantiated", (long long)h->m,
                     (long long)h->xM);
@@ -483,7 +478,7 @@ static int sum_finish_facets_impl(swiftly_hip_t* h, int dtype, const void* in, i
     fill_facet_groups(a, h, nfacets, facet_off0s, facet_off1s);
     fill_group_rounds(a, h);
     a.placed = placed ? 1 : 0;
-    if (placed && h->log_xM >= 12)
+    if (placed && h->log_xM > kPlacedMaxLogXM)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "axis-1-first pipeline: rows of %lld points run the wave-parallel sum_finish form, "
                     "which has no placed mode", (long long)h->xM);
     a.fn = h->fn_f;
@@ -778,7 +773,7 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
         auto it = h->mixed.find(h->yN);
         if (it != h->mixed.end() && it->second.tw_f && !band_is_split(h)) mx = &it->second;
     }
-    if ((h->log_yN < 0 && !mx) || h->log_m < 0 || h->log_yN > 18)
+    if ((h->log_yN < 0 && !mx) || h->log_m < 0 || h->log_yN > kBackwardBandMaxLogYN)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: sizes not supported (yN a power of two or Q * 2^k, m a power of two)");
     if (nchunks <= 0 || nchunks > kColZC) return fail(SWIFTLY_ERR_PARAM, "1..%d source chunks", kColZC);
     if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN) return fail(SWIFTLY_ERR_PARAM, "bad band");

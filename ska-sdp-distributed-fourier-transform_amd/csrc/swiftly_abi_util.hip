@@ -32,6 +32,41 @@ int swiftly_hip_set_column_precision(swiftly_hip_t* h, int bits) {
 }
 int swiftly_hip_get_column_precision(const swiftly_hip_t* h) { return h ? (h->col_f64 ? 64 : 32) : -1; }
 
+// the capability table (swiftly_caps.h) for callers: sizes in, no handle, no device
+int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets) {
+    std::string why = check_sizes(N, yN_size, xM_size);
+    if (why.empty()) {
+        const Sizes s = make_sizes(N, yN_size, xM_size);
+        switch (feature) {
+            case SWIFTLY_FEATURE_FUSED_SUBGRID: why = why_not_fused_subgrid(s, dtype, n_facets); break;
+            case SWIFTLY_FEATURE_BAND_PIPELINE: why = why_not_band_pipeline(s, dtype, n_facets, false); break;
+            case SWIFTLY_FEATURE_BAND_PIPELINE_EXPLICIT: why = why_not_band_pipeline(s, dtype, n_facets, true); break;
+            case SWIFTLY_FEATURE_BACKWARD_BAND: why = why_not_backward_band(s, dtype); break;
+            case SWIFTLY_FEATURE_SPLIT_BAND: why = why_not_split_band(s); break;
+            case SWIFTLY_FEATURE_WINDOW_ROWS: why = why_not_window_rows(s); break;
+            default: why = reason("unknown feature %d", feature);
+        }
+    }
+    if (why.empty()) return 1;
+    fail(SWIFTLY_ERR_UNSUPPORTED, "%s", why.c_str());
+    return 0;
+}
+int64_t swiftly_hip_limit(int which) {
+    switch (which) {
+        case SWIFTLY_LIMIT_FUSED_FACETS: return kSumFinishMaxFacets;
+        case SWIFTLY_LIMIT_WINDOW_ROWS_STAGE_COLUMNS: return row_pass_whole_stage_columns();
+        case SWIFTLY_LIMIT_WINDOW_ROWS_WINDOWS: return kWholeMaxWindows;
+        default: return -1;
+    }
+}
+int swiftly_hip_mixed_factor(int64_t n, int* Q, int* log2_rest) {
+    int q = 0, l = 0;
+    if (!mixed_factor(n, &q, &l)) return 0;
+    if (Q) *Q = q;
+    if (log2_rest) *log2_rest = l;
+    return 1;
+}
+
 int swiftly_hip_debug_row_band_occupancy(void) { return swf::row_pass_band_occupancy(); }
 
 int swiftly_hip_debug_occupancy(int lds_bytes) { return swf::row_pass_half_occupancy(lds_bytes); }

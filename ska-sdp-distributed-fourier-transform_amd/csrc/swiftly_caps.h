@@ -1,0 +1,200 @@
+// Capability table of libswiftly_hip.so: which kernels and pipelines exist for a configuration, as pure host functions
+// of the sizes (no handle, no HIP call).  The entry points refuse through these functions and swiftly_hip_supports /
+// swiftly_hip_limit / swiftly_hip_mixed_factor (include/swiftly_hip.h) answer from them, so every rule lives here once;
+// the Python layer holds none.
+#pragma once
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+
+#include "../../include/swiftly_hip.h"
+
+namespace swf {
+
+static inline int ilog2_exact(int64_t n) {
+    if (n <= 0 || (n & (n - 1))) return -1;
+    int l = 0;
+    while ((int64_t(1) << l) < n) l++;
+    return l;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// lengths and instance tables of the kernels
+constexpr int kMinLogN = 3;        // power-of-two lengths of the row kernels (swiftly_rows.h): 8 points ...
+constexpr int kMaxLogNFloat = 15;  // ... to 32768 in one complex64 launch
+
+constexpr int kSumFinishMaxFacets = 64;  // facets summed by one sum_finish_facets call (table sizes of swiftly_sumfinish.h)
+constexpr int kWholeMaxWindows = 256;    // window table of the whole-row K1 (LDS, swiftly_rowwhole.h)
+
+bool col_pass_f64_supported(int logn);  // float64-arithmetic instances (ColPassArgs::f64; also the complex128 ones): col_pass.hip
+int row_pass_whole_stage_columns();     // physical band columns (both parities) the window-rows epilogue can stage: row_whole.hip
+
+// (m, xM) instances of the fused sum + finish row kernels (sum_finish.hip), as log2
+#define SF_PAIRS(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10) X(9, 11) X(10, 11) X(10, 12)
+// complex128 sum_finish_facets (register form, m-point transform of K3 in one column pass: m <= 512; (9, 11) would keep 32
+// complex128 accumulator values per lane and spills even at 256 VGPRs)
+#define SF_PAIRS_C128(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10)
+
+#define SF_HAS(M, XX) \
+    if (logm == M && logx == XX) return true;
+inline bool sum_finish_supported(int logm, int logx) {
+    SF_PAIRS(SF_HAS)
+    return false;
+}
+inline bool sum_finish_c128_supported(int logm, int logx) {  // complex128 sum_finish_facets_kernel instances
+    SF_PAIRS_C128(SF_HAS)
+    return false;
+}
+#undef SF_HAS
+// "(128, 256), (128, 1024), ...": the sizes of SF_PAIRS_C128 for refusal texts
+inline std::string sum_finish_c128_sizes() {
+    std::string s;
+#define SF_NAME(M, XX) s += (s.empty() ? "(" : ", (") + std::to_string(1 << M) + ", " + std::to_string(1 << XX) + ")";
+    SF_PAIRS_C128(SF_NAME)
+#undef SF_NAME
+    return s;
+}
+
+// n = Q * 2^k with Q in {3, 5, 7, 9} and 2^k a length the power-of-two kernels take (one radix-Q pass in front of them,
+// swiftly_mixed.h): Q and k, else false (powers of two included: they need no pass)
+inline bool mixed_factor(int64_t n, int* Q, int* logM) {
+    if (n <= 0) return false;
+    for (int q : {3, 5, 7, 9}) {
+        if (n % q) continue;
+        const int l = ilog2_exact(n / q);
+        if (l >= kMinLogN) {
+            *Q = q;
+            *logM = l;
+            return true;
+        }
+    }
+    return false;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// a configuration: the sizes and their exact log2 (-1 when not a power of two); base of the handle
+struct Sizes {
+    int64_t N = 0, yN = 0, xM = 0, m = 0;
+    int log_yN = -1, log_xM = -1, log_m = -1;
+};
+
+inline std::string reason(const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return buf;
+}
+// parameter checks of core.py:55-74: empty when (N, yN, xM) is a configuration, else what is wrong
+inline std::string check_sizes(int64_t N, int64_t yN, int64_t xM) {
+    if (N <= 0 || yN <= 0 || xM <= 0) return "sizes must be positive";
+    if (N % yN != 0) return reason("Image size %lld not divisible by facet size %lld!", (long long)N, (long long)yN);
+    if (N % xM != 0) return reason("Image size %lld not divisible by subgrid size %lld!", (long long)N, (long long)xM);
+    if ((xM * yN) % N != 0)
+        return reason("Contribution size not integer with image size %lld, subgrid size %lld and facet size %lld!", (long long)N,
+                      (long long)xM, (long long)yN);
+    return {};
+}
+inline Sizes make_sizes(int64_t N, int64_t yN, int64_t xM) {
+    Sizes s;
+    s.N = N; s.yN = yN; s.xM = xM; s.m = xM * yN / N;
+    s.log_yN = ilog2_exact(yN); s.log_xM = ilog2_exact(xM); s.log_m = ilog2_exact(s.m);
+    return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// limits of the band pipelines that no single kernel table states
+constexpr int kBandMinLog = 6;  // K2 (prepare_facet_columns) takes m >= 64: the facet kernels behind it run 64 lanes per transform;
+                                // the same floor for yN (and 2^k of Q * 2^k) is a policy of the streaming layer
+constexpr int kBandMaxLogYN = kMaxLogNFloat + 1;  // forward K1 in complex64 (prepare_facet_band): the band row kernel, 65536 points
+constexpr int kBandMaxLogYNC128 = 15;  // forward K1 in complex128: the two-kernel long-row form (swiftly_rowslong.h), 32768 points
+constexpr int kBandMixedMaxLog = kMaxLogNFloat;  // yN = Q * 2^k: sub-transforms of the radix-Q tables (make_mixed)
+constexpr int kFusedMaxLogM = 10;  // K3 (transform_contributions): m-point transform in ONE column pass (kColPassMaxLog)
+constexpr int kBackwardBandMinLogYN = 2;   // backward band: shortest column-tile pass (kColPassMinLog) ...
+constexpr int kBackwardBandMaxLogYN = 18;  // ... to the longest four-step of accumulate_facet_columns
+constexpr int kSplitBandMinLogYN = 14;  // yN the two-workgroup long-row K1 produces a band for (row_pass.hip)
+constexpr int kSplitBandMaxLogYN = 16;
+constexpr int kPlacedMaxLogXM = 11;  // sum_finish_facets, placed mode (axis-1-first pipeline): not in the wave-parallel form (xM >= 4096)
+// window rows (whole-row K1 that finishes the contiguous axis, row_whole.hip): instances for 32768-point rows with the
+// 512-point epilogue, in front of the placed sum_finish_facets
+constexpr int kWindowRowsLogYN = 15, kWindowRowsLogM = 9;
+
+// Band layout: parity-split where the two-workgroup long-row kernel produces the band (yN >= 16384), else PLAIN (logical
+// column d of the band at physical column d; K1 is the generic contiguous-axis transform and keeps the whole padded axis).
+inline bool band_is_split(const Sizes* s) { return s->log_yN >= kSplitBandMinLogYN && s->log_yN <= kSplitBandMaxLogYN; }
+// complex128 band pipeline (K2, K3, sum_finish_facets): power-of-two padded facets up to 32768 points in the plain band
+// layout, m-point transforms in one column pass (m <= 512) and a complex128 sum_finish_facets instance for (m, xM)
+inline bool band_pipeline_c128_supported(const Sizes* s) {
+    return s->log_yN >= kBandMinLog && s->log_yN <= kBandMaxLogYNC128 && col_pass_f64_supported(s->log_m) &&
+           sum_finish_c128_supported(s->log_m, s->log_xM);
+}
+
+// yN of a band pipeline: a power of two 2^lo .. 2^hi, or Q * 2^k within the range of the radix-Q pass
+inline bool band_yN_supported(const Sizes& s, int lo, int hi) {
+    int Q = 0, k = 0;
+    if (s.log_yN >= 0) return s.log_yN >= lo && s.log_yN <= hi;
+    return mixed_factor(s.yN, &Q, &k) && k >= kBandMinLog && k <= kBandMixedMaxLog;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// pipeline-level features (swiftly_hip_supports): empty = supported, else the reason why not.  n_facets <= 0: not given.
+inline std::string too_many_facets(int64_t n_facets) {
+    if (n_facets <= kSumFinishMaxFacets) return {};
+    return reason("the fused subgrid side sums at most %d facets in one kernel, got %lld", kSumFinishMaxFacets, (long long)n_facets);
+}
+// transform_contributions + sum_finish_facets
+inline std::string why_not_fused_subgrid(const Sizes& s, int dtype, int64_t n_facets) {
+    if (s.log_m < 0 || s.log_xM < 0)
+        return reason("fused subgrid side: m %lld and xM %lld must be powers of two", (long long)s.m, (long long)s.xM);
+    if (dtype != SWIFTLY_C64) return "fused subgrid side: complex64 only (complex128: the band pipeline, when asked for explicitly)";
+    if (std::string why = too_many_facets(n_facets); !why.empty()) return why;
+    if (s.log_m > kFusedMaxLogM || !sum_finish_supported(s.log_m, s.log_xM))
+        return reason("fused subgrid side: no sum_finish instance for m %lld, xM %lld", (long long)s.m, (long long)s.xM);
+    return {};
+}
+// contiguous-axis-first forward kernels; `explicit_`: the caller asked for this pipeline (complex128 runs only then)
+inline std::string why_not_band_pipeline(const Sizes& s, int dtype, int64_t n_facets, bool explicit_) {
+    if (dtype == SWIFTLY_C128) {
+        if (!explicit_) return "complex128 band pipeline: runs only when asked for explicitly";
+        if (s.log_yN < 0 || s.log_xM < 0 || s.log_m < 0)
+            return reason("complex128 band pipeline: yN %lld, xM %lld and m %lld must be powers of two", (long long)s.yN,
+                          (long long)s.xM, (long long)s.m);
+        if (std::string why = too_many_facets(n_facets); !why.empty()) return why;
+        if (!band_pipeline_c128_supported(&s) || s.log_m < kBandMinLog)
+            return reason("complex128 band pipeline: needs yN %d .. %d and an instance for (m, xM) = %s; got yN %lld, m %lld, xM %lld",
+                          1 << kBandMinLog, 1 << kBandMaxLogYNC128, sum_finish_c128_sizes().c_str(), (long long)s.yN,
+                          (long long)s.m, (long long)s.xM);
+        return {};
+    }
+    if (std::string why = why_not_fused_subgrid(s, dtype, n_facets); !why.empty()) return why;
+    if (s.log_m < kBandMinLog || !band_yN_supported(s, kBandMinLog, kBandMaxLogYN))
+        return reason("band pipeline: needs m >= %d and yN a power of two %d .. %d or Q * 2^k (Q = 3, 5, 7, 9; 2^k %d .. %d); "
+                      "got m %lld, yN %lld", 1 << kBandMinLog, 1 << kBandMinLog, 1 << kBandMaxLogYN, 1 << kBandMinLog,
+                      1 << kBandMixedMaxLog, (long long)s.m, (long long)s.yN);
+    return {};
+}
+// accumulate_facet_columns / finish_facet_band
+inline std::string why_not_backward_band(const Sizes& s, int dtype) {
+    if (dtype != SWIFTLY_C64) return "backward band: complex64 only";
+    if (s.log_xM < 0 || s.log_m < 0 || !band_yN_supported(s, kBackwardBandMinLogYN, kBackwardBandMaxLogYN))
+        return reason("backward band: needs xM and m powers of two and yN a power of two %d .. %d or Q * 2^k (Q = 3, 5, 7, 9; "
+                      "2^k %d .. %d); got xM %lld, m %lld, yN %lld", 1 << kBackwardBandMinLogYN, 1 << kBackwardBandMaxLogYN,
+                      1 << kBandMinLog, 1 << kBandMixedMaxLog, (long long)s.xM, (long long)s.m, (long long)s.yN);
+    return {};
+}
+inline std::string why_not_split_band(const Sizes& s) {
+    if (band_is_split(&s)) return {};
+    return reason("yN %lld keeps the whole padded axis in the plain band layout (split: %d .. %d)", (long long)s.yN,
+                  1 << kSplitBandMinLogYN, 1 << kSplitBandMaxLogYN);
+}
+// size part of prepare_facet_window_rows (the band, the facets and the windows are per call)
+inline std::string why_not_window_rows(const Sizes& s) {
+    if (s.log_yN == kWindowRowsLogYN && s.log_m == kWindowRowsLogM && s.xM <= (int64_t(1) << kPlacedMaxLogXM)) return {};
+    return reason("window rows: needs yN %d, m %d and xM <= %d; got yN %lld, m %lld, xM %lld", 1 << kWindowRowsLogYN,
+                  1 << kWindowRowsLogM, 1 << kPlacedMaxLogXM, (long long)s.yN, (long long)s.m, (long long)s.xM);
+}
+
+}  // namespace swf

@@ -11,6 +11,7 @@
 // scalar unit with scalar loads; the vector unit only sees the butterflies,
 // one 8-byte global access per point and the LDS exchange.
 #pragma once
+#include "swiftly_caps.h"  // col_pass_f64_supported
 #include "swiftly_fft.h"
 
 namespace swf {
@@ -480,6 +481,5 @@ constexpr int kColPassMaxLog = 10;  // 1024 points: 32-column tiles
 
 int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s);
 int init_col_pass();
-bool col_pass_f64_supported(int logn);  // float64-arithmetic instances (ColPassArgs::f64; also the complex128 ones)
 
 }  // namespace swf

@@ -12,6 +12,7 @@
 #include <mutex>
 #include <vector>
 
+#include "swiftly_caps.h"  // row_pass_whole_stage_columns
 #include "swiftly_fft.h"
 
 // groups of three loads the W4 instances of the band row kernel request before the first one is consumed (0: the
@@ -813,6 +814,5 @@ int row_pass_band_occupancy();
 int launch_row_pass_whole(const RowPassArgs& a, int nseg, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s);
 int init_row_pass_whole();
 int row_pass_whole_grid();  // workgroups of a whole-row launch (one per CU)
-int row_pass_whole_stage_columns();  // physical band columns (both parities) the window-rows epilogue can stage
 
 }  // namespace swf

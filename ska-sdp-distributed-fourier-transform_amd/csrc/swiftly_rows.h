@@ -8,6 +8,7 @@
 // with different AxisMaps (see swiftly_abi.hip for the table that maps the
 // reference's core.py:189-484 onto it).
 #pragma once
+#include "swiftly_caps.h"  // kMinLogN, kMaxLogNFloat
 #include "swiftly_fft.h"
 
 namespace swf {
@@ -264,8 +265,6 @@ struct GeoFor {
     using type = Geo<R, LOGN, LOGP, NT, SPLIT>;
 };
 
-constexpr int kMinLogN = 3;
-constexpr int kMaxLogNFloat = 15;
 constexpr int kMaxLogNDouble = 13;  // single-workgroup double kernels, Bluestein and radix-Q double tables
 // power-of-two complex128 transforms of the primitives (run_rows): 2^14 / 2^15 as four-steps -- along a strided axis
 // through two fft_rows_kernel passes, along the contiguous axis through swiftly_rowslong.h

@@ -109,8 +109,7 @@ __device__ __forceinline__ void opaque_values(cx<float> (&v)[K]) {
 
 // WIN (RowPassArgs::win_full): the band of a row is staged in the exchange buffer (free once the last gather is done) and the
 // epilogue finishes the contiguous axis for every planned window (see RowPassArgs) -- the K1 of the axis-1-first pipeline.
-constexpr int kWholeMaxWindows = 256;
-// exchange buffer | Fn | window table of the window epilogue
+// exchange buffer | Fn | window table of the window epilogue (kWholeMaxWindows entries, swiftly_caps.h)
 constexpr size_t kWholeWinLds = RGeoWhole::LDS_BYTES + 512 * sizeof(float) + kWholeMaxWindows * sizeof(int);
 template <int NSEG, bool WIN = false>
 __global__ __launch_bounds__(512, 2) void row_pass_whole_kernel(const RowPassArgs A, const cx<float>* __restrict__ gin,

@@ -10,6 +10,7 @@
 // column buffers, one write of the half-finished subgrid (vs. zero-fill +
 // read-modify-write per group + read/write of the finish in the unfused form).
 #pragma once
+#include "swiftly_caps.h"  // kSumFinishMaxFacets, the (m, xM) instance tables
 #include "swiftly_fft.h"
 
 namespace swf {
@@ -182,8 +183,7 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT)) void sum_finish_rows_kerne
 // facet's off1 (core.py:274-285), then finishes axis 1 (inverse transform, crop, mask; core.py:316-323).  Each input
 // row is read exactly once; there is no zero-fill and no read-modify-write (r1: colacc zero-filled, re-written by one
 // launch per facet off0, re-read here).
-constexpr int kSumFinishMaxFacets = 64;
-
+// (at most kSumFinishMaxFacets facets, swiftly_caps.h)
 struct SumFinishFacetArgs {
     const cx<float>* in;   // G[f][b][k][m]
     cx<float>* out;        // tmp[b][r][xA]
@@ -722,8 +722,6 @@ int launch_sum_finish_facets(int logm, int logx, const SumFinishFacetArgs& a, in
 int launch_sum_finish_facets_c128(int logm, int logx, const SumFinishFacetArgs& a, int nbatch, hipStream_t s);
 int launch_sum_finish_rows(int logm, int logx, const SumFinishArgs& a, int nbatch, hipStream_t s);
 int init_sum_finish_rows();
-bool sum_finish_supported(int logm, int logx);
-bool sum_finish_c128_supported(int logm, int logx);  // complex128 sum_finish_facets_kernel instances
 int launch_axis1_rows(int logm, const Axis1RowsArgs& a, int nfacets, hipStream_t s);
 
 }  // namespace swf

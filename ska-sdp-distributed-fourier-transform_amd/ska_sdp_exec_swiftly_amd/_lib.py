@@ -15,6 +15,10 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("SWIFTLY_HIP_LIB", "libswiftly_hip
 
 C64, C128 = 0, 1
 ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
+# swiftly_hip_supports / swiftly_hip_limit (include/swiftly_hip.h)
+(FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
+ FEATURE_WINDOW_ROWS) = range(6)
+LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None
 
@@ -37,6 +41,12 @@ def _declare(lib):
     lib.swiftly_hip_contribution_size.argtypes = [vp]
     lib.swiftly_hip_supports_dtype.restype = c_int
     lib.swiftly_hip_supports_dtype.argtypes = [vp, c_int]
+    lib.swiftly_hip_supports.restype = c_int
+    lib.swiftly_hip_supports.argtypes = [c_int, c_int, i64, i64, i64, i64]
+    lib.swiftly_hip_limit.restype = i64
+    lib.swiftly_hip_limit.argtypes = [c_int]
+    lib.swiftly_hip_mixed_factor.restype = c_int
+    lib.swiftly_hip_mixed_factor.argtypes = [i64, POINTER(c_int), POINTER(c_int)]
     lib.swiftly_hip_build_id.restype = ctypes.c_char_p
     lib.swiftly_hip_build_id.argtypes = []
     lib.swiftly_hip_chain_chunk_streams.restype = None
@@ -187,12 +197,17 @@ def check(rc):
     backends raise for the same condition."""
     if rc == 0:
         return
-    msg = load().swiftly_hip_last_error().decode("utf-8", "replace")
+    msg = last_error()
     if rc == ERR_PARAM:
         raise ValueError(msg)
     if rc == ERR_UNSUPPORTED:
         raise NotImplementedError(msg)
     raise SwiftlyHipError(msg)
+
+
+def last_error():
+    """text of the calling thread's last refusal (``swiftly_hip_last_error``)"""
+    return load().swiftly_hip_last_error().decode("utf-8", "replace")
 
 
 def build_info():

@@ -202,7 +202,7 @@ class SwiftlyBackward:
                 raise ValueError(f"subgrid has shape {tuple(ten.shape)}, expected {(xA, xA)}")
             subs.append(ten)
         dev, dt = core.device, self.dtype
-        if core.supports_fused_subgrid(dt) and F <= 64:
+        if core.supports_fused_subgrid(dt, n_facets=F):
             # prepare_subgrid along axis 0 on the xA columns, then ONE kernel per padded row for the contiguous-axis
             # half (prepare axis 1 + extract axis 1 for every facet, on chip) and one column pass for the rest
             step = xA * xA * subs[0].element_size()

@@ -85,14 +85,11 @@ def _band_range_cached(N, yN, m, subgrid_offs, align):
 
 def mixed_factor(n):
     """``(Q, k)`` when ``n = Q * 2^k`` with Q in {3, 5, 7, 9} and ``2^k >= 8`` -- the lengths that run through one
-    radix-Q pass in front of the power-of-two kernels (csrc/swiftly_mixed.h; the same rule as ``mixed_factor`` in
-    csrc/swiftly_abi.hip) -- else None (powers of two included: they need no pass)."""
-    n = int(n)
-    for q in (3, 5, 7, 9):
-        if n > 0 and n % q == 0:
-            r = n // q
-            if r >= 8 and r & (r - 1) == 0:
-                return q, r.bit_length() - 1
+    radix-Q pass in front of the power-of-two kernels (csrc/swiftly_mixed.h) -- else None (powers of two included: they
+    need no pass).  The native library's rule (``swiftly_hip_mixed_factor``)."""
+    q, k = ctypes.c_int(), ctypes.c_int()
+    if _lib.load().swiftly_hip_mixed_factor(int(n), ctypes.byref(q), ctypes.byref(k)):
+        return q.value, k.value
     return None
 
 
@@ -522,20 +519,14 @@ class SwiftlyCoreHip:
         return out
 
     # ------------------------------------------------------------------ contiguous-axis-first pipeline
-    def _logs(self, need=("yN", "xM", "m")):
-        """log2 of the transform lengths named in ``need``; None unless all of THOSE are powers of two"""
-        logs = {}
-        for name, n in (("yN", self.yN_size), ("xM", self.xM_size), ("m", self.xM_yN_size)):
-            if name not in need:
-                continue
-            if n <= 0 or n & (n - 1):
-                return None
-            logs[name] = n.bit_length() - 1
-        return logs
-
-    def _mixed_yN(self):
-        """``(Q, k)`` when ``yN_size = Q * 2^k`` with Q in {3, 5, 7, 9} (:py:func:`mixed_factor`), else None"""
-        return mixed_factor(self.yN_size)
+    def _supports(self, feature, dtype=None, n_facets=None):
+        """Ask the native capability table (``swiftly_hip_supports``, csrc/swiftly_caps.h) about these sizes; on False,
+        ``swiftly_hip_last_error`` holds the reason.  ``dtype=None`` means complex64; anything but the two complex torch
+        dtypes has no kernels."""
+        torch = _torch()
+        code = {None: _lib.C64, torch.complex64: _lib.C64, torch.complex128: _lib.C128}.get(dtype, -1)
+        sizes = (int(self.N), int(self.yN_size), int(self.xM_size))
+        return bool(_lib.load().swiftly_hip_supports(feature, code, *sizes, int(n_facets or 0)))
 
     def supports_dtype(self, dtype):
         """True when every transform length of this configuration (``yN_size``, ``xM_size``, ``xM_yN_size``) has a
@@ -553,64 +544,33 @@ class SwiftlyCoreHip:
             raise ValueError(f"dtype must be complex64 or complex128, not {dtype}")
         return bool(self._lib.swiftly_hip_supports_dtype(self._handle, code))
 
-    MAX_FUSED_FACETS = 64  # kSumFinishMaxFacets (csrc/swiftly_sumfinish.h): facets summed by one sum_finish_facets call
+    @property
+    def MAX_FUSED_FACETS(self):  # pylint: disable=invalid-name
+        """facets summed by one sum_finish_facets call (``swiftly_hip_limit``)"""
+        return int(_lib.load().swiftly_hip_limit(_lib.LIMIT_FUSED_FACETS))
 
     def supports_fused_subgrid(self, dtype=None, n_facets=None):
         """True when transform_contributions + sum_finish_facets (include/swiftly_hip.h) exist for these sizes
         (and, when given, for ``n_facets`` facets: the facet sum runs inside one kernel)."""
-        torch = _torch()
-        logs = self._logs(("xM", "m"))
-        if logs is None or (dtype is not None and dtype != torch.complex64):
-            return False
-        if n_facets is not None and n_facets > self.MAX_FUSED_FACETS:
-            return False
-        pairs = {(7, 8), (7, 10), (8, 9), (8, 10), (9, 10), (9, 11), (10, 11), (10, 12)}  # sum_finish instances
-        return logs["m"] <= 10 and (logs["m"], logs["xM"]) in pairs  # m: single-pass column transform
-
-    #: (m, xM) pairs of the complex128 sum_finish_facets instances (csrc/sum_finish.hip, SF_PAIRS_C128)
-    C128_FUSED_PAIRS = frozenset({(7, 8), (7, 10), (8, 9), (8, 10), (9, 10)})
+        return self._supports(_lib.FEATURE_FUSED_SUBGRID, dtype, n_facets)
 
     def supports_band_pipeline(self, dtype=None, n_facets=None, explicit=False):
         """True when the contiguous-axis-first forward kernels (include/swiftly_hip.h) exist for these sizes.
 
         ``explicit=True`` also answers for complex128, whose pipeline runs only when asked for (``SwiftlyForward(...,
-        wave_axis=1)``): power-of-two ``yN_size`` of 64 .. 32768 in the plain band layout (whole padded axis kept),
-        ``m`` of 64 .. 512 and an (m, xM) pair with a complex128 ``sum_finish_facets`` instance.  With the default the
-        answer for complex128 is False: nothing picks that pipeline on its own."""
-        torch = _torch()
-        if explicit and dtype == torch.complex128:
-            logs = self._logs()
-            if logs is None or (n_facets is not None and n_facets > self.MAX_FUSED_FACETS):
-                return False
-            return 6 <= logs["yN"] <= 15 and 6 <= logs["m"] <= 9 and (logs["m"], logs["xM"]) in self.C128_FUSED_PAIRS
-        # K1: the two-workgroup band kernel for yN = 16384 .. 65536 (band-pruned output), the generic contiguous-axis
-        # transform below that (whole padded axis kept)
-        # yN = Q * 2^k (r3): the radix-Q pass in front of the same kernels, whole padded axis kept, forward only
-        if not self.supports_fused_subgrid(dtype, n_facets) or self._logs(("m",))["m"] < 6:
-            return False
-        logs = self._logs(("yN",))
-        if logs is not None:
-            return 6 <= logs["yN"] <= 16
-        mixed = self._mixed_yN()
-        return mixed is not None and 6 <= mixed[1] <= 15
+        wave_axis=1)``; the sizes it takes: csrc/swiftly_caps.h, or ``_lib.last_error()`` after a False).  With the
+        default the answer for complex128 is False: nothing picks that pipeline on its own."""
+        feature = _lib.FEATURE_BAND_PIPELINE_EXPLICIT if explicit else _lib.FEATURE_BAND_PIPELINE
+        return self._supports(feature, dtype, n_facets)
 
     def supports_backward_band(self, dtype=None):
         """True when accumulate_facet_columns / finish_facet_band (include/swiftly_hip.h) exist for these sizes."""
-        torch = _torch()
-        if dtype is not None and dtype != torch.complex64:
-            return False
-        logs = self._logs()
-        if logs is not None:
-            return 2 <= logs["yN"] <= 18
-        # yN = Q * 2^k (r3): radix-Q pass with the gather-sum load + column-tile sub-transforms, plain band layout
-        mixed = self._mixed_yN()
-        return self._logs(("xM", "m")) is not None and mixed is not None and 6 <= mixed[1] <= 15
+        return self._supports(_lib.FEATURE_BACKWARD_BAND, dtype)
 
     def band_for_offsets(self, subgrid_offs):
         """Smallest cyclic range ``(start, length)`` of centred indices of the padded facet axis that contains
         the ``xM_yN_size`` window of every given subgrid offset (core.py:243-253); ``(0, yN_size)`` = all."""
-        logs = self._logs(("yN",))
-        if logs is None or not 14 <= logs["yN"] <= 16:
+        if not self._supports(_lib.FEATURE_SPLIT_BAND):
             return 0, self.yN_size  # short / non-power-of-two padded facets keep the whole axis (plain band layout)
         return band_range(self.N, self.yN_size, self.xM_yN_size, subgrid_offs)
 
@@ -651,8 +611,10 @@ class SwiftlyCoreHip:
         )
         return out
 
-    #: physical band columns the window-rows epilogue of the whole-row K1 can stage (row_whole.hip, row_pass_whole_stage_columns)
-    WINDOW_ROWS_STAGE_COLUMNS = 12800
+    @property
+    def WINDOW_ROWS_STAGE_COLUMNS(self):  # pylint: disable=invalid-name
+        """physical band columns the window-rows epilogue of the whole-row K1 can stage (``swiftly_hip_limit``)"""
+        return int(_lib.load().swiftly_hip_limit(_lib.LIMIT_WINDOW_ROWS_STAGE_COLUMNS))
 
     def window_starts(self, band, wave_off1s):
         """``(first logical column of the contribution window of wave off1 - band start) mod yN`` for every wave: the
@@ -662,10 +624,11 @@ class SwiftlyCoreHip:
 
     def supports_window_rows(self, band, facet_size, facet_off1s, n_windows=1):
         """can K1 finish the contiguous axis for every planned window in its epilogue (``prepare_facet_window_rows``)?
-        (yN = 32768, m = 512, xM <= 2048 for the placed subgrid side, the band fits the LDS stage, at most 256 windows,
-        16-byte loads possible)"""
+        (sizes with a whole-row kernel and a placed subgrid side, the band fits the LDS stage, no more windows than its
+        table holds -- all three from the native library -- and 16-byte loads possible)"""
         return (
-            0 < int(n_windows) <= 256 and self.yN_size == 32768 and self.xM_yN_size == 512 and self.xM_size <= 2048 and
+            0 < int(n_windows) <= int(_lib.load().swiftly_hip_limit(_lib.LIMIT_WINDOW_ROWS_WINDOWS)) and
+            self._supports(_lib.FEATURE_WINDOW_ROWS) and
             self.band_columns(band) <= self.WINDOW_ROWS_STAGE_COLUMNS and int(band[1]) < self.yN_size and
             int(facet_size) % 2 == 0 and all(int(o) % 2 == 0 for o in facet_off1s)
         )
@@ -773,7 +736,7 @@ class SwiftlyCoreHip:
         """four-step scratch of K2 for F facets (``element_size``: 8 = complex64, 16 = complex128); yN = Q * 2^k also holds
         the output of the radix-Q pass"""
         n = F * self.yN_size * self.xM_yN_size * int(element_size)
-        return n if self._mixed_yN() is None else 2 * n + 4096
+        return n if mixed_factor(self.yN_size) is None else 2 * n + 4096
 
     SCRATCH_TAIL_BYTES = 1 << 16
 

@@ -8,6 +8,7 @@ import os
 
 import numpy
 
+from . import _lib
 from .core_hip import band_range
 from .ingest import _FacetIngest, _mask_table
 from .prefetch import WavePrefetch, _knobs
@@ -396,11 +397,7 @@ class SwiftlyForward(WavePrefetch):
         torch = _torch()
         if not self.core.supports_band_pipeline(self.dtype, explicit=True):
             if self.dtype == torch.complex128:
-                raise ValueError(
-                    "wave_axis=1 is not available for complex128 facets of this configuration (power-of-two yN_size up to "
-                    "32768, contribution size 64 .. 512 and a complex128 sum_finish_facets instance for (m, xM): see "
-                    "core.supports_band_pipeline(torch.complex128, explicit=True))"
-                )
+                raise ValueError(f"wave_axis=1 is not available for complex128 facets of this configuration: {_lib.last_error()}")
             raise ValueError("wave_axis=1 is not available for this configuration / dtype (see preferred_wave_axis)")
         if len(self.facet_configs) > self.core.MAX_FUSED_FACETS:
             raise ValueError(

@@ -1,7 +1,7 @@
 """
 Every compiled instance of the fused subgrid-side kernels against the 1-D oracle.
 
-The fused pipelines pick their kernels from compile-time tables: ``SF_PAIRS`` / ``SF_PAIRS_C128`` in csrc/sum_finish.hip
+The fused pipelines pick their kernels from compile-time tables: ``SF_PAIRS`` / ``SF_PAIRS_C128`` in csrc/swiftly_caps.h
 ((log2 m, log2 xM) pairs of sum_finish_rows, sum_finish_facets and split_prepare_facets) and the column-pass dispatcher
 of csrc/col_pass.hip.  Each pair has its own threads per row, rows per workgroup, LDS layout and (from xM = 4096) the
 wave-parallel form with rounds of disjoint placement windows.  This module runs one small synthetic core per pair (table
@@ -71,7 +71,7 @@ from oracle import swiftly_oracle as orc
 pytestmark = pytest.mark.gpu
 
 W = 11.0
-#: one synthetic core per (log2 m, log2 xM) pair of SF_PAIRS (csrc/sum_finish.hip); all accepted by swiftly_hip_create
+#: one synthetic core per (log2 m, log2 xM) pair of SF_PAIRS (csrc/swiftly_caps.h); all accepted by swiftly_hip_create
 PAIRS = {
     (7, 8): dict(N=1024, yN=512, xM=256),
     (7, 10): dict(N=4096, yN=512, xM=1024),
@@ -672,14 +672,28 @@ def _cell_params(logm, logx):
     return dict(N=2 << logx, xM=1 << logx, yN=2 << logm)
 
 
+def library_pairs(feature, dtype):
+    """(log2 m, log2 xM) in 0..17 x 0..17 that the built library's capability table (``swiftly_hip_supports``) has
+    ``feature`` for, without a GPU; the padded facet of ``2^max(10, log2 m)`` points is in range for every pipeline"""
+    from ska_sdp_exec_swiftly_amd import _lib
+
+    lib, found = _lib.load(), set()
+    for logm in range(18):
+        for logx in range(18):
+            xM, yN = 1 << logx, 1 << max(10, logm)
+            if lib.swiftly_hip_supports(feature, dtype, (xM * yN) >> logm, yN, xM, 0):
+                found.add((logm, logx))
+    return found
+
+
 def test_python_and_native_tables_agree():
     """one core per cell of log2 m in 6..10 by log2 xM in 7..12: the Python-side gates, this module's tables and the
     entry point itself name the same instances"""
     import torch
 
-    from ska_sdp_exec_swiftly_amd import SwiftlyCoreHip
+    from ska_sdp_exec_swiftly_amd import SwiftlyCoreHip, _lib
 
-    assert set(PAIRS_C128) == set(SwiftlyCoreHip.C128_FUSED_PAIRS)
+    assert set(PAIRS_C128) == library_pairs(_lib.FEATURE_BAND_PIPELINE_EXPLICIT, _lib.C128)
     cells = 0
     for logm in range(6, 11):
         for logx in range(7, 13):
