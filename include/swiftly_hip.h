@@ -99,7 +99,8 @@ enum {
     SWIFTLY_FEATURE_FUSED_SUBGRID = 0,          /* transform_contributions + sum_finish_facets (dtype, n_facets) */
     SWIFTLY_FEATURE_BAND_PIPELINE = 1,          /* contiguous-axis-first forward kernels (dtype, n_facets) */
     SWIFTLY_FEATURE_BAND_PIPELINE_EXPLICIT = 2, /* ... when the caller asks for them: also answers for complex128 */
-    SWIFTLY_FEATURE_BACKWARD_BAND = 3,          /* accumulate_facet_columns + finish_facet_band (dtype) */
+    SWIFTLY_FEATURE_BACKWARD_BAND = 3,          /* accumulate_facet_columns + finish_facet_band (dtype): complex64, yN_size a
+                                                   power of two 64 .. 65536 or Q * 2^k; both entry points refuse other sizes through it */
     SWIFTLY_FEATURE_SPLIT_BAND = 4,             /* band buffers are parity-split and band-pruned (else whole axis, plain) */
     SWIFTLY_FEATURE_WINDOW_ROWS = 5             /* prepare_facet_window_rows, size part (band / facets / windows: per call) */
 };

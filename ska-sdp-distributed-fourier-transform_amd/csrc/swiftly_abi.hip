@@ -1696,6 +1696,9 @@ int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, i
     const int64_t in_cs = 1, out_cs = 1;
     CHECK_COMMON();
     CHECK_FACET_SIZE();
+    // (the size part of swiftly_hip_supports(BACKWARD_BAND); complex128 rows keep running here, they have no gather-sum pass)
+    if (const std::string why = why_not_backward_band(*h, SWIFTLY_C64); !why.empty())
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band: %s", why.c_str());
     if (band_len <= 0 || band_len > h->yN || band_start < 0 || band_start >= h->yN)
         return fail(SWIFTLY_ERR_PARAM, "band [%lld, +%lld) is not a cyclic range of [0, %lld)", (long long)band_start,
                     (long long)band_len, (long long)h->yN);

@@ -29,7 +29,9 @@
 
 using namespace swf;
 
-static_assert(kFusedMaxLogM == kColPassMaxLog && kBackwardBandMinLogYN == kColPassMinLog, "swiftly_caps.h names the column-pass limits");
+static_assert(kFusedMaxLogM == kColPassMaxLog && kBackwardBandMinLogYN >= kColPassMinLog && kBackwardBandMinLogYN >= kMinLogN &&
+                  kBackwardBandMaxLogYN <= kMaxLogNFloat + 1,
+              "swiftly_caps.h names the column-pass limits; the backward band stays inside the twiddle tables of make_twiddles");
 
 // ---------------------------------------------------------------------------
 // error state: integer status + thread-local message (swiftly_hip_last_error)

@@ -253,6 +253,10 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
                     (long long)h->yN, (long long)h->m, (long long)h->xM);
     const int yN = (int)h->yN, m = (int)h->m;
     if (h->log_m < kBandMinLog) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: sizes not supported");
+    // (the yN range of swiftly_hip_supports(BAND_PIPELINE): refuse here, not at a missing twiddle table further down)
+    if (!c128 && !band_yN_supported(*h, kBandMinLog, kBandMaxLogYN))
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: padded facet size %d not supported (power of two %d .. %d, or "
+                    "Q * 2^k with Q = 3, 5, 7, 9)", yN, 1 << kBandMinLog, 1 << kBandMaxLogYN);
     if (rows <= 0 || rows >= yN) return fail(SWIFTLY_ERR_PARAM, "facet size %lld must be in [1, yN_size - 1]", (long long)rows);
     if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN) return fail(SWIFTLY_ERR_PARAM, "bad band");
     if (nfacets <= 0 || nwaves <= 0) return 0;
@@ -773,8 +777,12 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
         auto it = h->mixed.find(h->yN);
         if (it != h->mixed.end() && it->second.tw_f && !band_is_split(h)) mx = &it->second;
     }
-    if ((h->log_yN < 0 && !mx) || h->log_m < 0 || h->log_yN > kBackwardBandMaxLogYN)
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: sizes not supported (yN a power of two or Q * 2^k, m a power of two)");
+    // (the gate of swiftly_hip_supports(BACKWARD_BAND): a caller that asked it is never refused here)
+    if (const std::string why = why_not_backward_band(*h, dtype); !why.empty())
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: %s", why.c_str());
+    if (h->log_yN < 0 && !mx)
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: yN %lld = Q * 2^k has no complex64 radix-Q table "
+                    "(2^k above %d), or would need the split band layout", (long long)h->yN, 1 << kBandMixedMaxLog);
     if (nchunks <= 0 || nchunks > kColZC) return fail(SWIFTLY_ERR_PARAM, "1..%d source chunks", kColZC);
     if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN) return fail(SWIFTLY_ERR_PARAM, "bad band");
     if (nfacets <= 0) return 0;

@@ -113,8 +113,12 @@ constexpr int kBandMaxLogYN = kMaxLogNFloat + 1;  // forward K1 in complex64 (pr
 constexpr int kBandMaxLogYNC128 = 15;  // forward K1 in complex128: the two-kernel long-row form (swiftly_rowslong.h), 32768 points
 constexpr int kBandMixedMaxLog = kMaxLogNFloat;  // yN = Q * 2^k: sub-transforms of the radix-Q tables (make_mixed)
 constexpr int kFusedMaxLogM = 10;  // K3 (transform_contributions): m-point transform in ONE column pass (kColPassMaxLog)
-constexpr int kBackwardBandMinLogYN = 2;   // backward band: shortest column-tile pass (kColPassMinLog) ...
-constexpr int kBackwardBandMaxLogYN = 18;  // ... to the longest four-step of accumulate_facet_columns
+// backward band (accumulate_facet_columns + finish_facet_band): the lengths both entry points run and the facet sweep
+// (tests/test_hip_facet_sweep_gpu.py) pins on the oracle.  The column-tile passes alone would reach from 2^2
+// (kColPassMinLog) to 2^20, but the handle holds no twiddle table below 2^3 (kMinLogN) and no float table above 2^16, and
+// finish_facet_band has no row kernel above 65536 points; no catalogue entry lies outside 256 .. 65536.
+constexpr int kBackwardBandMinLogYN = kBandMinLog;
+constexpr int kBackwardBandMaxLogYN = kMaxLogNFloat + 1;
 constexpr int kSplitBandMinLogYN = 14;  // yN the two-workgroup long-row K1 produces a band for (row_pass.hip)
 constexpr int kSplitBandMaxLogYN = 16;
 constexpr int kPlacedMaxLogXM = 11;  // sum_finish_facets, placed mode (axis-1-first pipeline): not in the wave-parallel form (xM >= 4096)

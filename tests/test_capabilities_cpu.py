@@ -77,7 +77,10 @@ def test_band_pipeline_complex128_only_when_explicit():
 
 
 def test_backward_band_boundaries():
-    for log_yN, want in ((1, False), (2, True), (18, True), (19, False)):
+    # 64 .. 65536: the lengths accumulate_facet_columns AND finish_facet_band run (twiddle tables exist for 2^3 .. 2^16, the
+    # finishing row kernels end at 65536) and tests/test_hip_facet_sweep_gpu.py sweeps; the gate used to answer yes for
+    # 4 .. 262144, where the entry points refused
+    for log_yN, want in ((5, False), (6, True), (16, True), (17, False)):
         assert supports("BACKWARD_BAND", C64, *sizes(0, 0, 1 << log_yN)) == want, log_yN
         assert not supports("BACKWARD_BAND", C128, *sizes(0, 0, 1 << log_yN))
     for k, want in ((5, False), (6, True), (15, True), (16, False)):
