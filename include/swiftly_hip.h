@@ -102,7 +102,14 @@ enum {
     SWIFTLY_FEATURE_BACKWARD_BAND = 3,          /* accumulate_facet_columns + finish_facet_band (dtype): complex64, yN_size a
                                                    power of two 64 .. 65536 or Q * 2^k; both entry points refuse other sizes through it */
     SWIFTLY_FEATURE_SPLIT_BAND = 4,             /* band buffers are parity-split and band-pruned (else whole axis, plain) */
-    SWIFTLY_FEATURE_WINDOW_ROWS = 5             /* prepare_facet_window_rows, size part (band / facets / windows: per call) */
+    SWIFTLY_FEATURE_WINDOW_ROWS = 5,            /* prepare_facet_window_rows, size part (band / facets / windows: per call) */
+    SWIFTLY_FEATURE_BACKWARD_BAND_EXPLICIT = 6, /* BACKWARD_BAND when the caller asks for the band schedule: complex64 as
+                                                   BACKWARD_BAND; also answers for complex128 (xM, m powers of two, yN_size a
+                                                   power of two 64 .. 32768, no Q * 2^k).  The gate accumulate_facet_columns
+                                                   and finish_facet_band refuse through */
+    SWIFTLY_FEATURE_SPLIT_PREPARE = 7           /* split_prepare_facets + wave_split_subgrids (dtype, n_facets): complex64 as
+                                                   FUSED_SUBGRID; complex128 for (m, xM) = (128, 256), (128, 1024), (256, 512),
+                                                   (256, 1024), (512, 1024), up to 64 facets */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -480,7 +487,8 @@ int swiftly_hip_prepare_facet_window_rows(swiftly_hip_t* h, int dtype, const voi
  * prepare_subgrid of subgrid b along axis 0 ONLY (core.py:328-368); out[f][b] = [m, m] contiguous = the contribution
  * of subgrid b to facet f, i.e. api_helper.prepare_and_split_subgrid (api_helper.py:115-139): prepare_subgrid along
  * axis 1 and both extract_from_subgrid (core.py:396-439).  The prepared [xM, xM] subgrid and the per-off0
- * intermediates never reach HBM.  (m, xM) pairs of sum_finish_facets; up to 64 facets. */
+ * intermediates never reach HBM.  (m, xM) pairs of sum_finish_facets; up to 64 facets.  SWIFTLY_C128: complex128 in / out
+ * for the pairs of SWIFTLY_FEATURE_SPLIT_PREPARE, the gate this entry point and wave_split_subgrids refuse through. */
 int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in, int64_t in_sub_stride,
                                      int64_t in_row_stride, int64_t subgrid_size, int64_t nsub,
                                      const int64_t* subgrid_off1s, int64_t nfacets, const int64_t* facet_off0s,
@@ -489,7 +497,7 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
 
 /* The subgrid side of one backward wave in ONE native call without stream-ordered allocations: prepare_subgrid along
  * axis 0 of subgrids[nsub][subgrid_size][subgrid_size] (contiguous) followed by split_prepare_facets.  work: device
- * scratch of work_elems >= 2 * nsub * xM * subgrid_size complex64 elements. */
+ * scratch of work_elems >= 2 * nsub * xM * subgrid_size complex elements of `dtype`. */
 int swiftly_hip_wave_split_subgrids(swiftly_hip_t* h, int dtype, const void* subgrids, int64_t subgrid_size, int64_t nsub,
                                     const int64_t* subgrid_off0s, const int64_t* subgrid_off1s, int64_t nfacets,
                                     const int64_t* facet_off0s, const int64_t* facet_off1s, void* work,
@@ -508,19 +516,21 @@ int swiftly_hip_wave_split_subgrids(swiftly_hip_t* h, int dtype, const void* sub
  *   encoded  chunk << 20 | row : read at parts + chunk_offsets[chunk] + f * chunk_facet_strides[chunk] + row *
  *   part_row_stride (elements; row = b*m + k for contiguous [m, m] blocks).  Chunks (<= 16) are the pieces of a
  *   multi-GPU receive buffer; a single-process caller passes one chunk.  masks: device float [nfacets][facet_size]
- *   or NULL.  bands[f] = [facet_size rows][band_len] plain column order, read-modify-written (zero it first).
+ *   (SWIFTLY_C128: double) or NULL.  bands[f] = [facet_size rows][band_len] plain column order, read-modify-written (zero it first).
  *   touched: optional device bytes [band_len], zero before the first call: band columns whose byte is 0 have not
  *   been written yet and are stored plainly (bands need no zero fill, no read of the old value); the call then marks
  *   its columns.  band_zero_untouched clears the columns no call has written (bands[rows][band_len], rows = all
  *   facets' rows when the facets are contiguous) -- call it before finish_facet_band.  NULL: always read-modify-write.
- *   workspace: optional device scratch (nfacets*yN*m*8 bytes used when large enough), else stream-ordered allocation.
+ *   workspace: optional device scratch (nfacets*yN*m*8 bytes used when large enough; SWIFTLY_C128: 16 bytes per
+ *   element), else stream-ordered allocation.  SWIFTLY_C128: parts, bands and the workspace hold complex128, the
+ *   arithmetic is float64 whatever swiftly_hip_set_column_precision says; sizes of SWIFTLY_FEATURE_BACKWARD_BAND_EXPLICIT.
  * finish_facet_band: finish_facet (core.py:481-510) along the contiguous axis of a band accumulator row:
  *     out[r, :] = mask * Fb * crop( FFT_yN( band row r placed at columns band_start + d, zero elsewhere ) ). */
 int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void* parts, int64_t part_row_stride,
                                          int64_t nchunks, const int64_t* chunk_offsets,
                                          const int64_t* chunk_facet_strides, const int32_t* row_sources,
                                          int64_t nfacets, const int64_t* facet_off0s, int64_t facet_size,
-                                         const float* masks, int64_t subgrid_off1, void* bands, int64_t band_row_stride,
+                                         const void* masks, int64_t subgrid_off1, void* bands, int64_t band_row_stride,
                                          int64_t band_facet_stride, int64_t band_start, int64_t band_len,
                                          unsigned char* touched, void* workspace, int64_t workspace_bytes,
                                          void* stream);

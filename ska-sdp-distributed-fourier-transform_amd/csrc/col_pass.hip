@@ -111,16 +111,30 @@ template <>
 struct CGeoC128<8> : CGeo<8, 4, true, 32, 8> {
     static constexpr int MINW = 2;
 };
+// Gather-sum load with complex128 storage (backward band schedule, accumulate_facet_columns): the same tiles.  Pass A of
+// the four-steps of 1024 .. 32768 points (32 / 64 / 128 points) and the single passes of 64 .. 512 points; the 32-column
+// tiles (128, 256 and 512 points) read their source rows per half-wave.
+template <int LOGN, int MODE>
+constexpr bool kColC128HasGs = (MODE == 0 && LOGN >= 5 && LOGN <= 7) || (MODE == 2 && LOGN >= 6 && LOGN <= kColPassMaxLogF64);
 template <int LOGN, int MODE>
 static int launch_mode_c128(const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
     if constexpr (LOGN < kColF64MinLog || LOGN > kColPassMaxLogF64) {
         return (int)hipErrorInvalidConfiguration;
     } else {
         using G = CGeoC128<LOGN>;
-        if (!a.twd || (MODE == 0 && !a.twd_full) || a.gs) return (int)hipErrorInvalidValue;
+        if (!a.twd || (MODE == 0 && !a.twd_full)) return (int)hipErrorInvalidValue;
         const cx<double>* in = reinterpret_cast<const cx<double>*>(a.in);
         cx<double>* out = reinterpret_cast<cx<double>*>(a.out);
         dim3 grid((unsigned)((a.ncols + G::COLS - 1) / G::COLS), (unsigned)outer, (unsigned)nbatch);
+        if (a.gs) {  // never fall through to the plain load, which would read the encoded table as a row map
+            if constexpr (kColC128HasGs<LOGN, MODE>) {
+                hipLaunchKernelGGL((col_pass_kernel<G, MODE, true, true, double, double>), grid, dim3(G::NT), G::LDS_BYTES, s,
+                                   a, in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
+                return (int)hipGetLastError();
+            } else {
+                return (int)hipErrorInvalidConfiguration;
+            }
+        }
         if (MODE == 2 || a.scratch_nt)
             hipLaunchKernelGGL((col_pass_kernel<G, MODE, true, false, double, double>), grid, dim3(G::NT), G::LDS_BYTES, s, a,
                                in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
@@ -143,6 +157,11 @@ static int init_mode_c128() {
             rc = (int)hipFuncSetAttribute(
                 reinterpret_cast<const void*>(&col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double, double>),
                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
+        if constexpr (kColC128HasGs<LOGN, MODE>) {
+            if (!rc)
+                rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<G, MODE, true, true, double, double>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
+        }
         return rc;
     }
 }

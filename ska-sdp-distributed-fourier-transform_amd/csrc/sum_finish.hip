@@ -30,18 +30,25 @@ static int init_one_f() {
     return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&sum_finish_facets_kernel<LOGM, LOGX, R>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sum_finish_facets_kernel_lds<LOGM, LOGX, R>()));
 }
-template <int LOGM, int LOGX>
+// (complex128: exchange buffer of the m-point transforms + the prepared row, in doubles; never the wave-parallel geometry)
+template <int LOGM, int LOGX, typename R>
+constexpr size_t split_prepare_lds() {
+    if constexpr (std::is_same_v<R, float>) return sum_finish_facets_lds<LOGM, LOGX>();  // (the same wave-parallel geometry)
+    else return SFGeo<LOGM, LOGX, R>::LDS_BYTES;
+}
+template <int LOGM, int LOGX, typename R = float>
 static int launch_one_s(const SplitFacetArgs& a, int nbatch, hipStream_t s) {
-    using S = SFGeo<LOGM, LOGX>;
+    using S = SFGeo<LOGM, LOGX, R>;
     dim3 grid((unsigned)((a.nrows + S::RB - 1) / S::RB), (unsigned)nbatch);
-    constexpr size_t lds = sum_finish_facets_lds<LOGM, LOGX>();  // (the same wave-parallel geometry)
-    hipLaunchKernelGGL((split_prepare_facets_kernel<LOGM, LOGX>), grid, dim3(S::NT), lds, s, a);
+    constexpr size_t lds = split_prepare_lds<LOGM, LOGX, R>();
+    static_assert(lds <= 160 * 1024, "LDS per workgroup");
+    hipLaunchKernelGGL((split_prepare_facets_kernel<LOGM, LOGX, R>), grid, dim3(S::NT), lds, s, a);
     return (int)hipGetLastError();
 }
-template <int LOGM, int LOGX>
+template <int LOGM, int LOGX, typename R = float>
 static int init_one_s() {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&split_prepare_facets_kernel<LOGM, LOGX>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sum_finish_facets_lds<LOGM, LOGX>()));
+    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&split_prepare_facets_kernel<LOGM, LOGX, R>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(split_prepare_lds<LOGM, LOGX, R>()));
 }
 
 template <int LOGM>
@@ -91,6 +98,13 @@ int launch_split_prepare_facets(int logm, int logx, const SplitFacetArgs& a, int
 #undef SF_CASE_S
     return -1;
 }
+int launch_split_prepare_facets_c128(int logm, int logx, const SplitFacetArgs& a, int nbatch, hipStream_t s) {
+#define SF_CASE_SD(M, XX) \
+    if (logm == M && logx == XX) return launch_one_s<M, XX, double>(a, nbatch, s);
+    SPLIT_PAIRS_C128(SF_CASE_SD)
+#undef SF_CASE_SD
+    return -1;
+}
 int init_sum_finish_rows() {
     int rc = 0;
 #define SF_INIT(M, XX)               \
@@ -103,6 +117,10 @@ int init_sum_finish_rows() {
     if (!rc) rc = init_one_f<M, XX, double>();
     SF_PAIRS_C128(SF_INIT_D)
 #undef SF_INIT_D
+#define SF_INIT_SD(M, XX) \
+    if (!rc) rc = init_one_s<M, XX, double>();
+    SPLIT_PAIRS_C128(SF_INIT_SD)
+#undef SF_INIT_SD
     return rc;
 }
 

@@ -427,13 +427,13 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
         ws = t_call_ws;
         ws_bytes = t_call_ws_bytes;
     }
-    // single pass up to 1024 points; the gather-sum load (c.gs, backward pass) exists for 64-column tiles only, i.e. up to
-    // 512 points: longer gather-sum transforms go through the four-step, whose pass A carries the load (r3 bug: a
-    // 1024-point gather-sum transform ran the plain 32-column kernel, which read the encoded table as a row map)
-    // complex128 storage (c.c128): float64 arithmetic in every pass, single pass up to 512 points
+    // single pass up to 1024 points; the gather-sum load (c.gs, backward pass) has complex64 instances for 64-column tiles
+    // only, i.e. up to 512 points: longer gather-sum transforms go through the four-step, whose pass A carries the load (r3
+    // bug: a 1024-point gather-sum transform ran the plain 32-column kernel, which read the encoded table as a row map)
+    // complex128 storage (c.c128): float64 arithmetic in every pass, single pass up to 512 points -- with the gather-sum
+    // load too (32-column tiles at 128, 256 and 512 points), and pass A of its four-steps at 32 .. 128 points
     const bool c128 = c.c128 != 0;
     const size_t esz = c128 ? sizeof(cx<double>) : sizeof(cx<float>);
-    if (c128 && c.gs) return -1;
     const bool two = logn > (c.gs ? 9 : c128 ? kColPassMaxLogF64 : kColPassMaxLog);
     const int l1 = two ? logn / 2 : logn, l2 = logn - l1;  // (32768 = 128 x 256; 256 x 128 and 64 x 512 measured slower, r4)
     if (l1 < kColPassMinLog || l1 > kColPassMaxLog || (two && (l2 < kColPassMinLog || l2 > kColPassMaxLog))) return -1;
@@ -441,7 +441,7 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
     // float64 arithmetic where the caller asks for it and the instances exist (else float32, silently: same results to
     // float32 rounding)
     const bool f64 = (c.f64 || c128) && (two ? (col_pass_f64_supported(l1) && col_pass_f64_supported(l2))
-                                             : (col_pass_f64_supported(logn) && !(c.gs && logn > 8)));
+                                             : (col_pass_f64_supported(logn) && !(c.gs && !c128 && logn > 8)));
     if (c128 && !f64) return -1;
     if (!two) {
         ColPassArgs one = c;
@@ -1696,8 +1696,9 @@ int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, i
     const int64_t in_cs = 1, out_cs = 1;
     CHECK_COMMON();
     CHECK_FACET_SIZE();
-    // (the size part of swiftly_hip_supports(BACKWARD_BAND); complex128 rows keep running here, they have no gather-sum pass)
-    if (const std::string why = why_not_backward_band(*h, SWIFTLY_C64); !why.empty())
+    // (the gate of swiftly_hip_supports(BACKWARD_BAND_EXPLICIT): identical to BACKWARD_BAND in complex64; complex128 rows run
+    // through do_finish_facet<double>, 64 .. 32768 points)
+    if (const std::string why = why_not_backward_band(*h, dtype, true); !why.empty())
         return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band: %s", why.c_str());
     if (band_len <= 0 || band_len > h->yN || band_start < 0 || band_start >= h->yN)
         return fail(SWIFTLY_ERR_PARAM, "band [%lld, +%lld) is not a cyclic range of [0, %lld)", (long long)band_start,

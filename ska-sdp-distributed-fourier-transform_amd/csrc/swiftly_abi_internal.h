@@ -32,6 +32,12 @@ using namespace swf;
 static_assert(kFusedMaxLogM == kColPassMaxLog && kBackwardBandMinLogYN >= kColPassMinLog && kBackwardBandMinLogYN >= kMinLogN &&
                   kBackwardBandMaxLogYN <= kMaxLogNFloat + 1,
               "swiftly_caps.h names the column-pass limits; the backward band stays inside the twiddle tables of make_twiddles");
+// complex128 backward band: four-step twiddles from the double tables of make_twiddles (up to 2^(kMaxLogNFloat + 1)), gather-sum
+// passes of at most 2^kColPassMaxLogF64 points (single pass, and both halves of the longest four-step), finish_facet_band
+// through the complex128 row kernels (run_rows_long up to 2^kMaxLogNDoubleRows)
+static_assert(kBandMaxLogYNC128 <= kMaxLogNFloat + 1 && kBandMaxLogYNC128 <= kMaxLogNDoubleRows &&
+                  (kBandMaxLogYNC128 + 1) / 2 <= kColPassMaxLogF64 && kBackwardBandMinLogYN >= 6,
+              "the complex128 backward band stays inside the double twiddle tables, the complex128 column passes and the long-row kernels");
 
 // ---------------------------------------------------------------------------
 // error state: integer status + thread-local message (swiftly_hip_last_error)

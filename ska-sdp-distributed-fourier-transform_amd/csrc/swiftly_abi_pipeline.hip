@@ -16,11 +16,12 @@ __global__ void mark_columns_kernel(unsigned char* __restrict__ touched, int m, 
     if (d < band_len) touched[d] = 1;
 }
 // zero the band columns no wave has written (rows x band_len, row stride `pitch`)
-__global__ void zero_untouched_kernel(cx<float>* __restrict__ band, const unsigned char* __restrict__ touched, long long rows,
+template <typename R>
+__global__ void zero_untouched_kernel(cx<R>* __restrict__ band, const unsigned char* __restrict__ touched, long long rows,
                                       long long pitch, int band_len) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= band_len || touched[d]) return;
-    for (long long r = blockIdx.y; r < rows; r += gridDim.y) band[r * pitch + d] = cx<float>{0.f, 0.f};
+    for (long long r = blockIdx.y; r < rows; r += gridDim.y) band[r * pitch + d] = cx<R>{(R)0, (R)0};
 }
 
 
@@ -577,12 +578,12 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
     if (!h || !in || !out || !facet_off0s || !facet_off1s || !subgrid_off1s) return fail(SWIFTLY_ERR_PARAM, "null argument");
     DeviceGuard device_guard_(h->device);
     CHECK_SUBGRID_SIZE();
-    if (dtype != SWIFTLY_C64) return fail(SWIFTLY_ERR_UNSUPPORTED, "split_prepare_facets: complex64 only");
-    if (nfacets <= 0 || nfacets > kSumFinishMaxFacets)
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "split_prepare_facets: 1..%d facets supported", kSumFinishMaxFacets);
-    if (!sum_finish_supported(h->log_m, h->log_xM) || h->log_m > kColPassMaxLog)
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "split_prepare_facets: (m, xM) = (%lld, %lld) not instantiated", (long long)h->m,
-                    (long long)h->xM);
+    const bool c128 = dtype == SWIFTLY_C128;
+    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    if (nfacets <= 0) return fail(SWIFTLY_ERR_UNSUPPORTED, "split_prepare_facets: 1..%d facets supported", kSumFinishMaxFacets);
+    // (the gate of swiftly_hip_supports(SPLIT_PREPARE): a caller that asked it is never refused here)
+    if (const std::string why = why_not_split_prepare(*h, dtype, nfacets); !why.empty())
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "split_prepare_facets: %s", why.c_str());
     if (nsub <= 0) return 0;
     const int xM = (int)h->xM, xA = (int)subgrid_size, m = (int)h->m;
     SplitFacetArgs a;
@@ -597,17 +598,25 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
     a.tw_m = twiddles<float>(h, h->log_m);
     a.tw_x = twiddles<float>(h, h->log_xM);
     if (!a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
-    // table values from the compact copies (m-point transforms: 64 lanes each; rows: 64 lanes, 256 from 4096 points on)
-    a.twc_m = compact_twiddles(h, h->log_m, h->log_m - 6);
-    a.twc_x = compact_twiddles(h, h->log_xM, h->log_xM - (h->log_xM >= 12 ? 8 : 6));
-    if (!a.twc_m || !a.twc_x) return fail(SWIFTLY_ERR_HIP, "internal: missing compact twiddle tables");
+    if (c128) {  // double Fn and plain double twiddle tables (the complex128 instances read no compact copies)
+        a.fn = (const float*)h->fn_d;
+        a.tw_m = (const cx<float>*)twiddles<double>(h, h->log_m);
+        a.tw_x = (const cx<float>*)twiddles<double>(h, h->log_xM);
+        if (!a.fn || !a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing double tables");
+    } else {
+        // table values from the compact copies (m-point transforms: 64 lanes each; rows: 64 lanes, 256 from 4096 points on)
+        a.twc_m = compact_twiddles(h, h->log_m, h->log_m - 6);
+        a.twc_x = compact_twiddles(h, h->log_xM, h->log_xM - (h->log_xM >= 12 ? 8 : 6));
+        if (!a.twc_m || !a.twc_x) return fail(SWIFTLY_ERR_HIP, "internal: missing compact twiddle tables");
+    }
     for (int64_t b0 = 0; b0 < nsub; b0 += kSumFinishMaxBatch) {
         const int nb = (int)std::min<int64_t>(kSumFinishMaxBatch, nsub - b0);
-        a.in = (const cx<float>*)in + b0 * in_sub_stride;
-        a.out = (cx<float>*)out + b0 * out_sub_stride;
+        a.in = cx_at(in, b0 * in_sub_stride, c128);
+        a.out = cx_at(out, b0 * out_sub_stride, c128);
         for (int b = 0; b < nb; b++) a.ld_a[b] = pmod(-(xM / 2 - xA / 2 + subgrid_off1s[b0 + b]), xM);
-        int e = launch_split_prepare_facets(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
-        if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        int e = c128 ? launch_split_prepare_facets_c128(h->log_m, h->log_xM, a, nb, (hipStream_t)stream)
+                     : launch_split_prepare_facets(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
+        if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", e > 0 ? hipGetErrorString((hipError_t)e) : "no instance");
     }
     // axis-0 remainder of extract_from_subgrid, in place: out[f][b][:, j] = cifft_m( Fn[k] * E[f][b][(k - s'0_f) ..., j] )
     ColPassArgs c;
@@ -617,11 +626,11 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
     c.in_pitch = c.out_pitch = (unsigned)m;
     c.ld_mul = c.st_mul = 1;
     c.ld_a = 0; c.ld_len = m; c.ld_c = 0; c.ld_mod = m;
-    c.ld_win = h->fn_f;
+    c.ld_win = c128 ? (const float*)h->fn_d : h->fn_f;  // (complex128: the double table)
     c.st_a = 0; c.st_len = m; c.st_c = 0; c.st_mod = m;
     c.conj_ld = c.conj_st = 1;
-    c.scale = 1.f / (float)m;
-    c.tw = a.tw_m;
+    c.scale = 1.f / (float)m;  // (a power of two: exact in either precision)
+    c.tw = twiddles<float>(h, h->log_m);
     for (int64_t f0 = 0; f0 < nfacets; f0 += kColZF) {
         const int nf = (int)std::min<int64_t>(kColZF, nfacets - f0);
         for (int64_t b0 = 0; b0 < nsub; b0 += kColZB) {
@@ -630,11 +639,18 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
             cz.nb = nb;
             cz.flags = kZLoadAF;
             for (int f = 0; f < nf; f++) cz.f_lda[f] = pmod(-floordiv(facet_off0s[f0 + f] * h->xM, h->N), m);
-            c.in = (const cx<float>*)out + f0 * out_facet_stride + b0 * out_sub_stride;
+            c.in = cx_at((const void*)out, f0 * out_facet_stride + b0 * out_sub_stride, c128);
             c.in_bdiv = nb; c.in_bs_hi = out_facet_stride; c.in_bs = out_sub_stride;
-            c.out = (cx<float>*)out + f0 * out_facet_stride + b0 * out_sub_stride;
+            c.out = cx_at(out, f0 * out_facet_stride + b0 * out_sub_stride, c128);
             c.out_bdiv = nb; c.out_bs_hi = out_facet_stride; c.out_bs = out_sub_stride;
-            set_col_precision(h, c, h->log_m);
+            if (c128) {  // complex128 storage: always the float64-arithmetic instance (m <= 512: one pass)
+                c.c128 = 1;
+                c.f64 = 1;
+                c.twd = twiddles<double>(h, h->log_m);
+                c.twd_full = c.twd;
+            } else {
+                set_col_precision(h, c, h->log_m);
+            }
             if (int rc = launch_col_checked(h->log_m, 2, c, cz, 1, nf * nb, (hipStream_t)stream)) return rc;
         }
     }
@@ -643,7 +659,7 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
 
 /* The whole subgrid side of one backward wave natively, without stream-ordered allocations: prepare_subgrid along
  * axis 0 (four-step through `work`) + split_prepare_facets.  work: device scratch of >= 2 * nsub * xM * subgrid_size
- * complex64 elements (first half: tmp[nsub][xM][subgrid_size], second half: four-step scratch). */
+ * complex elements of `dtype` (first half: tmp[nsub][xM][subgrid_size], second half: four-step scratch). */
 int swiftly_hip_wave_split_subgrids(swiftly_hip_t* h, int dtype, const void* subgrids, int64_t subgrid_size, int64_t nsub,
                                     const int64_t* subgrid_off0s, const int64_t* subgrid_off1s, int64_t nfacets,
                                     const int64_t* facet_off0s, const int64_t* facet_off1s, void* work,
@@ -652,14 +668,20 @@ int swiftly_hip_wave_split_subgrids(swiftly_hip_t* h, int dtype, const void* sub
     if (!h || !subgrids || !work || !out || !subgrid_off0s || !subgrid_off1s) return fail(SWIFTLY_ERR_PARAM, "null argument");
     DeviceGuard device_guard_(h->device);
     CHECK_SUBGRID_SIZE();
-    if (dtype != SWIFTLY_C64) return fail(SWIFTLY_ERR_UNSUPPORTED, "wave_split_subgrids: complex64 only");
+    const bool c128 = dtype == SWIFTLY_C128;
+    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    // (refused before the first launch: the gate of split_prepare_facets)
+    if (const std::string why = why_not_split_prepare(*h, dtype, nfacets); !why.empty())
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "wave_split_subgrids: %s", why.c_str());
     if (nsub <= 0 || nfacets <= 0) return 0;
     const int xM = (int)h->xM, xA = (int)subgrid_size;
     const int64_t half = nsub * (int64_t)xM * xA;
     if (work_elems < 2 * half) return fail(SWIFTLY_ERR_PARAM, "work holds %lld elements, %lld needed", (long long)work_elems, (long long)(2 * half));
-    cx<float>* tmp = (cx<float>*)work;
+    void* tmp = work;
+    const size_t esz = c128 ? sizeof(cx<double>) : sizeof(cx<float>);
     ColPassArgs c;
     std::memset(&c, 0, sizeof c);
+    c.c128 = c128 ? 1 : 0;
     c.ncols = xA;
     c.full_logn = h->log_xM;
     c.in_pitch = c.out_pitch = (unsigned)xA;
@@ -676,11 +698,11 @@ int swiftly_hip_wave_split_subgrids(swiftly_hip_t* h, int dtype, const void* sub
             cz.b_lda[b] = pmod(-(xM / 2 - xA / 2 + subgrid_off0s[b0 + b]), xM);
             cz.b_ldc[b] = 0;
         }
-        c.in = (const cx<float>*)subgrids + b0 * (int64_t)xA * xA;
+        c.in = cx_at(subgrids, b0 * (int64_t)xA * xA, c128);
         c.in_bs = (long long)xA * xA;
-        c.out = tmp + b0 * (int64_t)xM * xA;
+        c.out = cx_at(tmp, b0 * (int64_t)xM * xA, c128);
         c.out_bs = (long long)xM * xA;
-        const int rc = col_transform(h, h->log_xM, c, cz, xA, nb, (hipStream_t)stream, tmp + half, (size_t)half * sizeof(cx<float>));
+        const int rc = col_transform(h, h->log_xM, c, cz, xA, nb, (hipStream_t)stream, cx_at(tmp, half, c128), (size_t)half * esz);
         if (rc == -1) return fail(SWIFTLY_ERR_UNSUPPORTED, "wave_split_subgrids: padded subgrid size %d not supported", xM);
         if (rc) return rc;
     }
@@ -762,14 +784,15 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
                                          int64_t nchunks, const int64_t* chunk_offsets,
                                          const int64_t* chunk_facet_strides, const int32_t* row_sources,
                                          int64_t nfacets, const int64_t* facet_off0s, int64_t facet_size,
-                                         const float* masks, int64_t subgrid_off1, void* bands, int64_t band_row_stride,
+                                         const void* masks, int64_t subgrid_off1, void* bands, int64_t band_row_stride,
                                          int64_t band_facet_stride, int64_t band_start, int64_t band_len,
                                          unsigned char* touched, void* workspace, int64_t workspace_bytes,
                                          void* stream) {
     if (!h || !parts || !bands || !chunk_offsets || !chunk_facet_strides || !row_sources || !facet_off0s)
         return fail(SWIFTLY_ERR_PARAM, "null argument");
     DeviceGuard device_guard_(h->device);
-    if (dtype != SWIFTLY_C64) return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: complex64 only");
+    const bool c128 = dtype == SWIFTLY_C128;
+    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
     CHECK_FACET_SIZE();
     const int yN = (int)h->yN, m = (int)h->m;
     const swiftly_hip::Mixed* mx = nullptr;  // yN = Q * 2^k: radix-Q pass with the gather-sum load + sub-transforms
@@ -777,8 +800,9 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
         auto it = h->mixed.find(h->yN);
         if (it != h->mixed.end() && it->second.tw_f && !band_is_split(h)) mx = &it->second;
     }
-    // (the gate of swiftly_hip_supports(BACKWARD_BAND): a caller that asked it is never refused here)
-    if (const std::string why = why_not_backward_band(*h, dtype); !why.empty())
+    // (the gate of swiftly_hip_supports(BACKWARD_BAND_EXPLICIT), in complex64 identical to BACKWARD_BAND: a caller that asked
+    // it is never refused here)
+    if (const std::string why = why_not_backward_band(*h, dtype, true); !why.empty())
         return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: %s", why.c_str());
     if (h->log_yN < 0 && !mx)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: yN %lld = Q * 2^k has no complex64 radix-Q table "
@@ -788,7 +812,7 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
     if (nfacets <= 0) return 0;
     if ((uint64_t)facet_size * (uint64_t)band_row_stride >= (uint64_t(1) << 32) ||
         (uint64_t)part_row_stride << kGsRowBits >= (uint64_t(1) << 32))
-        return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");
+        return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");  // (ELEMENT offsets, of either storage type)
     const int lo = yN / 2 - (int)(facet_size / 2);
     ColPassArgs c;
     std::memset(&c, 0, sizeof c);
@@ -800,17 +824,20 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
     c.ld_mul = c.st_mul = 1;
     c.ld_a = 0; c.ld_len = yN; c.ld_c = 0; c.ld_mod = yN;
     c.ld_rowmap = row_sources; c.gs = 1;
-    c.f64 = h->col_f64;
+    c.f64 = h->col_f64;  // (complex128 storage: always float64 arithmetic, the column_precision setting does not matter)
+    c.c128 = c128 ? 1 : 0;
     c.st_a = 0; c.st_len = (int)facet_size; c.st_c = 0; c.st_mod = (int)facet_size;
-    c.st_win = masks; c.st_win_bs = masks ? facet_size : 0;
-    c.st_win2 = h->invp_f + lo;
+    // masks and 1/pswf: float tables, double ones with complex128 storage (the kernel reinterprets the pointers)
+    const size_t rsz = c128 ? sizeof(double) : sizeof(float);
+    c.st_win = (const float*)masks; c.st_win_bs = masks ? facet_size : 0;
+    c.st_win2 = c128 ? (const float*)(h->invp_d + lo) : h->invp_f + lo;
     c.scale = 1.f;
     c.accumulate = 1;
     c.touched = touched;
     c.cg_mod = m; c.cg_full = yN;
     c.cg_band_start = (int)band_start; c.cg_band_len = (int)band_len; c.cg_band_half = 0;
     const int64_t cap = workspace ? workspace_bytes : (int64_t(4) << 30);
-    const int64_t per_item = mx ? ((int64_t)yN + (int64_t(1) << mx->logM)) * m * 8 + 4096 : (int64_t)yN * m * 8;
+    const int64_t per_item = mx ? ((int64_t)yN + (int64_t(1) << mx->logM)) * m * 8 + 4096 : (int64_t)yN * m * (c128 ? 16 : 8);
     const int per_f = (int)std::max<int64_t>(1, std::min<int64_t>(kColZF, cap / per_item));
     const int64_t s1 = floordiv(subgrid_off1 * h->yN, h->N);
     for (int64_t f0 = 0; f0 < nfacets; f0 += per_f) {
@@ -825,9 +852,9 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
             cz.c_base[k] = chunk_offsets[k] + f0 * chunk_facet_strides[k];
             cz.c_fs[k] = chunk_facet_strides[k];
         }
-        c.out = (cx<float>*)bands + f0 * band_facet_stride;
+        c.out = cx_at(bands, f0 * band_facet_stride, c128);
         c.out_bs = band_facet_stride;
-        if (masks) c.st_win = masks + f0 * facet_size;
+        if (masks) c.st_win = (const float*)((const char*)masks + (size_t)(f0 * facet_size) * rsz);
         int rc = 0;
         if (!mx) {
             rc = col_transform(h, h->log_yN, c, cz, m, nf, (hipStream_t)stream, workspace,
@@ -895,11 +922,15 @@ int swiftly_hip_band_zero_untouched(swiftly_hip_t* h, int dtype, void* bands, in
                                     int64_t band_len, const unsigned char* touched, void* stream) {
     if (!h || !bands || !touched) return fail(SWIFTLY_ERR_PARAM, "null argument");
     DeviceGuard device_guard_(h->device);
-    if (dtype != SWIFTLY_C64) return fail(SWIFTLY_ERR_UNSUPPORTED, "band_zero_untouched: complex64 only");
+    if (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
     if (rows <= 0 || band_len <= 0) return 0;
     dim3 grid((unsigned)((band_len + 63) / 64), (unsigned)std::min<int64_t>(rows, 1024));
-    hipLaunchKernelGGL(zero_untouched_kernel, grid, dim3(64), 0, (hipStream_t)stream, (cx<float>*)bands, touched,
-                       (long long)rows, (long long)band_row_stride, (int)band_len);
+    if (dtype == SWIFTLY_C128)
+        hipLaunchKernelGGL(zero_untouched_kernel<double>, grid, dim3(64), 0, (hipStream_t)stream, (cx<double>*)bands, touched,
+                           (long long)rows, (long long)band_row_stride, (int)band_len);
+    else
+        hipLaunchKernelGGL(zero_untouched_kernel<float>, grid, dim3(64), 0, (hipStream_t)stream, (cx<float>*)bands, touched,
+                           (long long)rows, (long long)band_row_stride, (int)band_len);
     HIP_TRY(hipGetLastError());
     return 0;
 }

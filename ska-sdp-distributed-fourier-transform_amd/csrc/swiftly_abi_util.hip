@@ -44,6 +44,8 @@ int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int
             case SWIFTLY_FEATURE_BACKWARD_BAND: why = why_not_backward_band(s, dtype); break;
             case SWIFTLY_FEATURE_SPLIT_BAND: why = why_not_split_band(s); break;
             case SWIFTLY_FEATURE_WINDOW_ROWS: why = why_not_window_rows(s); break;
+            case SWIFTLY_FEATURE_BACKWARD_BAND_EXPLICIT: why = why_not_backward_band(s, dtype, true); break;
+            case SWIFTLY_FEATURE_SPLIT_PREPARE: why = why_not_split_prepare(s, dtype, n_facets); break;
             default: why = reason("unknown feature %d", feature);
         }
     }

@@ -36,6 +36,9 @@ int row_pass_whole_stage_columns();     // physical band columns (both parities)
 // complex128 sum_finish_facets (register form, m-point transform of K3 in one column pass: m <= 512; (9, 11) would keep 32
 // complex128 accumulator values per lane and spills even at 256 VGPRs)
 #define SF_PAIRS_C128(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10)
+// complex128 split_prepare_facets (backward mirror of the above; the prepared row stays in LDS, the axis-0 remainder is one
+// complex128 m-point column pass: m <= 512): the same five pairs, none spills
+#define SPLIT_PAIRS_C128(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10)
 
 #define SF_HAS(M, XX) \
     if (logm == M && logx == XX) return true;
@@ -47,15 +50,24 @@ inline bool sum_finish_c128_supported(int logm, int logx) {  // complex128 sum_f
     SF_PAIRS_C128(SF_HAS)
     return false;
 }
+inline bool split_prepare_c128_supported(int logm, int logx) {  // complex128 split_prepare_facets_kernel instances
+    SPLIT_PAIRS_C128(SF_HAS)
+    return false;
+}
 #undef SF_HAS
-// "(128, 256), (128, 1024), ...": the sizes of SF_PAIRS_C128 for refusal texts
+// "(128, 256), (128, 1024), ...": the sizes of SF_PAIRS_C128 / SPLIT_PAIRS_C128 for refusal texts
+#define SF_NAME(M, XX) s += (s.empty() ? "(" : ", (") + std::to_string(1 << M) + ", " + std::to_string(1 << XX) + ")";
 inline std::string sum_finish_c128_sizes() {
     std::string s;
-#define SF_NAME(M, XX) s += (s.empty() ? "(" : ", (") + std::to_string(1 << M) + ", " + std::to_string(1 << XX) + ")";
     SF_PAIRS_C128(SF_NAME)
-#undef SF_NAME
     return s;
 }
+inline std::string split_prepare_c128_sizes() {
+    std::string s;
+    SPLIT_PAIRS_C128(SF_NAME)
+    return s;
+}
+#undef SF_NAME
 
 // n = Q * 2^k with Q in {3, 5, 7, 9} and 2^k a length the power-of-two kernels take (one radix-Q pass in front of them,
 // swiftly_mixed.h): Q and k, else false (powers of two included: they need no pass)
@@ -159,6 +171,17 @@ inline std::string why_not_fused_subgrid(const Sizes& s, int dtype, int64_t n_fa
         return reason("fused subgrid side: no sum_finish instance for m %lld, xM %lld", (long long)s.m, (long long)s.xM);
     return {};
 }
+// split_prepare_facets + wave_split_subgrids
+inline std::string why_not_split_prepare(const Sizes& s, int dtype, int64_t n_facets) {
+    if (dtype != SWIFTLY_C128) return why_not_fused_subgrid(s, dtype, n_facets);  // complex64: the pairs of sum_finish_facets
+    if (s.log_m < 0 || s.log_xM < 0)
+        return reason("split_prepare_facets: m %lld and xM %lld must be powers of two", (long long)s.m, (long long)s.xM);
+    if (std::string why = too_many_facets(n_facets); !why.empty()) return why;
+    if (!split_prepare_c128_supported(s.log_m, s.log_xM) || !col_pass_f64_supported(s.log_m))
+        return reason("split_prepare_facets: complex128 instances exist for (m, xM) = %s; got (%lld, %lld)",
+                      split_prepare_c128_sizes().c_str(), (long long)s.m, (long long)s.xM);
+    return {};
+}
 // contiguous-axis-first forward kernels; `explicit_`: the caller asked for this pipeline (complex128 runs only then)
 inline std::string why_not_band_pipeline(const Sizes& s, int dtype, int64_t n_facets, bool explicit_) {
     if (dtype == SWIFTLY_C128) {
@@ -180,9 +203,19 @@ inline std::string why_not_band_pipeline(const Sizes& s, int dtype, int64_t n_fa
                       1 << kBandMixedMaxLog, (long long)s.m, (long long)s.yN);
     return {};
 }
-// accumulate_facet_columns / finish_facet_band
-inline std::string why_not_backward_band(const Sizes& s, int dtype) {
-    if (dtype != SWIFTLY_C64) return "backward band: complex64 only";
+// accumulate_facet_columns / finish_facet_band; `explicit_`: the caller asked for the band schedule (complex128 runs only
+// then: nothing picks it on its own)
+inline std::string why_not_backward_band(const Sizes& s, int dtype, bool explicit_ = false) {
+    if (dtype == SWIFTLY_C128 && explicit_) {
+        // the gather-sum column pass with 16-byte points: single passes of 64 .. 512 points, four-steps up to 32768; there
+        // is no double radix-Q gather-sum pass, so no Q * 2^k
+        if (s.log_xM < 0 || s.log_m < 0 || s.log_yN < kBackwardBandMinLogYN || s.log_yN > kBandMaxLogYNC128)
+            return reason("complex128 backward band: needs xM and m powers of two and yN a power of two %d .. %d (no Q * 2^k: "
+                          "there is no float64 radix-Q gather-sum pass); got xM %lld, m %lld, yN %lld",
+                          1 << kBackwardBandMinLogYN, 1 << kBandMaxLogYNC128, (long long)s.xM, (long long)s.m, (long long)s.yN);
+        return {};
+    }
+    if (dtype != SWIFTLY_C64) return "backward band: complex64 only (complex128: when asked for explicitly)";
     if (s.log_xM < 0 || s.log_m < 0 || !band_yN_supported(s, kBackwardBandMinLogYN, kBackwardBandMaxLogYN))
         return reason("backward band: needs xM and m powers of two and yN a power of two %d .. %d or Q * 2^k (Q = 3, 5, 7, 9; "
                       "2^k %d .. %d); got xM %lld, m %lld, yN %lld", 1 << kBackwardBandMinLogYN, 1 << kBackwardBandMaxLogYN,

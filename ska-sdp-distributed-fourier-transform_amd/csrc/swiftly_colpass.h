@@ -134,7 +134,8 @@ struct ColPassArgs {
     // callers for which it was measured -- K3 of the forward wave loop, which runs next to K2 of the following waves (r5)
     int tile32;
     // complex128 STORAGE (in, out and the four-step scratch hold cx<double>; the pointers above are then reinterpreted):
-    // the float64-arithmetic geometries with 16-byte loads and stores.  Lengths 32 .. 512 per pass, no gather-sum load.
+    // the float64-arithmetic geometries with 16-byte loads and stores.  Lengths 32 .. 512 per pass; with the gather-sum
+    // load (gs): pass A of a four-step at 32 .. 128 points and single passes of 64 .. 512 points (col_pass.hip).
     int c128;
 };
 
@@ -208,7 +209,8 @@ struct CGeoFor<LOGN, double> {
     // instead of two; measured r4 on the 64k pass: 757 -> 632 us per wave) and for 512 points (1024 threads); 256 points
     // stay at 64 columns (1024 threads, 128 KiB: 608 us against 632 us with 32 columns)
     using type = CGeo<LOGN, LOGP, true, ((LOGN == 7 || LOGN >= 9) ? 32 : 64), 8>;
-    // the gather-sum load (backward pass) exists for 64-column tiles only
+    // the gather-sum load (backward pass) of the complex64-storage instances runs on 64-column tiles only (the load itself
+    // also knows the half-wave rows of 32-column tiles: the complex128-storage instances of col_pass.hip use them)
     using type_gs = CGeo<LOGN, LOGP, true, (LOGN >= 9 ? 32 : 64), 8>;
 };
 
@@ -255,7 +257,6 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>
     constexpr int P = G::P, T = G::T;
     static_assert(P <= 64, "one lane per row slot");
     constexpr bool HALF = G::HALF;
-    static_assert(!(HALF && GS), "gather-sum load: 64-column tiles only");
     constexpr bool RAW_LD = MODE == 1, RAW_ST = MODE == 0;
     constexpr bool NT_LD = RAW_LD ? SNT : true, NT_ST = RAW_ST ? SNT : true;
     // last Stockham phase: radix 2^LR at stride 2^LNS  (phases are LOGP, LOGP, ..., remainder)
@@ -394,13 +395,14 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>
         const int row = slot_bcast<HALF>(in_row, v, hw);
         cx<ST> val = {(ST)0, (ST)0};
         if constexpr (GS) {
-            const int lo1 = __builtin_amdgcn_readlane((int)gs_off1, v), hi1 = __builtin_amdgcn_readlane((int)(gs_off1 >> 32), v);
-            if (hi1 >= 0) {  // uniform
+            // (32-column tiles: the two half-waves read the slots of their own rows, as the plain load does)
+            const int lo1 = slot_bcast<HALF>((int)gs_off1, v, hw), hi1 = slot_bcast<HALF>((int)(gs_off1 >> 32), v, hw);
+            if (hi1 >= 0) {  // uniform (per half-wave with 32-column tiles)
                 const long long o1 = ((long long)hi1 << 32) | (unsigned)lo1;
                 if (live) val = cp_load<NT_LD>(in + o1);
             }
-            const int lo2 = __builtin_amdgcn_readlane((int)gs_off2, v), hi2 = __builtin_amdgcn_readlane((int)(gs_off2 >> 32), v);
-            if (hi2 >= 0) {  // uniform
+            const int lo2 = slot_bcast<HALF>((int)gs_off2, v, hw), hi2 = slot_bcast<HALF>((int)(gs_off2 >> 32), v, hw);
+            if (hi2 >= 0) {  // uniform (per half-wave)
                 const long long o2 = ((long long)hi2 << 32) | (unsigned)lo2;
                 if (live) {
                     const cx<ST> w2 = cp_load<NT_LD>(in + o2);

@@ -591,15 +591,29 @@ struct SplitFacetArgs {
     const cx<float>* twc_x;
 };
 
-template <int LOGM, int LOGX>
-__global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT)) void split_prepare_facets_kernel(const SplitFacetArgs A) {
-    using S = SFGeo<LOGM, LOGX>;
+// R = double: complex128 tmp / E, double Fn and plain (not compact) double twiddle tables (the pointers of SplitFacetArgs
+// reinterpreted), as sum_finish_facets_kernel; the form with one transform per row group only (!SFWide::ON), the prepared
+// row stays in LDS
+template <int LOGM, int LOGX, typename R = float>
+__global__ __launch_bounds__((SFGeo<LOGM, LOGX, R>::NT)) void split_prepare_facets_kernel(const SplitFacetArgs A) {
+    using S = SFGeo<LOGM, LOGX, R>;
     using GX = typename S::GX;
     using W = SFWide<LOGM, LOGX>;  // 4096-point rows: every wave extracts a different group (see SFWide)
     using GM = std::conditional_t<W::ON, typename W::GM, typename S::GM>;
+    constexpr bool F32 = std::is_same_v<R, float>;
+    static_assert(F32 || !W::ON, "complex128: one transform per row group only");
+    using GMC = std::conditional_t<F32, SFCompact<GM>, GM>;
+    using GXC = std::conditional_t<F32, SFCompact<GX>, GX>;
+    const cx<R>* g_in = reinterpret_cast<const cx<R>*>(A.in);
+    cx<R>* g_out = reinterpret_cast<cx<R>*>(A.out);
+    const R* g_fn = reinterpret_cast<const R*>(A.fn);
+    const cx<R>* tw_m = reinterpret_cast<const cx<R>*>(A.tw_m);
+    const cx<R>* tw_x = reinterpret_cast<const cx<R>*>(A.tw_x);
+    const cx<R>* twc_m = F32 ? reinterpret_cast<const cx<R>*>(A.twc_m) : nullptr;
+    const cx<R>* twc_x = F32 ? reinterpret_cast<const cx<R>*>(A.twc_x) : nullptr;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    cx<float>* ex_m = reinterpret_cast<cx<float>*>(smem);
-    cx<float>* acc = reinterpret_cast<cx<float>*>(smem + (W::ON ? W::LDS_M : S::LDS_M));
+    cx<R>* ex_m = reinterpret_cast<cx<R>*>(smem);
+    cx<R>* acc = reinterpret_cast<cx<R>*>(smem + (W::ON ? W::LDS_M : S::LDS_M));
     constexpr int M = GM::N, X = GX::N, PM = GM::P, PX = GX::P, TR = S::TR;
     const int t = threadIdx.x % TR, rb = threadIdx.x / TR;
     const int b = blockIdx.y;
@@ -608,22 +622,22 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT)) void split_prepare_facets_
     const bool live = row < A.nrows;
 
     {   // prepare_subgrid along the row: zero-pad + shift on load, forward transform, result kept in LDS (array order)
-        const cx<float>* __restrict__ in = A.in + (long long)b * A.in_bs + (long long)(live ? row : 0) * A.in_rs;
+        const cx<R>* __restrict__ in = g_in + (long long)b * A.in_bs + (long long)(live ? row : 0) * A.in_rs;
         const int lda = A.ld_a[b];
-        cx<float> y[PX];
+        cx<R> y[PX];
         static_for<0, PX>([&](auto vI) {
             constexpr int v = decltype(vI)::value;
             const int q = (((t + v * TR) ^ (X >> 1)) + lda) & (X - 1);
             const bool ok = live && q < A.xA;
-            const cx<float> val = in[ok ? q : 0];
-            y[v] = ok ? val : cx<float>{0.f, 0.f};
+            const cx<R> val = in[ok ? q : 0];
+            y[v] = ok ? val : cx<R>{(R)0, (R)0};
         });
-        fft_phases<SFCompact<GX>, float, 0>(y, t, rb, false, acc, A.tw_x, [&](int e, cx<float> v) {
+        fft_phases<GXC, R, 0>(y, t, rb, false, acc, tw_x, [&](int e, cx<R> v) {
             acc[lds_pos<GX>(rb, e ^ (X >> 1), false)] = v;
-        }, nullptr, A.twc_x);
+        }, nullptr, twc_x);
         row_sync<GX>(false);
     }
-    const float scale = 1.f / (float)M;
+    const R scale = (R)1 / (R)M;
     constexpr int NS = 4;  // facets of a group served by one transform (more: the transform is repeated)
     if constexpr (W::ON) {
         static_assert(S::RB == 1, "one row per workgroup");
@@ -637,7 +651,7 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT)) void split_prepare_facets_
             const int c1 = ((X >> 1) - (M >> 1) + sp) & (X - 1);
             while (n < ne) {
                 // (slots filled through compile-time indices: a runtime index would put the pointers into scratch memory)
-                cx<float>* outp[NS];
+                cx<R>* outp[NS];
                 int cnt = 0;
                 static_for<0, NS>([&](auto sI) {
                     constexpr int sl = decltype(sI)::value;
@@ -645,27 +659,27 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT)) void split_prepare_facets_
                     for (; n < ne && cnt == sl; n++) {  // the next covering facet of the group, if any
                         const int k = (row - A.base0[n]) & (X - 1);
                         if (live && k < M) {
-                            outp[sl] = A.out + (long long)A.fidx[n] * A.out_fs + (long long)b * A.out_bs + (long long)k * A.out_rs;
+                            outp[sl] = g_out + (long long)A.fidx[n] * A.out_fs + (long long)b * A.out_bs + (long long)k * A.out_rs;
                             cnt++;
                         }
                     }
                 });
                 if (cnt == 0) break;
-                cx<float> x[PM];
+                cx<R> x[PM];
                 static_for<0, PM>([&](auto vI) {
                     constexpr int v = decltype(vI)::value;
                     const int q = (((lane + v * 64) ^ (M >> 1)) - sp) & (M - 1);
-                    const cx<float> val = acc[lds_pos<GX>(0, (q + c1) & (X - 1), false)];
-                    const float w = A.fn[q];
-                    x[v] = cx<float>{val.x * w, -val.y * w};  // inverse transform = conj(FFT(conj(.)))
+                    const cx<R> val = acc[lds_pos<GX>(0, (q + c1) & (X - 1), false)];
+                    const R w = g_fn[q];
+                    x[v] = cx<R>{val.x * w, -val.y * w};  // inverse transform = conj(FFT(conj(.)))
                 });
-                fft_phases<SFCompact<GM>, float, 0>(x, lane, wv, false, ex_m, A.tw_m, [&](int e, cx<float> v) {
-                    const cx<float> o = cx<float>{v.x * scale, -v.y * scale};
+                fft_phases<GMC, R, 0>(x, lane, wv, false, ex_m, tw_m, [&](int e, cx<R> v) {
+                    const cx<R> o = cx<R>{v.x * scale, -v.y * scale};
                     static_for<0, NS>([&](auto sI) {
                         constexpr int sl = decltype(sI)::value;
                         if (outp[sl]) outp[sl][e ^ (M >> 1)] = o;
                     });
-                }, nullptr, A.twc_m);
+                }, nullptr, twc_m);
                 __builtin_amdgcn_wave_barrier();  // this wave's quarter of ex_m is reused by its next transform
             }
         }
@@ -686,7 +700,7 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT)) void split_prepare_facets_
                 if (any) fs[cnt++] = n;
             }
             if (cnt == 0) break;
-            cx<float>* outp[NS];
+            cx<R>* outp[NS];
             static_for<0, NS>([&](auto sI) {
                 constexpr int sl = decltype(sI)::value;
                 outp[sl] = nullptr;
@@ -694,30 +708,31 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX>::NT)) void split_prepare_facets_
                     const int nn = fs[sl];
                     const int k = (row - A.base0[nn]) & (X - 1);
                     if (live && k < M)
-                        outp[sl] = A.out + (long long)A.fidx[nn] * A.out_fs + (long long)b * A.out_bs + (long long)k * A.out_rs;
+                        outp[sl] = g_out + (long long)A.fidx[nn] * A.out_fs + (long long)b * A.out_bs + (long long)k * A.out_rs;
                 }
             });
-            cx<float> x[PM];
+            cx<R> x[PM];
             static_for<0, PM>([&](auto vI) {
                 constexpr int v = decltype(vI)::value;
                 const int q = (((t + v * TR) ^ (M >> 1)) - sp) & (M - 1);
-                const cx<float> val = acc[lds_pos<GX>(rb, (q + c1) & (X - 1), false)];
-                const float w = A.fn[q];
-                x[v] = cx<float>{val.x * w, -val.y * w};  // inverse transform = conj(FFT(conj(.)))
+                const cx<R> val = acc[lds_pos<GX>(rb, (q + c1) & (X - 1), false)];
+                const R w = g_fn[q];
+                x[v] = cx<R>{val.x * w, -val.y * w};  // inverse transform = conj(FFT(conj(.)))
             });
-            fft_phases<SFCompact<GM>, float, 0>(x, t, rb, false, ex_m, A.tw_m, [&](int e, cx<float> v) {
-                const cx<float> o = cx<float>{v.x * scale, -v.y * scale};
+            fft_phases<GMC, R, 0>(x, t, rb, false, ex_m, tw_m, [&](int e, cx<R> v) {
+                const cx<R> o = cx<R>{v.x * scale, -v.y * scale};
                 static_for<0, NS>([&](auto sI) {
                     constexpr int sl = decltype(sI)::value;
                     if (outp[sl]) outp[sl][e ^ (M >> 1)] = o;
                 });
-            }, nullptr, A.twc_m);
+            }, nullptr, twc_m);
             row_sync<GX>(false);  // ex_m is reused by the next transform
         }
     }
 }
 
 int launch_split_prepare_facets(int logm, int logx, const SplitFacetArgs& a, int nbatch, hipStream_t s);
+int launch_split_prepare_facets_c128(int logm, int logx, const SplitFacetArgs& a, int nbatch, hipStream_t s);
 int launch_sum_finish_facets(int logm, int logx, const SumFinishFacetArgs& a, int nbatch, hipStream_t s);
 int launch_sum_finish_facets_c128(int logm, int logx, const SumFinishFacetArgs& a, int nbatch, hipStream_t s);
 int launch_sum_finish_rows(int logm, int logx, const SumFinishArgs& a, int nbatch, hipStream_t s);

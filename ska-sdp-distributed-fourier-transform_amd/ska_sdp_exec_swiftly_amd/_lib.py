@@ -17,7 +17,7 @@ C64, C128 = 0, 1
 ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
 # swiftly_hip_supports / swiftly_hip_limit (include/swiftly_hip.h)
 (FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
- FEATURE_WINDOW_ROWS) = range(6)
+ FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE) = range(8)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None

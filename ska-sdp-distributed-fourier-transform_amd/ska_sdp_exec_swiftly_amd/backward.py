@@ -7,6 +7,7 @@ import logging
 
 import numpy
 
+from . import _lib
 from .core_hip import band_range
 from .ingest import _mask_table
 from .tasks import DeviceTask, LRUCache, TaskQueue, _torch, _unwrap
@@ -32,11 +33,16 @@ class SwiftlyBackward:
         transform at the end runs along the contiguous axis in one kernel.  Any request order is correct.
     :param subgrid_configs: (wave_axis=1) the subgrids that will be added: sizes the band accumulators to the
         columns they touch; without it the band is the whole padded axis
+    :param dtype: ``None`` (default): the dtype is the first data's, and the band schedule takes complex64 only.
+        A torch or numpy complex dtype fixes the accumulator and staging dtype at construction; data of another
+        dtype then raises ``ValueError`` on the band schedule.  ``wave_axis=1, dtype=torch.complex128`` is the
+        explicit request that runs the band schedule in complex128 (power-of-two ``yN_size`` 64 .. 32768); nothing
+        picks it on its own: with ``wave_axis=None`` complex128 stays on the reference's schedule.
     """
 
     # pylint: disable=too-many-arguments,too-many-instance-attributes
     def __init__(self, swiftly_config, facets_config_list, lru_backward=1, queue_size=20, client=None,
-                 subgrid_configs=None, wave_axis=None, delayed=False):
+                 subgrid_configs=None, wave_axis=None, delayed=False, dtype=None):
         self.delayed = bool(delayed)  # finish() hands out DeviceTask handles instead of bare device tensors
         # wave_axis=None: the reference's schedule, unless the caller hands over the plan of subgrids it will add and
         # the band kernels exist -- decided when the first subgrid shows the dtype (complex64 only)
@@ -62,6 +68,19 @@ class SwiftlyBackward:
         self.dtype = None
         self._off0s = sorted({cfg.off0 for cfg in facets_config_list})
         self._off0_of = [self._off0s.index(cfg.off0) for cfg in facets_config_list]
+        self._fixed_dtype = None
+        if dtype is not None:
+            torch = _torch()
+            if not isinstance(dtype, torch.dtype):
+                dtype = {numpy.dtype(numpy.complex64): torch.complex64, numpy.dtype(numpy.complex128): torch.complex128}.get(
+                    numpy.dtype(dtype)
+                )
+            if dtype not in (torch.complex64, torch.complex128):
+                raise ValueError("dtype must be complex64 or complex128")
+            self._fixed_dtype = self.dtype = dtype
+            # an explicit request for the band schedule is answered at once (complex128: the explicit gate)
+            if self.wave_axis == 1 and not self._auto_axis and not self.core.supports_backward_band(dtype, explicit=True):
+                raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={dtype}): {_lib.last_error()}")
 
     def add_new_subgrid_task(self, subgrid_config, new_subgrid_task):
         """Fold one subgrid into the facet sums (reference api.py:347-372)."""
@@ -80,6 +99,8 @@ class SwiftlyBackward:
         is_c64 = dt in (torch.complex64, torch.float32) if isinstance(first_subgrid, torch.Tensor) else (
             numpy.asarray(first_subgrid).dtype in (numpy.complex64, numpy.float32)
         )
+        if self._fixed_dtype is not None:  # the accumulators' dtype, not the data's, decides
+            is_c64 = self._fixed_dtype == torch.complex64
         sizes = {cfg.size for cfg in self.facets_config_list}
         if self._plan is not None and is_c64 and len(sizes) == 1 and self.core.supports_backward_band(torch.complex64):
             self.wave_axis = 1
@@ -138,19 +159,22 @@ class SwiftlyBackward:
         torch = _torch()
         core = self.core
         xA = sgs[0].size
+        sdt = self._fixed_dtype or torch.complex64  # staging dtype
         if staged is None:
             cap = planned if planned is not None else 8
-            staged = dict(cfgs=[], buf=torch.empty((max(cap, len(sgs)), xA, xA), dtype=torch.complex64, device=core.device))
+            staged = dict(cfgs=[], buf=torch.empty((max(cap, len(sgs)), xA, xA), dtype=sdt, device=core.device))
         need = len(staged["cfgs"]) + len(sgs)
         if need > staged["buf"].shape[0]:
-            grown = torch.empty((max(need, 2 * staged["buf"].shape[0]), xA, xA), dtype=torch.complex64, device=core.device)
+            grown = torch.empty((max(need, 2 * staged["buf"].shape[0]), xA, xA), dtype=sdt, device=core.device)
             grown[: len(staged["cfgs"])].copy_(staged["buf"][: len(staged["cfgs"])])
             staged["buf"] = grown
         for sg, data in zip(sgs, subgrids):
             ten, _ = core._as_device(data)  # pylint: disable=protected-access
             if tuple(ten.shape) != (xA, xA):
                 raise ValueError(f"subgrid has shape {tuple(ten.shape)}, expected {(xA, xA)}")
-            if ten.dtype != torch.complex64:
+            if ten.dtype != sdt:
+                if self._fixed_dtype is not None:
+                    raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={sdt}) got {ten.dtype} data")
                 raise ValueError("SwiftlyBackward(wave_axis=1) needs complex64 data and power-of-two yN_size / xM_yN_size")
             staged["buf"][len(staged["cfgs"])].copy_(ten)
             staged["cfgs"].append(sg)
@@ -197,12 +221,17 @@ class SwiftlyBackward:
             if self.dtype is None:
                 self.dtype = ten.dtype
             elif ten.dtype != self.dtype:
+                if self.wave_axis == 1 and self._fixed_dtype is not None:  # no silent conversion on the explicit band schedule
+                    raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={self.dtype}) got {ten.dtype} data")
                 ten = ten.to(self.dtype)
             if tuple(ten.shape) != (xA, xA):
                 raise ValueError(f"subgrid has shape {tuple(ten.shape)}, expected {(xA, xA)}")
             subs.append(ten)
         dev, dt = core.device, self.dtype
-        if core.supports_fused_subgrid(dt, n_facets=F):
+        # complex128 takes the split kernel only on the explicitly requested band schedule: every path that existed before
+        # keeps its launch sequence (and its rounding)
+        explicit128 = self.wave_axis == 1 and self._fixed_dtype is not None and dt == torch.complex128
+        if core.supports_fused_subgrid(dt, n_facets=F) or (explicit128 and core.supports_split_prepare(dt, n_facets=F)):
             # prepare_subgrid along axis 0 on the xA columns, then ONE kernel per padded row for the contiguous-axis
             # half (prepare axis 1 + extract axis 1 for every facet, on chip) and one column pass for the rest
             step = xA * xA * subs[0].element_size()
@@ -315,7 +344,13 @@ class SwiftlyBackward:
         torch = _torch()
         core = self.core
         if self._bands is None:
-            if dtype != torch.complex64 or not core.supports_backward_band(dtype):
+            if self._fixed_dtype is not None:
+                # explicit dtype: complex128 runs through the explicit gate (complex64: the same answer as without)
+                if dtype != self._fixed_dtype:
+                    raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={self._fixed_dtype}) got {dtype} contributions")
+                if not core.supports_backward_band(dtype, explicit=True):
+                    raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={dtype}): {_lib.last_error()}")
+            elif dtype != torch.complex64 or not core.supports_backward_band(dtype):
                 raise ValueError("SwiftlyBackward(wave_axis=1) needs complex64 data and power-of-two yN_size / xM_yN_size")
             sizes = {cfg.size for cfg in self.facets_config_list}
             if len(sizes) != 1:
@@ -334,7 +369,8 @@ class SwiftlyBackward:
             self._masks0 = _mask_table(core, self.facets_config_list, "mask0", yB, dtype)
             self._facet_off0s = [cfg.off0 for cfg in self.facets_config_list]
             # four-step scratch of accumulate_facet_columns (+ the radix-Q pass's output when yN = Q * 2^k)
-            self._work = torch.empty((core._k2_scratch_bytes(F) // 8,), dtype=dtype, device=core.device)
+            esz = 16 if dtype == torch.complex128 else 8
+            self._work = torch.empty((core._k2_scratch_bytes(F, element_size=esz) // esz,), dtype=dtype, device=core.device)
         return self._bands
 
     def _accumulate_band(self, off1, chunks):
@@ -358,6 +394,11 @@ class SwiftlyBackward:
         if self.dtype is None:
             self.dtype = chunks[0][1].dtype
         bands = self._band_state(chunks[0][1].dtype)
+        for _sgs, parts in chunks:
+            # on EVERY call, not only the one that creates the accumulators: the native side reads `parts` with the
+            # accumulators' element size
+            if parts.dtype != bands.dtype:
+                raise ValueError(f"band accumulators are {bands.dtype}, got {parts.dtype} contributions")
         if self._planned is not None and off1 not in self._planned:
             raise ValueError(f"subgrid off1={off1} is not in the subgrid_configs this SwiftlyBackward was planned for")
         F = len(self.facets_config_list)

@@ -563,9 +563,19 @@ class SwiftlyCoreHip:
         feature = _lib.FEATURE_BAND_PIPELINE_EXPLICIT if explicit else _lib.FEATURE_BAND_PIPELINE
         return self._supports(feature, dtype, n_facets)
 
-    def supports_backward_band(self, dtype=None):
-        """True when accumulate_facet_columns / finish_facet_band (include/swiftly_hip.h) exist for these sizes."""
-        return self._supports(_lib.FEATURE_BACKWARD_BAND, dtype)
+    def supports_backward_band(self, dtype=None, explicit=False):
+        """True when accumulate_facet_columns / finish_facet_band (include/swiftly_hip.h) exist for these sizes.
+
+        ``explicit=True`` also answers for complex128, whose band schedule runs only when asked for
+        (``SwiftlyBackward(..., wave_axis=1, dtype=torch.complex128)``); with the default the answer for complex128 is
+        False: nothing picks that schedule on its own."""
+        feature = _lib.FEATURE_BACKWARD_BAND_EXPLICIT if explicit else _lib.FEATURE_BACKWARD_BAND
+        return self._supports(feature, dtype)
+
+    def supports_split_prepare(self, dtype=None, n_facets=None):
+        """True when split_prepare_facets / wave_split_subgrids (include/swiftly_hip.h) exist for these sizes (and, when
+        given, for ``n_facets`` facets); complex64: the answer of :py:meth:`supports_fused_subgrid`."""
+        return self._supports(_lib.FEATURE_SPLIT_PREPARE, dtype, n_facets)
 
     def band_for_offsets(self, subgrid_offs):
         """Smallest cyclic range ``(start, length)`` of centred indices of the padded facet axis that contains
@@ -937,11 +947,16 @@ class SwiftlyCoreHip:
         """``bands[f] += mask0_f * finish_facet_axis0(sum_b add_to_facet_axis0(C[f][b]))`` placed at the band columns
         of ``subgrid_off1`` (``swiftly_hip_accumulate_facet_columns``, include/swiftly_hip.h).  ``parts``: device
         tensor holding the contribution blocks (chunk offsets / facet strides in elements relative to its start),
-        ``bands``: ``[F, facet_size, band length]``, ``masks``: float32 ``[F, facet_size]`` or None, ``touched``: uint8
+        ``bands``: ``[F, facet_size, band length]``, ``masks``: float32 (complex128: float64) ``[F, facet_size]`` or None, ``touched``: uint8
         ``[band length]`` first-write flags (then ``bands`` may start uninitialised; :py:meth:`band_zero_untouched`)."""
         F = bands.shape[0]
         nch = len(chunk_offsets)
         cvp = ctypes.c_void_p
+        # (the native side reads parts and masks with the element size of `bands`)
+        if parts.dtype != bands.dtype:
+            raise ValueError(f"parts are {parts.dtype}, bands {bands.dtype}")
+        if masks is not None and bands.dtype == _torch().complex128 and masks.dtype != _torch().float64:
+            raise ValueError(f"complex128 bands need float64 masks, got {masks.dtype}")
         _lib.check(
             self._lib.swiftly_hip_accumulate_facet_columns(
                 self._handle, self._code(bands), cvp(parts.data_ptr()), int(part_row_stride), nch,
