@@ -31,6 +31,18 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+int launch_status(int e, const char* what, const char* negative) {
+    if (!e) return 0;
+    const char* text = (e < 0 && negative) ? negative : hipGetErrorString((hipError_t)e);
+    if (what) return fail(SWIFTLY_ERR_HIP, "kernel launch failed (%s): %s", what, text);
+    return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", text);
+}
+int radix_launch_status(int e, int Q, const char* pass) {
+    if (!e) return 0;
+    char what[48]; snprintf(what, sizeof what, "radix-%d %s", Q, pass);
+    return launch_status(e, what);
+}
+
 template <typename T>
 static int upload(swiftly_hip* h, T** dst, const std::vector<T>& v) {
     void* p = nullptr;
@@ -385,289 +397,7 @@ static AxisMap<R> identity_map(int n) {
 
 template <typename R>
 static int launch_checked(int logn, const RowsArgs<R>& a, const OffTab& tab, hipStream_t st) {
-    int rc = launch_fft_rows(logn, a, tab, st);
-    if (rc) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return 0;
-}
-
-ColZ plain_colz() {
-    ColZ z;
-    std::memset(&z, 0, sizeof z);
-    z.nb = 1;
-    return z;
-}
-
-int launch_col_checked(int lg, int mode, const ColPassArgs& args, const ColZ& cz, int outer, int nb, hipStream_t st) {
-    int e = launch_col_pass(lg, mode, args, cz, outer, nb, st);
-    if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return 0;
-}
-
-// Strided-axis transform of length 2^logn over `W` adjacent columns and `nb` batch items with the column-tile
-// passes: one pass up to 512 points, otherwise four-step (N = n1*n2, input index y = y1*n2 + y2, output index
-// k = k1 + n1*k2) through a stream-ordered scratch [nb][N][W]:
-//   pass A (length n1 over y1, one per y2): scratch[k1*n2 + y2] = W_N^(y2 k1) * sum_y1 x[y1 n2 + y2] W_n1^(y1 k1)
-//   pass B (length n2 over y2, one per k1): X[k1 + n1 k2]       = sum_y2 scratch[k1*n2 + y2] W_n2^(y2 k2)
-// `c` carries the load / store maps, windows, conjugation flags, scale, batch strides, column gather and row
-// maps of the whole transform; in/out pitches and pointers are given separately.  Returns -1 when the length
-// is outside the column-pass range (caller falls back), else a status code.
-// Scratch handed down by an entry point for the duration of one ABI call on this host thread (the batch entry
-// points have no workspace parameter): col_transform prefers it to a stream-ordered allocation.  Measured on
-// MI355X: hipMallocAsync with a size that changes from call to call costs ~2 ms of HOST time per call (the pool
-// does not reuse a smaller free block), which made a 25-wave pass host-bound.
-thread_local void* t_call_ws = nullptr;
-thread_local size_t t_call_ws_bytes = 0;
-
-// Sub-transform form (qmul = Q > 0, swiftly_mixed.h): the input is the plain scratch of the radix-Q pass (element y of
-// the length-2^logn sub-transform j = qadd at row y of `c.in`), the store map of `c` refers to the full length full_n
-// with plain output index Q*k + j.
-int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz, int W, int nb, hipStream_t st, void* ws,
-                  size_t ws_bytes, int qmul, int qadd, int full_n) {
-    if (!ws && t_call_ws) {
-        ws = t_call_ws;
-        ws_bytes = t_call_ws_bytes;
-    }
-    // single pass up to 1024 points; the gather-sum load (c.gs, backward pass) has complex64 instances for 64-column tiles
-    // only, i.e. up to 512 points: longer gather-sum transforms go through the four-step, whose pass A carries the load (r3
-    // bug: a 1024-point gather-sum transform ran the plain 32-column kernel, which read the encoded table as a row map)
-    // complex128 storage (c.c128): float64 arithmetic in every pass, single pass up to 512 points -- with the gather-sum
-    // load too (32-column tiles at 128, 256 and 512 points), and pass A of its four-steps at 32 .. 128 points
-    const bool c128 = c.c128 != 0;
-    const size_t esz = c128 ? sizeof(cx<double>) : sizeof(cx<float>);
-    const bool two = logn > (c.gs ? 9 : c128 ? kColPassMaxLogF64 : kColPassMaxLog);
-    const int l1 = two ? logn / 2 : logn, l2 = logn - l1;  // (32768 = 128 x 256; 256 x 128 and 64 x 512 measured slower, r4)
-    if (l1 < kColPassMinLog || l1 > kColPassMaxLog || (two && (l2 < kColPassMinLog || l2 > kColPassMaxLog))) return -1;
-    const uint64_t n = uint64_t(1) << logn;
-    // float64 arithmetic where the caller asks for it and the instances exist (else float32, silently: same results to
-    // float32 rounding)
-    const bool f64 = (c.f64 || c128) && (two ? (col_pass_f64_supported(l1) && col_pass_f64_supported(l2))
-                                             : (col_pass_f64_supported(logn) && !(c.gs && !c128 && logn > 8)));
-    if (c128 && !f64) return -1;
-    if (!two) {
-        ColPassArgs one = c;
-        one.tw = twiddles<float>(h, logn);
-        if (!one.tw) return -1;
-        one.f64 = (f64 && (c128 || (h->col_f64_stages & 4))) ? 1 : 0;
-        one.twd = f64 ? twiddles<double>(h, logn) : nullptr;
-        one.twd_full = one.twd;
-        if (f64 && !one.twd) return -1;
-        if (qmul > 0) {
-            one.full_logn = logn; one.full_n = full_n; one.ld_plain = 1; one.st_qmul = qmul; one.st_qadd = qadd;
-            one.ld_mul = one.st_mul = 1;
-        }
-        return launch_col_checked(logn, 2, one, cz, 1, nb, st);
-    }
-    const int n1 = 1 << l1, n2 = 1 << l2;
-    const cx<float>* tw1 = twiddles<float>(h, l1);
-    const cx<float>* tw2 = twiddles<float>(h, l2);
-    const cx<float>* twf = twiddles<float>(h, logn);
-    if (!tw1 || !tw2 || !twf) return -1;
-    const cx<double>* twd1 = f64 ? twiddles<double>(h, l1) : nullptr;
-    const cx<double>* twd2 = f64 ? twiddles<double>(h, l2) : nullptr;
-    const cx<double>* twdf = f64 ? twiddles<double>(h, logn) : nullptr;
-    if (f64 && (!twd1 || !twd2 || !twdf)) return -1;
-    if (n * (uint64_t)W >= (uint64_t(1) << 32)) return -1;
-    const bool gathered = (cz.flags & kZColGather) != 0;
-    const long long Ws = (long long)W;  // scratch row width (column slabs that keep the intermediate cache-sized: no gain, r2-r4)
-    const size_t scratch_bytes = (size_t)nb * n * (size_t)Ws * esz;
-    auto elem = [esz](const cx<float>* p, long long k) { return (cx<float>*)((const char*)p + k * (long long)esz); };
-    void* scratch = nullptr;
-    hipError_t he = hipSuccess;
-    // caller-provided workspace (deterministic; the stream-ordered pool reuses memory across STREAMS only
-    // opportunistically, which made the two-stream schedule fall back to fresh multi-GB allocations on some runs)
-    const bool own = !(ws && ws_bytes >= scratch_bytes);
-    if (own) {
-        he = hipMallocAsync(&scratch, scratch_bytes, st);
-        if (he != hipSuccess) return fail(SWIFTLY_ERR_HIP, "hipMallocAsync(two-pass scratch): %s", hipGetErrorString(he));
-    } else {
-        scratch = ws;
-    }
-    int rc = 0;
-    // Layout of the intermediate (r4): row y2 * n1 + k1 -- a pass-A workgroup (one y2) WRITES n1 consecutive rows and a
-    // pass-B workgroup (one k1) reads a comb -- instead of row k1 * n2 + y2 (comb written, consecutive rows read).  HBM
-    // writes are the expensive direction on this chip (tools/mall_pipe.hip: a comb costs 7 % on the write side and nothing
-    // on the read side): pass A 425 -> 395 us per wave as a pure copy, 427 -> 386 us for the kernel.
-    constexpr bool y2_major = true;
-    // (r5: a TILE-major scratch -- [item][64-column tile][row][64], the n1 rows of a pass-A workgroup one contiguous run
-    // of n1 * 512 bytes -- measured the same within the run-to-run spread: 38.87 / 39.64 / 39.33 against 39.29 / 38.75 /
-    // 38.58 ms per pass, interleaved on one box; not kept)
-    const int a_i_rows = y2_major ? 1 : n2, a_o_rows = y2_major ? n1 : 1;  // pass A: row of (e = k1, o = y2)
-    const int b_i_rows = y2_major ? n1 : 1, b_o_rows = y2_major ? 1 : n2;  // pass B: row of (i = y2, o = k1)
-    // Chunked, two-stream form (r4; K2 = the gathered forward transform of several facets): the batch items are worked
-    // on in chunks of `zc` items x `Wc` columns whose two passes run back to back, chunks alternating between two
-    // internal streams, each stream re-using ONE chunk-sized slot of the scratch: pass A of one chunk (HBM reads, scratch
-    // writes) runs next to pass B of the other (scratch reads that can still hit the 256 MiB Infinity Cache).  Measured on
-    // the 64k workload (interleaved repeats on one box, gpurun_out/s3k, s3l): 40.7 -> 39.7 ms per pass with chunks of
-    // 2 facets x 256 columns (134 MB); 1 x 512: 40.0; 1 x 256, 4 x 128, 2 x 128, 3 x 256, 2 x 512: no gain or worse.  The
-    // gain is the overlap of the two kinds of pass, not cache residency: pure-copy stand-ins of the two passes bound it at
-    // 8 % of K2 (tools/mall_pipe.hip) -- the cache does not absorb the scratch WRITES.
-    // SWIFTLY_K2_CHUNK = "cols[,items]" | 0 (off) | unset: chunks of ~128 MB when the whole intermediate exceeds 256 MB.
-    static const char* chunk_env = getenv("SWIFTLY_K2_CHUNK");
-    int chunk_cols = chunk_env ? atoi(chunk_env) : -1;
-    int chunk_items = (chunk_env && strchr(chunk_env, ',')) ? std::max(1, atoi(strchr(chunk_env, ',') + 1)) : 1;
-    if (chunk_cols < 0) {  // automatic
-        chunk_cols = 0;
-        if (scratch_bytes > (size_t(256) << 20) && W >= 256) {
-            chunk_cols = 256;
-            chunk_items = (int)std::max<uint64_t>(1, (uint64_t(128) << 20) / (n * 256 * esz));
-        }
-    }
-    // (r5: three or four chunk streams instead of two -- 41.4-42.1 ms per pass against 38.9-39.8 with the default chunks,
-    // 39.5-39.7 against 39.1-39.3 with chunks of 1 facet x 256 columns; one stream: 41.7 -- two streams stay)
-    if (chunk_cols >= 64 && gathered && !(cz.flags & kZColScatter) && !c.gs && qmul == 0 &&
-        (nb > chunk_items || W > chunk_cols) && !own) {
-        const int Wc = std::min<int>((chunk_cols / 64) * 64, W), zc = std::min(chunk_items, nb);
-        const size_t slot_elems = (size_t)n * (size_t)Wc * (size_t)zc;
-        if (2 * slot_elems * esz <= ws_bytes) {
-            {
-                std::lock_guard<std::mutex> lock(h->chunk_mu);
-                for (hipStream_t& s2 : h->chunk_st)
-                    if (!s2) {
-                        he = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-                        if (he != hipSuccess) return fail(SWIFTLY_ERR_HIP, "hipStreamCreateWithFlags: %s", hipGetErrorString(he));
-                    }
-            }
-            // (events are per call: two host threads may drive the same handle on different streams)
-            hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-            auto drop_events = [&ev]() {
-                for (hipEvent_t& e : ev)
-                    if (e) {
-                        (void)hipEventDestroy(e);
-                        e = nullptr;
-                    }
-            };
-            for (hipEvent_t& e : ev) {
-                he = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-                if (he != hipSuccess) {
-                    e = nullptr;
-                    drop_events();
-                    return fail(SWIFTLY_ERR_HIP, "hipEventCreateWithFlags: %s", hipGetErrorString(he));
-                }
-            }
-            // fork: the chunk streams start behind everything queued on `st` (a failed record / wait would let them
-            // run ahead of the producer of the input: nothing has been launched yet, so just report it)
-            // (swiftly_hip_chain_chunk_streams: the caller vouches for the inputs; the chunk streams run on from the chunks
-            // of the previous call -- no pipeline drain and no idle event hops between consecutive waves, r5)
-            he = hipSuccess;
-            // (a chained call still forks when the un-chunked path has used THIS workspace since the last fork)
-            void* plain_ws = scratch;
-            const bool plain_pending = h->ws_plain_pending.compare_exchange_strong(plain_ws, nullptr);
-            if (!g_chain_chunk_streams || plain_pending) {
-                he = hipEventRecord(ev[0], st);
-                for (hipStream_t s2 : h->chunk_st)
-                    if (he == hipSuccess) he = hipStreamWaitEvent(s2, ev[0], 0);
-            }
-            if (he != hipSuccess) {
-                drop_events();
-                return fail(SWIFTLY_ERR_HIP, "chunked four-step, fork: %s", hipGetErrorString(he));
-            }
-            int i = 0;
-            for (int z0 = 0; z0 < nb && !rc; z0 += zc) {
-                const int nz = std::min(zc, nb - z0);
-                for (int c0 = 0; c0 < W && !rc; c0 += Wc, i++) {
-                    const int wc = std::min(Wc, W - c0);
-                    hipStream_t s2 = h->chunk_st[i & 1];
-                    // item z of the launch sits at slot + (z - z0) * n * Wc (raw_z0: the kernels address the scratch
-                    // with the item index relative to the launch's first item)
-                    cx<float>* slot = elem((const cx<float>*)scratch, (long long)((size_t)(i & 1) * slot_elems));
-                    ColPassArgs A = c;
-                    A.scratch_nt = 0;
-                    A.ncols = wc; A.col0 = c0; A.z0 = z0; A.raw_z0 = z0;
-                    A.out = slot; A.out_pitch = (unsigned)Wc; A.out_bs = (long long)(n * Wc);
-                    A.out_bdiv = 0; A.out_bs_hi = 0;
-                    A.ld_mul = n2;
-                    A.out_i_rows = a_i_rows; A.out_o_rows = a_o_rows;
-                    A.tw = tw1; A.tw_full = twf;
-                    A.f64 = (f64 && (c128 || (h->col_f64_stages & 1))) ? 1 : 0; A.twd = twd1; A.twd_full = twdf;
-                    A.conj_st = 0; A.accumulate = 0; A.scale = 1.f;
-                    A.col_win = nullptr; A.st_rowmap = nullptr; A.st_win = nullptr; A.st_win2 = nullptr;
-                    rc = launch_col_checked(l1, 0, A, cz, n2, nz, s2);
-                    if (rc) break;
-                    ColPassArgs B = c;
-                    B.scratch_nt = 0;
-                    ColZ zb = cz;
-                    zb.flags &= ~(kZColGather | kZLoadB | kZLoadAF);  // the scratch is read plainly
-                    B.ncols = wc; B.col0 = 0; B.z0 = z0; B.raw_z0 = z0;
-                    B.in = slot; B.in_pitch = (unsigned)Wc; B.in_bs = (long long)(n * Wc);
-                    B.in_bdiv = 0; B.in_bs_hi = 0;
-                    B.in_i_rows = b_i_rows; B.in_o_rows = b_o_rows;
-                    B.ld_rowmap = nullptr; B.ld_win = nullptr; B.ld_win2 = nullptr; B.gs = 0;
-                    B.out = elem(c.out, c0);
-                    B.st_mul = n1;
-                    B.tw = tw2; B.tw_full = twf;
-                    B.f64 = (f64 && (c128 || (h->col_f64_stages & 2))) ? 1 : 0; B.twd = twd2; B.twd_full = twdf;
-                    B.conj_ld = 0;
-                    if (B.col_win) B.col_win += c128 ? 2 * c0 : c0;  // (double table with complex128 storage)
-                    rc = launch_col_checked(l2, 1, B, zb, n1, nz, s2);
-                }
-            }
-            // join: `st` continues behind both chunk streams.  If the join cannot be queued, the consumer of the output
-            // on `st` must not start early: wait for the chunk streams on the host instead
-            for (int k = 0; k < 2; k++) {
-                he = hipEventRecord(ev[1 + k], h->chunk_st[k]);
-                if (he == hipSuccess) he = hipStreamWaitEvent(st, ev[1 + k], 0);
-                if (he != hipSuccess) {
-                    (void)hipStreamSynchronize(h->chunk_st[k]);
-                    if (!rc) rc = fail(SWIFTLY_ERR_HIP, "chunked four-step, join: %s", hipGetErrorString(he));
-                }
-            }
-            drop_events();
-            return rc;
-        }
-    }
-    // scratch accesses: a small intermediate is left cacheable so that pass B finds it in the 256 MiB Infinity
-    // Cache (measured: the 160 MB of a K5b wave, K3-5 12.5 -> 11.6 ms per pass); a large one is streamed
-    // non-temporally (measured: K2, 1.2 GB per wave, 18.5 ms vs 19.6 ms cacheable).
-    const int scratch_nt = scratch_bytes > (size_t(192) << 20) ? 1 : 0;
-    if (!own) h->ws_plain_pending.store(scratch);  // `ws` is written on `st` below: a later chained chunked call has to wait for it
-    for (long long c0 = 0; c0 < (long long)W && !rc; c0 += Ws) {
-        const int wc = (int)std::min<long long>(Ws, (long long)W - c0);
-        // pass A: length n1 over y1 (input index y1*n2 + y2), outer = y2; scratch row k1*n2 + y2
-        ColPassArgs A = c;
-        A.scratch_nt = scratch_nt;
-        A.ncols = wc;
-        A.in = elem(c.in, c0);
-        A.out = (cx<float>*)scratch; A.out_pitch = (unsigned)Ws; A.out_bs = (long long)(n * Ws);
-        A.out_bdiv = 0; A.out_bs_hi = 0;
-        A.ld_mul = n2;
-        A.out_i_rows = a_i_rows; A.out_o_rows = a_o_rows;
-        A.tw = tw1; A.tw_full = twf;
-        A.f64 = (f64 && (c128 || (h->col_f64_stages & 1))) ? 1 : 0; A.twd = twd1; A.twd_full = twdf;
-        if (qmul > 0) {
-            A.full_logn = logn; A.full_n = 0; A.ld_plain = 1; A.st_qmul = 0;
-        }
-        A.conj_st = 0; A.accumulate = 0; A.scale = 1.f;
-        A.col_win = nullptr; A.st_rowmap = nullptr; A.st_win = nullptr; A.st_win2 = nullptr;
-        ColZ za = cz;
-        za.flags &= ~kZColScatter;  // the scratch is written plainly
-        rc = launch_col_checked(l1, 0, A, za, n2, nb, st);
-        if (rc) break;
-        // pass B: length n2 over y2, outer = k1; output index k1 + n1*k2
-        ColPassArgs B = c;
-        B.scratch_nt = scratch_nt;
-        ColZ zb = cz;
-        zb.flags &= ~(kZColGather | kZLoadB | kZLoadAF);  // the scratch is read plainly
-        B.ncols = wc;
-        B.in = (const cx<float>*)scratch; B.in_pitch = (unsigned)Ws; B.in_bs = (long long)(n * Ws);
-        B.in_bdiv = 0; B.in_bs_hi = 0;
-        B.in_i_rows = b_i_rows; B.in_o_rows = b_o_rows;
-        B.ld_rowmap = nullptr; B.ld_win = nullptr; B.ld_win2 = nullptr; B.gs = 0;
-        B.out = elem(c.out, c0);
-        B.st_mul = n1;
-        B.tw = tw2; B.tw_full = twf;
-        B.f64 = (f64 && (c128 || (h->col_f64_stages & 2))) ? 1 : 0; B.twd = twd2; B.twd_full = twdf;
-        if (qmul > 0) {
-            B.full_logn = logn; B.full_n = full_n; B.st_qmul = qmul; B.st_qadd = qadd;
-        }
-        B.conj_ld = 0;
-        if (B.col_win) B.col_win += c128 ? 2 * c0 : c0;
-        rc = launch_col_checked(l2, 1, B, zb, n1, nb, st);
-    }
-    if (own) {
-        he = hipFreeAsync(scratch, st);
-        if (!rc && he != hipSuccess) rc = fail(SWIFTLY_ERR_HIP, "hipFreeAsync: %s", hipGetErrorString(he));
-    }
-    return rc;
+    return launch_status(launch_fft_rows(logn, a, tab, st));
 }
 
 // Lean path for complex64 transforms along the strided axis of row-major
@@ -778,13 +508,11 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
         const cx<float>* tw14 = twiddles<float>(h, 14);
         const cx<float>* tw13 = twiddles<float>(h, 13);
         if (tw14 && prep_ld) {
-            int e2 = launch_row_pass_band(r, tw14, r.tw, st);
-            *rc_out = e2 ? fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e2)) : 0;
+            *rc_out = launch_status(launch_row_pass_band(r, tw14, r.tw, st));
             return true;
         }
         if (tw14 && tw13) {
-            int e2 = launch_row_pass_split(r, tw14, tw13, r.tw, st);
-            *rc_out = e2 ? fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e2)) : 0;
+            *rc_out = launch_status(launch_row_pass_split(r, tw14, tw13, r.tw, st));
             return true;
         }
     }
@@ -799,7 +527,7 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
             }
             int e2 = launch_row_pass_band(r, tw14, r.tw, st, &h->win4);
             if (tmp) (void)hipFreeAsync(tmp, st);
-            *rc_out = e2 ? fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e2)) : 0;
+            *rc_out = launch_status(e2);
             return true;
         }
     }
@@ -817,11 +545,10 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
         }
         int e2 = launch_row_pass_band_n(16, r, tw15, r.tw, st);
         if (tmp) (void)hipFreeAsync(tmp, st);
-        *rc_out = e2 ? fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e2)) : 0;
+        *rc_out = launch_status(e2);
         return true;
     }
-    int e = launch_row_pass(logn, mode, r, st);
-    *rc_out = e ? fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e)) : 0;
+    *rc_out = launch_status(launch_row_pass(logn, mode, r, st));
     return true;
 }
 
@@ -890,11 +617,8 @@ static int run_rows_long(swiftly_hip* h, int logn, RowsArgs<double>& a, const Of
         const int rows = std::min(chunk, a.nrows - row0);
         L.row0 = row0;
         L.nrows = rows;
-        int e = launch_fft_long_a(A, tab, L, st);
-        if (e) {
-            rc = fail(SWIFTLY_ERR_HIP, "kernel launch failed (long-row pass A): %s", hipGetErrorString((hipError_t)e));
-            break;
-        }
+        rc = launch_status(launch_fft_long_a(A, tab, L, st), "long-row pass A");
+        if (rc) break;
         B.nrows = rows;
         B.out = a.out + (long long)row0 * a.out_rs;
         B.row_win = a.row_win ? a.row_win + row0 : nullptr;
@@ -1063,7 +787,7 @@ static int run_rows_bluestein(swiftly_hip* h, int64_t n, RowsArgs<R>& a, const O
     B.work = (cx<R>*)w1;
     const unsigned gy = (unsigned)std::min<int64_t>(a.nrows, 65535);
     hipLaunchKernelGGL((blu_load_kernel<R>), dim3((unsigned)((L + 255) / 256), gy, (unsigned)nb), dim3(256), 0, st, B, tab);
-    int rc = (int)hipGetLastError() ? fail(SWIFTLY_ERR_HIP, "kernel launch failed (blu_load)") : 0;
+    int rc = launch_status((int)hipGetLastError(), "blu_load");
     RowsArgs<R> f;
     OffTab none;
     none.use = 0;
@@ -1086,12 +810,12 @@ static int run_rows_bluestein(swiftly_hip* h, int64_t n, RowsArgs<R>& a, const O
         const unsigned gy2 = (unsigned)std::min<int64_t>(rows_total, 65535);
         hipLaunchKernelGGL((blu_mul_kernel<R>), dim3((unsigned)((L + 255) / 256), gy2), dim3(256), 0, st, (cx<R>*)w2, spec,
                            (long long)rows_total, (int)L);
-        if (hipGetLastError() != hipSuccess) rc = fail(SWIFTLY_ERR_HIP, "kernel launch failed (blu_mul)");
+        rc = launch_status((int)hipGetLastError(), "blu_mul");
     }
     if (!rc) rc = fft_L(w2, w1, true);
     if (!rc) {
         hipLaunchKernelGGL((blu_store_kernel<R>), dim3((unsigned)((n + 255) / 256), gy, (unsigned)nb), dim3(256), 0, st, B, tab);
-        if (hipGetLastError() != hipSuccess) rc = fail(SWIFTLY_ERR_HIP, "kernel launch failed (blu_store)");
+        rc = launch_status((int)hipGetLastError(), "blu_store");
     }
     (void)hipFreeAsync(w1, st);
     (void)hipFreeAsync(w2, st);
@@ -1103,26 +827,19 @@ static int run_rows_bluestein(swiftly_hip* h, int64_t n, RowsArgs<R>& a, const O
 template <typename R>
 static int run_rows_mixed(swiftly_hip* h, int64_t n, const swiftly_hip::Mixed& mx, RowsArgs<R>& a, const OffTab& tab,
                           hipStream_t st) {
-    const cx<R>* tw_n;
-    if constexpr (sizeof(R) == 4) tw_n = mx.tw_f; else tw_n = mx.tw_d;
-    if (!tw_n) return fail(SWIFTLY_ERR_UNSUPPORTED, "transform length %lld: no %s tables", (long long)n, sizeof(R) == 8 ? "complex128" : "complex64");
+    MixedArgs<R> X = mixed_args<R>(mx, n);
+    if (!X.tw_n) return fail(SWIFTLY_ERR_UNSUPPORTED, "transform length %lld: no %s tables", (long long)n, sizeof(R) == 8 ? "complex128" : "complex64");
     const int Q = mx.Q, logM = mx.logM;
     const long long M = 1ll << logM;
     const int nb = a.nbatch > 0 ? a.nbatch : 1;
     const long long W = a.nrows;
     if ((uint64_t)n * (uint64_t)W >= (uint64_t(1) << 32))
         return fail(SWIFTLY_ERR_PARAM, "rows * transform length must be < 2^32 for lengths that are not a power of two; split the call");
-    void* scratch = nullptr;
-    HIP_TRY(hipMallocAsync(&scratch, (size_t)nb * (size_t)n * (size_t)W * sizeof(cx<R>), st));
-    MixedArgs<R> X;
-    std::memset(&X, 0, sizeof X);
-    X.Q = Q; X.M = (int)M; X.n = (int)n;
-    for (int r = 0; r < Q; r++) {
-        const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)r / (long double)Q;
-        X.wq[r] = cx<R>{(R)cosl(ang), (R)sinl(ang)};
-    }
-    X.tw_n = tw_n;
-    X.scratch = (cx<R>*)scratch;
+    ScratchLease lease;  // (no workspace reaches the batch primitives: always a stream-ordered allocation)
+    if (int rc = lease.acquire(nullptr, 0, (size_t)nb * (size_t)n * (size_t)W * sizeof(cx<R>), st,
+                               "hipMallocAsync(&scratch, (size_t)nb * (size_t)n * (size_t)W * sizeof(cx<R>), st)"))
+        return rc;
+    X.scratch = (cx<R>*)lease.p;
     X.s_b = (long long)n * W;
     if (a.rowfast) {  // rows are the contiguous direction: scratch[b][j][y2][row]
         X.s_row = 1; X.s_y = W; X.s_j = M * W;
@@ -1131,14 +848,13 @@ static int run_rows_mixed(swiftly_hip* h, int64_t n, const swiftly_hip::Mixed& m
     }
     RowsArgs<R> P = a;
     P.full_n = (int)n;
-    int e = launch_mixed_pass(Q, P, tab, X, nb, st);
-    int rc = e ? fail(SWIFTLY_ERR_HIP, "kernel launch failed (radix-%d pass): %s", Q, hipGetErrorString((hipError_t)e)) : 0;
+    int rc = radix_launch_status(launch_mixed_pass(Q, P, tab, X, nb, st), Q);
     // the Q sub-transforms: ONE launch with j as the kernel's outer index when the sub-transform is a single pass
     // (qadd = -1), one four-step pair per j along a strided axis
     const bool one_launch = !(a.rowfast && logM >= kTwoPassMinLog);
     for (int j = 0; j < (one_launch ? 1 : Q) && !rc; j++) {
         RowsArgs<R> B = a;
-        B.in = (const cx<R>*)scratch + (long long)j * X.s_j;
+        B.in = X.scratch + (long long)j * X.s_j;
         B.in_rs = X.s_row;
         B.in_cs = (unsigned)X.s_y;
         B.in_bs = X.s_b;
@@ -1150,9 +866,7 @@ static int run_rows_mixed(swiftly_hip* h, int64_t n, const swiftly_hip::Mixed& m
         B.in_os = X.s_j;      // (used by the one-launch form only)
         rc = run_rows_chunk(h, logM, B, tab, st, Q, one_launch ? -1 : j);
     }
-    hipError_t e2 = hipFreeAsync(scratch, st);
-    if (!rc && e2 != hipSuccess) rc = fail(SWIFTLY_ERR_HIP, "hipFreeAsync: %s", hipGetErrorString(e2));
-    return rc;
+    return lease.release(rc);
 }
 
 // The gates of run_rows, shared with swiftly_hip_supports_dtype: largest power-of-two length, and whether a length
@@ -1660,8 +1374,7 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
     if (e == -2)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_window_rows: needs yN_size 32768, contribution size 512, even facet "
                     "size / offset / row stride and a band of at most %d physical columns", row_pass_whole_stage_columns());
-    if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return 0;
+    return launch_status(e);
 }
 
 int swiftly_hip_prepare_facet_band_rows(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,

@@ -1,7 +1,7 @@
 // Internals shared by the translation units of the C ABI (swiftly_abi.hip: handles + the eight primitives and their
-// batch forms; swiftly_abi_pipeline.hip: the fused / per-wave entry points of the streaming classes;
-// swiftly_abi_util.hip: device memory, stream and diagnostic helpers).  Not installed: include/swiftly_hip.h is the
-// public header.
+// batch forms; swiftly_abi_coltransform.hip: the strided-axis transform, col_transform; swiftly_abi_pipeline.hip: the
+// fused / per-wave entry points of the streaming classes; swiftly_abi_util.hip: device memory, stream and diagnostic
+// helpers).  Not installed: include/swiftly_hip.h is the public header.
 #pragma once
 
 #include <algorithm>
@@ -47,6 +47,31 @@ int fail(int code, const char* fmt, ...);
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) return fail(SWIFTLY_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+// Status of a kernel launcher's return value `e` (a hipError_t, or negative: no instance): 0, or SWIFTLY_ERR_HIP and the
+// message "...[ (what)]: <error>".  `negative`: the text for e < 0 ("no instance"), else hipGetErrorString takes every value.
+int launch_status(int e, const char* what = nullptr, const char* negative = nullptr);
+int radix_launch_status(int e, int Q, const char* pass = "pass");  // what = "radix-<Q> <pass>"
+
+// Scratch of one call: the caller's workspace when it is big enough, else a stream-ordered allocation that release()
+// frees on the same stream.  No destructor: a path that forgets release() leaks visibly instead of queueing a hidden free.
+struct ScratchLease {
+    void* p = nullptr; bool own = false; hipStream_t st = nullptr;
+    int acquire(void* ws, size_t ws_bytes, size_t need, hipStream_t stream, const char* what) {  // error: "<what>: <hip error>"
+        own = !(ws && ws_bytes >= need);
+        st = stream;
+        p = ws;
+        if (!own) return 0;
+        const hipError_t e = hipMallocAsync(&p, need, st);
+        if (e == hipSuccess) return 0;
+        own = false;
+        return fail(SWIFTLY_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    }
+    int release(int rc) {  // `rc`: the status of the work on the scratch; a failed free is reported only when that was 0
+        const hipError_t e = own ? hipFreeAsync(p, st) : hipSuccess;
+        own = false;
+        return (!rc && e != hipSuccess) ? fail(SWIFTLY_ERR_HIP, "hipFreeAsync: %s", hipGetErrorString(e)) : rc;
+    }
+};
 
 static inline int64_t floordiv(int64_t a, int64_t b) {
     int64_t q = a / b;
@@ -106,6 +131,29 @@ struct swiftly_hip : Sizes {  // N, yN, xM, m and log_yN, log_xM, log_m (swiftly
     Win4Cache win4;
 };
 
+// The radix-Q descriptor of a length n = Q * 2^k (swiftly_mixed.h); the caller adds `scratch` and the s_* strides of its layout.
+template <typename R>
+inline MixedArgs<R> mixed_args(const swiftly_hip::Mixed& mx, int64_t n) {
+    MixedArgs<R> X;
+    std::memset(&X, 0, sizeof X);
+    X.Q = mx.Q; X.M = (int)(1ll << mx.logM); X.n = (int)n;
+    for (int r = 0; r < mx.Q; r++) {
+        const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)r / (long double)mx.Q;
+        X.wq[r] = cx<R>{(R)cosl(ang), (R)sinl(ang)};
+    }
+    if constexpr (sizeof(R) == 4) X.tw_n = mx.tw_f; else X.tw_n = mx.tw_d;
+    return X;
+}
+// Workspace of the band entry points at such a length: [radix-Q scratch: nf * yN * m][sub-transform scratch: nf * M * m, + 4096]
+struct MixedWorkspace {
+    size_t radix_bytes, sub_bytes;
+    MixedWorkspace(int nf, int yN, long long M, int m)
+        : radix_bytes((size_t)nf * (size_t)yN * (size_t)m * sizeof(cx<float>)),
+          sub_bytes((size_t)nf * (size_t)M * (size_t)m * sizeof(cx<float>) + 4096) {}
+    size_t bytes() const { return radix_bytes + sub_bytes; }
+    char* sub(void* base) const { return (char*)base + radix_bytes; }
+};
+
 // swiftly_hip_chain_chunk_streams (include/swiftly_hip.h): the calling thread's chunked four-step launches skip their fork
 extern thread_local int g_chain_chunk_streams;
 
@@ -162,7 +210,7 @@ static inline const cx<float>* cx_at(const void* p, int64_t k, bool c128) {
 static inline cx<float>* cx_at(void* p, int64_t k, bool c128) {
     return (cx<float>*)((char*)p + k * (int64_t)(c128 ? sizeof(cx<double>) : sizeof(cx<float>)));
 }
-// column-tile passes (swiftly_abi.hip)
+// column-tile passes (swiftly_abi_coltransform.hip)
 ColZ plain_colz();
 // single-pass launch of length 2^logn: float64 arithmetic when the handle asks for it and the instance exists
 inline void set_col_precision(const swiftly_hip* h, ColPassArgs& c, int logn) {

@@ -65,8 +65,7 @@ int swiftly_hip_sum_finish_rows(swiftly_hip_t* h, int dtype, const void* in, int
         a.out = (cx<float>*)out + b0 * out_batch_stride;
         a.mask = mask ? (const float*)mask + b0 * mask_batch_stride : nullptr;
         for (int b = 0; b < nb; b++) a.st_a[b] = pmod(-(xM / 2 - xA / 2 + subgrid_offs[b0 + b]), xM);
-        int e = launch_sum_finish_rows(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
-        if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        if (int rc = launch_status(launch_sum_finish_rows(h->log_m, h->log_xM, a, nb, (hipStream_t)stream))) return rc;
     }
     return 0;
 }
@@ -160,18 +159,15 @@ static int prepare_facet_columns_mixed(swiftly_hip_t* h, const void* in, int64_t
         return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");
     const int lo = yN / 2 - (int)(rows / 2);
     hipStream_t st = (hipStream_t)stream;
-    // workspace: [radix-Q scratch: nf * yN * m][four-step scratch of the sub-transforms: nf * M * m]
+    MixedArgs<float> X = mixed_args<float>(it->second, yN);
+    X.s_row = 1; X.s_y = m; X.s_j = M * m; X.s_b = (long long)yN * m;
     const int per_f_cap = (int)std::min<int64_t>(kMaxBatch, kColZF);
     for (int64_t f0 = 0; f0 < nfacets; f0 += per_f_cap) {
         const int nf = (int)std::min<int64_t>(per_f_cap, nfacets - f0);
-        const size_t radix_bytes = (size_t)nf * (size_t)yN * (size_t)m * sizeof(cx<float>);
-        const size_t sub_bytes = (size_t)nf * (size_t)M * (size_t)m * sizeof(cx<float>) + 4096;
-        void* own = nullptr;
-        char* base = (char*)ws;
-        if (!ws || ws_bytes < radix_bytes + sub_bytes) {
-            HIP_TRY(hipMallocAsync(&own, radix_bytes + sub_bytes, st));
-            base = (char*)own;
-        }
+        const MixedWorkspace part(nf, yN, M, m);
+        ScratchLease lease;
+        if (int rc = lease.acquire(ws, ws_bytes, part.bytes(), st, "hipMallocAsync(&own, radix_bytes + sub_bytes, st)")) return rc;
+        X.scratch = (cx<float>*)lease.p;
         int rc = 0;
         for (int64_t w = 0; w < nwaves && !rc; w++) {
             const int64_t s1 = floordiv(wave_off1s[w] * h->yN, h->N);
@@ -195,23 +191,13 @@ static int prepare_facet_columns_mixed(swiftly_hip_t* h, const void* in, int64_t
             OffTab tab;
             tab.use = 1;
             for (int f = 0; f < nf; f++) tab.ld_a[f] = pmod(-(facet_off0s[f0 + f] + lo), yN);
-            MixedArgs<float> X;
-            std::memset(&X, 0, sizeof X);
-            X.Q = Q; X.M = (int)M; X.n = yN;
-            for (int r = 0; r < Q; r++) {
-                const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)r / (long double)Q;
-                X.wq[r] = cx<float>{(float)cosl(ang), (float)sinl(ang)};
-            }
-            X.tw_n = it->second.tw_f;
-            X.scratch = (cx<float>*)base;
-            X.s_row = 1; X.s_y = m; X.s_j = M * m; X.s_b = (long long)yN * m;
-            int e = launch_mixed_pass(Q, a, tab, X, nf, st);
-            if (e) { rc = fail(SWIFTLY_ERR_HIP, "kernel launch failed (radix-%d pass): %s", Q, hipGetErrorString((hipError_t)e)); break; }
+            rc = radix_launch_status(launch_mixed_pass(Q, a, tab, X, nf, st), Q);
+            if (rc) break;
             for (int j = 0; j < Q && !rc; j++) {
                 ColPassArgs c;
                 std::memset(&c, 0, sizeof c);
                 c.ncols = m;
-                c.in = (const cx<float>*)base + (long long)j * X.s_j;
+                c.in = X.scratch + (long long)j * X.s_j;
                 c.in_pitch = (unsigned)m;
                 c.in_bs = X.s_b;
                 c.out = (cx<float>*)out + f0 * out_facet_stride + w * out_wave_stride;
@@ -223,16 +209,12 @@ static int prepare_facet_columns_mixed(swiftly_hip_t* h, const void* in, int64_t
                 c.conj_ld = 0; c.conj_st = 1;
                 c.st_rowmap = rowmaps ? rowmaps + w * rowmap_stride : nullptr;
                 c.st_rowmap_bs = 0;
-                const int r2 = col_transform(h, logM, c, plain_colz(), m, nf, st, base + radix_bytes, sub_bytes, Q, j, yN);
+                const int r2 = col_transform(h, logM, c, plain_colz(), m, nf, st, part.sub(lease.p), part.sub_bytes, Q, j, yN);
                 if (r2 == -1) rc = fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: sub-transform length %lld not supported", M);
                 else rc = r2;
             }
         }
-        if (own) {
-            hipError_t e2 = hipFreeAsync(own, st);
-            if (!rc && e2 != hipSuccess) rc = fail(SWIFTLY_ERR_HIP, "hipFreeAsync: %s", hipGetErrorString(e2));
-        }
-        if (rc) return rc;
+        if ((rc = lease.release(rc))) return rc;
     }
     return 0;
 }
@@ -510,7 +492,7 @@ static int sum_finish_facets_impl(swiftly_hip_t* h, int dtype, const void* in, i
         for (int b = 0; b < nb; b++) a.st_a[b] = pmod(-(xM / 2 - xA / 2 + subgrid_off1s[b0 + b]), xM);
         int e = c128 ? launch_sum_finish_facets_c128(h->log_m, h->log_xM, a, nb, (hipStream_t)stream)
                      : launch_sum_finish_facets(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
-        if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        if (int rc = launch_status(e)) return rc;
     }
     return 0;
 }
@@ -562,9 +544,7 @@ int swiftly_hip_finish_axis1_rows(swiftly_hip_t* h, int dtype, const void* bands
     a.tw_m = twiddles<float>(h, h->log_m);
     a.twc_m = compact_twiddles(h, h->log_m, h->log_m - 6);
     if (!a.tw_m || !a.twc_m) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
-    int e = launch_axis1_rows(h->log_m, a, (int)nfacets, (hipStream_t)stream);
-    if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", e > 0 ? hipGetErrorString((hipError_t)e) : "no instance");
-    return 0;
+    return launch_status(launch_axis1_rows(h->log_m, a, (int)nfacets, (hipStream_t)stream), nullptr, "no instance");
 }
 
 /* Backward subgrid side, contiguous-axis half + axis-0 remainder (see swiftly_sumfinish.h): in[b] = [xM, xA] =
@@ -616,7 +596,7 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
         for (int b = 0; b < nb; b++) a.ld_a[b] = pmod(-(xM / 2 - xA / 2 + subgrid_off1s[b0 + b]), xM);
         int e = c128 ? launch_split_prepare_facets_c128(h->log_m, h->log_xM, a, nb, (hipStream_t)stream)
                      : launch_split_prepare_facets(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
-        if (e) return fail(SWIFTLY_ERR_HIP, "kernel launch failed: %s", e > 0 ? hipGetErrorString((hipError_t)e) : "no instance");
+        if (int rc = launch_status(e, nullptr, "no instance")) return rc;
     }
     // axis-0 remainder of extract_from_subgrid, in place: out[f][b][:, j] = cifft_m( Fn[k] * E[f][b][(k - s'0_f) ..., j] )
     ColPassArgs c;
@@ -837,7 +817,7 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
     c.cg_mod = m; c.cg_full = yN;
     c.cg_band_start = (int)band_start; c.cg_band_len = (int)band_len; c.cg_band_half = 0;
     const int64_t cap = workspace ? workspace_bytes : (int64_t(4) << 30);
-    const int64_t per_item = mx ? ((int64_t)yN + (int64_t(1) << mx->logM)) * m * 8 + 4096 : (int64_t)yN * m * (c128 ? 16 : 8);
+    const int64_t per_item = mx ? (int64_t)MixedWorkspace(1, yN, 1ll << mx->logM, m).bytes() : (int64_t)yN * m * (c128 ? 16 : 8);
     const int per_f = (int)std::max<int64_t>(1, std::min<int64_t>(kColZF, cap / per_item));
     const int64_t s1 = floordiv(subgrid_off1 * h->yN, h->N);
     for (int64_t f0 = 0; f0 < nfacets; f0 += per_f) {
@@ -860,18 +840,13 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
             rc = col_transform(h, h->log_yN, c, cz, m, nf, (hipStream_t)stream, workspace,
                                workspace ? (size_t)workspace_bytes : 0);
         } else {
-            // workspace: [radix-Q scratch nf * yN * m][four-step scratch of the sub-transforms nf * M * m]
             const int Q = mx->Q, logM = mx->logM;
             const long long M = 1ll << logM;
-            const size_t radix_bytes = (size_t)nf * (size_t)yN * (size_t)m * sizeof(cx<float>);
-            const size_t sub_bytes = (size_t)nf * (size_t)M * (size_t)m * sizeof(cx<float>) + 4096;
+            const MixedWorkspace part(nf, yN, M, m);
             hipStream_t st = (hipStream_t)stream;
-            void* own = nullptr;
-            char* base = (char*)workspace;
-            if (!workspace || (size_t)workspace_bytes < radix_bytes + sub_bytes) {
-                HIP_TRY(hipMallocAsync(&own, radix_bytes + sub_bytes, st));
-                base = (char*)own;
-            }
+            ScratchLease lease;
+            if ((rc = lease.acquire(workspace, (size_t)workspace_bytes, part.bytes(), st, "hipMallocAsync(&own, radix_bytes + sub_bytes, st)")))
+                return rc;
             MixedGsArgs g;
             std::memset(&g, 0, sizeof g);
             g.in = (const cx<float>*)parts;
@@ -882,30 +857,19 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
                 g.c_base[k] = cz.c_base[k];
                 g.c_fs[k] = cz.c_fs[k];
             }
-            MixedArgs<float> X;
-            std::memset(&X, 0, sizeof X);
-            X.Q = Q; X.M = (int)M; X.n = yN;
-            for (int r = 0; r < Q; r++) {
-                const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)r / (long double)Q;
-                X.wq[r] = cx<float>{(float)cosl(ang), (float)sinl(ang)};
-            }
-            X.tw_n = mx->tw_f;
-            X.scratch = (cx<float>*)base;
+            MixedArgs<float> X = mixed_args<float>(*mx, yN);
+            X.scratch = (cx<float>*)lease.p;
             X.s_row = 1; X.s_y = m; X.s_j = M * m; X.s_b = (long long)yN * m;
-            int e = launch_mixed_gs_pass(Q, g, X, nf, st);
-            if (e) rc = fail(SWIFTLY_ERR_HIP, "kernel launch failed (radix-%d gather-sum pass): %s", Q, hipGetErrorString((hipError_t)e));
+            rc = radix_launch_status(launch_mixed_gs_pass(Q, g, X, nf, st), Q, "gather-sum pass");
             for (int j = 0; j < Q && !rc; j++) {
                 ColPassArgs cs = c;  // the store side of the primitive; plain load from the pass's scratch
-                cs.in = (const cx<float>*)base + (long long)j * X.s_j;
+                cs.in = X.scratch + (long long)j * X.s_j;
                 cs.in_pitch = (unsigned)m;
                 cs.in_bs = X.s_b; cs.in_bdiv = 0; cs.in_bs_hi = 0;
                 cs.ld_rowmap = nullptr; cs.gs = 0;
-                rc = col_transform(h, logM, cs, cz, m, nf, st, base + radix_bytes, sub_bytes, Q, j, yN);
+                rc = col_transform(h, logM, cs, cz, m, nf, st, part.sub(lease.p), part.sub_bytes, Q, j, yN);
             }
-            if (own) {
-                hipError_t e2 = hipFreeAsync(own, st);
-                if (!rc && e2 != hipSuccess) rc = fail(SWIFTLY_ERR_HIP, "hipFreeAsync: %s", hipGetErrorString(e2));
-            }
+            rc = lease.release(rc);
         }
         if (rc == -1) return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: padded facet size %d not supported", yN);
         if (rc) return rc;

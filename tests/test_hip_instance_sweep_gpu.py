@@ -664,6 +664,72 @@ def test_prepare_facet_columns_c128_chunked_bit_identical(tmp_path):
             assert numpy.array_equal(a, b), (yN, use_rowmap)
 
 
+K2_C64_CHUNK_LENGTHS = [11, 13]  # log2 yN: the four-step splits 5+6 and 6+7
+
+
+def k2_c64_problem(L):
+    """``(core, oracle core, band rows [2, 96, yN], facet off0s, subgrid off1, row map, rows kept)`` of the complex64 chunk
+    test: the K2 case of the facet sweep at ``yN = 2^L`` (m = 128, 2 facets, its seed) with the negative ``off1``"""
+    import test_hip_facet_sweep_gpu as fs
+
+    core, ref = fs.cores(fs.params(L))
+    logical = fs.crandn(numpy.random.default_rng(600 + L), (2, 96, core.yN_size))
+    off0s, off1s, map_offs = fs.k2_offsets(core)
+    rowmap, n_kept = core.subgrid_column_rows(map_offs)
+    return core, ref, logical, off0s, off1s[1], rowmap, n_kept
+
+
+_K2_C64_CHILD = r"""
+import sys, numpy, torch
+sys.path[:0] = [sys.argv[2] + "/tests", sys.argv[2], sys.argv[3]]
+import test_hip_facet_sweep_gpu as fs
+import test_hip_instance_sweep_gpu as t
+for L in t.K2_C64_CHUNK_LENGTHS:
+    core, _, logical, off0s, off1, rowmap, n_kept = t.k2_c64_problem(L)
+    dev = torch.from_numpy(logical).cuda()
+    for bits in (32, 64):
+        with fs.precision(core, bits):
+            for use_rowmap in (False, True):
+                got = fs.k2_run(core, dev, off0s, (0, core.yN_size), off1, rowmap if use_rowmap else None,
+                                n_kept if use_rowmap else core.yN_size)
+                numpy.save(f"{sys.argv[1]}_{L}_{bits}_{int(use_rowmap)}.npy", got)
+"""
+
+
+def test_prepare_facet_columns_c64_chunked_bit_identical(tmp_path):
+    """the chunked two-stream four-step of COMPLEX64 K2 (which otherwise runs at the benchmark's size only) gives the same
+    bits as the plain one at 2048 (5+6) and 8192 (6+7) points, m = 128, 2 facets, with and without a row map, in float32
+    and in float64 arithmetic: ``SWIFTLY_K2_CHUNK=64,1`` makes four chunks (2 items x 2 x 64 columns) that alternate between
+    the two streams; one fresh child process per setting (the variable is read once per process).  The plain result also
+    meets the facet sweep's bound for its length and arithmetic against the oracle: identical means identically right."""
+    import test_hip_facet_sweep_gpu as fs
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pkg = os.path.join(root, "ska-sdp-distributed-fourier-transform_amd")
+    stems = []
+    for chunk in ("0", "64,1"):
+        stem = str(tmp_path / f"chunk_{chunk.replace(',', '_')}")
+        env = dict(os.environ, SWIFTLY_K2_CHUNK=chunk)
+        res = subprocess.run([sys.executable, "-c", _K2_C64_CHILD, stem, root, pkg], env=env, cwd=root, timeout=600,
+                             capture_output=True, text=True, check=False)
+        assert res.returncode == 0, (chunk, res.returncode, res.stderr[-3000:])
+        stems.append(stem)
+    for L in K2_C64_CHUNK_LENGTHS:
+        core, ref, logical, off0s, off1, rowmap, n_kept = k2_c64_problem(L)
+        yN, rm = core.yN_size, rowmap.cpu().numpy()
+        assert core.xM_yN_size == 128 and 0 < n_kept < yN
+        want = [fs.k2_want(ref, logical[f], off0s[f], off1) for f in range(2)]
+        for bits in (32, 64):
+            for use_rowmap in (0, 1):
+                plain, chunked = (numpy.load(f"{stem}_{L}_{bits}_{use_rowmap}.npy") for stem in stems)
+                assert plain.dtype == numpy.complex64 and plain.shape == chunked.shape == (2, n_kept if use_rowmap else yN, 128)
+                assert numpy.array_equal(plain, chunked), (L, bits, use_rowmap)
+                keep = rm >= 0 if use_rowmap else numpy.ones(yN, dtype=bool)
+                idx = rm[keep] if use_rowmap else numpy.arange(yN)
+                fs.check("K2 complex64, chunks off", L, bits, plain[:, idx], numpy.stack([w[keep] for w in want]), 1,
+                         fs.k2_has_f64(L), note=f"rowmap {use_rowmap}")
+
+
 # ------------------------------------------------------------------------------------------- (g) tables stay in step
 def _cell_params(logm, logx):
     """a valid parameter set with ``m = 2^logm`` and ``xM = 2^logx`` (``m < xM``: ``N = 2 xM``, ``yN = 2 m``), else None"""

@@ -1,7 +1,7 @@
 // SwiFTly on MI355X: both passes of a four-step column transform in ONE launch, the intermediate handed over in flight.
 //
-// col_transform (swiftly_abi.hip) runs a strided-axis transform of more than 1024 points as pass A (length n1, writes
-// the scratch [batch][N][W]) and pass B (length n2, reads it back): for K2 of the 64k workload that is 1.21 GB written
+// col_transform (swiftly_abi_coltransform.hip) runs a strided-axis transform of more than 1024 points as pass A (length n1,
+// writes the scratch [batch][N][W]) and pass B (length n2, reads it back): for K2 of the 64k workload that is 1.21 GB written
 // and 1.21 GB re-read per wave, a third of the pass's HBM traffic, long after the 256 MiB Infinity Cache has lost it.
 // Here the two passes are workgroups of one grid.  The unit of hand-over is a CHUNK = one (batch item, 64-column tile):
 // 2^l2 / SUB pass-A workgroups write its N x 64 intermediate (16.8 MB at N = 32768), 2^l1 pass-B workgroups read it.
