@@ -179,7 +179,7 @@ class SwiftlyBackward:
             staged["buf"][len(staged["cfgs"])].copy_(ten)
             staged["cfgs"].append(sg)
         if planned is not None and len(staged["cfgs"]) >= planned:
-            self.lru._items.pop(key, None)  # pylint: disable=protected-access
+            self.lru.discard(key)
             return self._flush_staged(staged)
         old_key, old = self.lru.set(key, staged)
         if old_key is not None and old is not None:

@@ -481,11 +481,10 @@ class DistributedForward:
         b, h, _, _ = self._coop_bands.sub[self.rank]
         fwd = self._coop[j]
         yB = self.facet_configs[j].size
-        fwd.BF_Fs_persist = recv.view(1, yB, 2 * h)
-        fwd._band = b  # pylint: disable=protected-access
-        # the band buffer did not come from the object's own K1, which is where it would have chosen its axis-1-first mode:
-        # choose it here (axis1_fused is off: a row pass per wave in front of K2, or 0), as the receiver's placed mode expects
-        fwd.__dict__["_axis1_mode"] = fwd._choose_axis1_mode()  # pylint: disable=protected-access
+        # installed as the object's own K1 would (axis1_fused is off: the axis-1-first mode is a row pass per wave in front of
+        # K2, or 0, as the receiver's placed mode expects); no bands-ready event: every prefetched K2 waits for this stream
+        fwd.set_band(b)
+        fwd.install_bands(recv.view(1, yB, 2 * h))
 
     def prepare_all_facets(self):
         """K1 for the local facets; cooperative facets: K1 on this rank's rows and the exchange of the band rows"""

@@ -5,6 +5,7 @@ contiguous-axis-first band pipeline (``wave_axis=1``).
 """
 import logging
 import os
+from functools import cached_property
 
 import numpy
 
@@ -55,6 +56,7 @@ class SwiftlyForward(WavePrefetch):
         self, swiftly_config, facet_tasks, lru_forward=1, queue_size=20, client=None, subgrid_configs=None,
         wave_axis=None, delayed=False,
     ):
+        WavePrefetch.__init__(self)
         self.delayed = bool(delayed)  # hand out DeviceTask handles instead of bare device tensors
         facet_tasks = [(cfg, _unwrap(data)) for cfg, data in facet_tasks]
         self.config = swiftly_config
@@ -65,7 +67,10 @@ class SwiftlyForward(WavePrefetch):
         self.queue_size = queue_size
         self._client = client
         self.lru = LRUCache(lru_forward)
-        self.BF_Fs_persist = None
+        # valid for one set of band buffers (set_band / install_bands): the buffers, their band, the axis-1-first mode and
+        # mode 2's {wave key: window}; the event behind K1, the one the side stream waited for, "a prefetched K2 has forked"
+        self.BF_Fs_persist, self._band, self._axis1_mode, self._window_of = None, None, None, None
+        self._bands_ready, self._side_waited, self._k2_chain_forked = None, None, False
         self._prewindowed = False
         torch = _torch()
         # facet ingestion (host <-> device edge): device tensors are used in place; host (numpy) facets are
@@ -92,19 +97,43 @@ class SwiftlyForward(WavePrefetch):
         # optional plan (extension): when the caller knows up front which subgrids it will ask for (sparse
         # covers, scripts/demo_sparse_facet.py style), the facet-sized intermediate only keeps what those read
         self._rowmap, self._n_rows = None, None
-        self._plan = None
+        self._plan, self._planned_keys = None, None
         if subgrid_configs is not None:
             self._plan = list(subgrid_configs)
             if self.wave_axis == 0:
                 self._rowmap, self._n_rows = self.core.subgrid_column_rows([sg.off0 for sg in subgrid_configs])
             self._planned_keys = {int(self._key(sg)) for sg in subgrid_configs}
-        self._band = None
         self._wave_rowmaps = {}
         # finished subgrids computed ahead of their request (see get_subgrid_tasks): (off0, off1, size, id) -> tensor
         self._results = {}
         self._result_bytes = 0
         self._result_budget = int(float(os.environ.get("SWIFTLY_RESULT_CACHE_GB", "16")) * 2**30)
-        self._plan_waves = None
+
+    # -- tables derived from the plan: each built on first use by ONE walk over the plan (505 configs x 25 waves on every
+    # pass otherwise), and not at all for objects that never need it
+    @cached_property
+    def _plan_waves(self):
+        """({(wave key, size): planned subgrids in plan order, duplicates dropped}, {identities of the planned subgrids})"""
+        waves, seen = {}, set()
+        for c in self._plan:
+            r = self._rid(c)
+            if r not in seen:
+                seen.add(r)
+                waves.setdefault((int(self._key(c)), int(c.size)), []).append(c)
+        return waves, seen
+
+    @cached_property
+    def _plan_off0s(self):
+        """{off1: the off0 of the planned subgrids of that wave}"""
+        by_key = {}
+        for sg in self._plan:
+            by_key.setdefault(int(sg.off1), []).append(sg.off0)
+        return by_key
+
+    @cached_property
+    def _plan_set(self):
+        """{(off0, off1) of the planned subgrids}"""
+        return {(int(sg.off0), int(sg.off1)) for sg in self._plan}
 
     def _band_pipeline_ok(self):
         """the contiguous-axis-first pipeline can serve these facets (sizes, dtype, layout, facet count)"""
@@ -224,15 +253,6 @@ class SwiftlyForward(WavePrefetch):
         a plan or when ``sg`` is not in the plan)"""
         if self._plan is None:
             return None
-        if self._plan_waves is None:
-            waves, seen = {}, set()
-            for c in self._plan:
-                r = self._rid(c)
-                if r in seen:
-                    continue
-                seen.add(r)
-                waves.setdefault((int(self._key(c)), int(c.size)), []).append(c)
-            self._plan_waves = (waves, seen)
         waves, seen = self._plan_waves
         if self._rid(sg) not in seen:
             return None
@@ -357,26 +377,7 @@ class SwiftlyForward(WavePrefetch):
         ``flat``: block (f, i) at ``layout[0][i] + f * layout[1][i]`` elements -- one native call
         (contiguous-axis-first pipeline only)."""
         self._check_planned(sgs)
-        bands = self.prepare_all_facets()
-        Q, rowmap, n_rows, compute = self._wave_Q(sgs[0].off1)
-        # (r6) the same free-running K2 chain as _wave_b: K2 of the next waves of the announced order (set_wave_order; the
-        # plan's own order otherwise) goes to the side stream before this wave's K3 -- the multi-GPU pass used to compute
-        # every K2 on the caller's stream (41.4 against 35.5 ms at world 1)
-        nxt = self._predict_next_waves(sgs[0].off1, _knobs()._PREFETCH_DEPTH)
-        if not compute:
-            self._prefetch_waves(nxt)
-        band = self._band
-        if compute:
-            bands, band = self._k2_source(sgs[0].off1)
-        try:
-            self.core.wave_facet_side(bands, [cfg.off0 for cfg in self.facet_configs], band, sgs[0].off1, rowmap,
-                                      n_rows, Q, compute, [sg.off0 for sg in sgs], flat, g_layout=layout)
-        except Exception:
-            if compute:  # Q was registered before it was computed: a later request must not find garbage
-                self.lru._items.pop(("b", sgs[0].off1), None)  # pylint: disable=protected-access
-            raise
-        if compute:
-            self._prefetch_waves(nxt)
+        self._facet_side(sgs, flat, layout)
 
     def _wave(self, sgs):
         # single-GPU route: the [m, m] contributions are never materialised -- the window gather is
@@ -421,17 +422,15 @@ class SwiftlyForward(WavePrefetch):
             torch = _torch()
             core = self.core
             # (complex128: K1 keeps the whole padded axis in the plain band layout)
-            self._band = (
+            mode = self.set_band(
                 core.band_for_offsets([sg.off1 for sg in self._plan])
                 if self._plan is not None and self.dtype == torch.complex64 else (0, core.yN_size)
             )
             F, yB = len(self._facet_info), self._facet_info[0][1][0]
-            mode = self.__dict__["_axis1_mode"] = self._choose_axis1_mode()
             if mode == 2:
                 # axis-1-first pipeline, contiguous-axis finish fused into K1: per facet row, for every planned window, the
                 # finished window row (core.prepare_facet_window_rows) instead of the band
-                keys = sorted(self._planned_keys)
-                self.__dict__["_window_of"] = {k: w for w, k in enumerate(keys)}
+                keys = list(self._window_of)
                 starts = torch.tensor(core.window_starts(self._band, keys), dtype=torch.int32, device=core.device)
                 # wave-major: K2 of wave w reads the contiguous block [f, w] (side by side in a row measured the same)
                 bands = torch.empty((F, len(keys), yB, core.xM_yN_size), dtype=self.dtype, device=core.device)
@@ -447,12 +446,27 @@ class SwiftlyForward(WavePrefetch):
                 if timer is not None:
                     timer.stop("K1_full_facet_transform", t0)
                 self._ingest.prefetch(j + 1)
-            self.BF_Fs_persist = bands
-            self.__dict__["_k2_chain_forked"] = False  # new band buffers: the next prefetched K2 forks behind K1 again
+            ready = None
             if self._plan is not None and _knobs()._PREFETCH and _knobs()._PREFETCH_DEPTH >= 2:
-                ready = self.__dict__["_bands_ready"] = torch.cuda.Event()
+                ready = torch.cuda.Event()
                 ready.record(torch.cuda.current_stream(core.device))
+            self.install_bands(bands, ready)
         return self.BF_Fs_persist
+
+    def set_band(self, band):
+        """First step of installing band buffers: the band they cover decides the axis-1-first mode (returned) and, in mode
+        2, the window table -- and with them the shape of the buffers (``[F, W, yB, m]`` against ``[F, yB, band columns]``)."""
+        self._band = band
+        self._axis1_mode = self._choose_axis1_mode()
+        self._window_of = {k: w for w, k in enumerate(sorted(self._planned_keys))} if self._axis1_mode == 2 else None
+        return self._axis1_mode
+
+    def install_bands(self, bands, ready=None):
+        """Second step: the finished buffers (this object's own K1 output, or what the band-row exchange of the multi-GPU
+        pass assembled).  ``ready``: an event recorded behind K1, which lets the side stream run K2 ahead without a hand-over
+        per wave (_prefetch_wave); without it every prefetched K2 waits for the caller's stream and none is chained."""
+        self.BF_Fs_persist, self._bands_ready = bands, ready
+        self._k2_chain_forked = False  # new band buffers: the next prefetched K2 forks behind K1 again
 
     def _wave_rows(self, off1):
         """(rowmap, n_rows) of the axis-0 rows the planned subgrids of wave ``off1`` read (None = all rows)."""
@@ -460,12 +474,7 @@ class SwiftlyForward(WavePrefetch):
             return None, self.core.yN_size
         key = int(off1)
         if key not in self._wave_rowmaps:
-            by_key = self.__dict__.get("_plan_off0s")
-            if by_key is None:  # one walk over the plan, not one per wave (505 configs x 25 waves on every pass)
-                by_key = self.__dict__["_plan_off0s"] = {}
-                for sg in self._plan:
-                    by_key.setdefault(int(sg.off1), []).append(sg.off0)
-            self._wave_rowmaps[key] = self.core.subgrid_column_rows(by_key.get(key, []))
+            self._wave_rowmaps[key] = self.core.subgrid_column_rows(self._plan_off0s.get(key, []))
         return self._wave_rowmaps[key]
 
     #: may the axis-1-first pipeline fuse the contiguous-axis finish into K1?  The multi-GPU classes switch this off for the
@@ -487,7 +496,7 @@ class SwiftlyForward(WavePrefetch):
     def _axis1(self):
         """the axis-1-first mode of this object (``SwiftlyConfig(axis1_first=True)``, wave_axis = 1): 0 = off, 1 = row pass
         per wave, 2 = fused into K1 (decided when the facets are prepared)"""
-        mode = self.__dict__.get("_axis1_mode")
+        mode = self._axis1_mode
         if mode is None:
             mode = self._choose_axis1_mode() if self.BF_Fs_persist is None else 0
         return mode
@@ -511,15 +520,22 @@ class SwiftlyForward(WavePrefetch):
             return bands[:, w], (start, m)
         return self.core.finish_axis1_rows(bands, [cfg.off1 for cfg in self.facet_configs], self._band, off1)
 
-    def _get_wave_columns(self, off1):
-        """K2: ``Q[F, rows, m]`` for the subgrid wave ``off1`` (LRU cached like the reference's per-off0 columns)."""
+    def _lookup_Q(self, off1):
+        """What the two forms of K2 share: a prefetched ``Q`` of wave ``off1`` is taken over, a cached one answers ``((Q,
+        rowmap), rowmap, n_rows)``; otherwise the wave is checked against the plan: ``(None, rowmap, n_rows)`` of its rows."""
         self._take_prefetched(off1)
         hit = self.lru.get(("b", off1))
+        if hit is not None:
+            return hit, hit[1], hit[0].shape[1]
+        if self._plan is not None and int(off1) not in self._planned_keys:
+            raise ValueError(f"subgrid wave off1={off1} was not in the subgrid_configs plan")
+        self.prepare_all_facets()
+        return (None, *self._wave_rows(off1))
+
+    def _get_wave_columns(self, off1):
+        """K2: ``Q[F, rows, m]`` for the subgrid wave ``off1`` (LRU cached like the reference's per-off0 columns)."""
+        hit, rowmap, n_rows = self._lookup_Q(off1)
         if hit is None:
-            if self._plan is not None and int(off1) not in self._planned_keys:
-                raise ValueError(f"subgrid wave off1={off1} was not in the subgrid_configs plan")
-            self.prepare_all_facets()
-            rowmap, n_rows = self._wave_rows(off1)
             bands, band = self._k2_source(off1)
             Q = self.core.prepare_facet_columns(
                 bands, [cfg.off0 for cfg in self.facet_configs], band, off1, rowmap, n_rows
@@ -529,12 +545,8 @@ class SwiftlyForward(WavePrefetch):
         return hit
 
     def _check_planned(self, sgs):
-        if self._plan is not None:
-            allowed = self.__dict__.get("_plan_set")
-            if allowed is None:  # (built once: a set comprehension as a setdefault argument would run on every call)
-                allowed = self.__dict__["_plan_set"] = {(int(sg.off0), int(sg.off1)) for sg in self._plan}
-            if any((int(sg.off0), int(sg.off1)) not in allowed for sg in sgs):
-                raise ValueError("subgrid was not in the subgrid_configs plan")
+        if self._plan is not None and any((int(sg.off0), int(sg.off1)) not in self._plan_set for sg in sgs):
+            raise ValueError("subgrid was not in the subgrid_configs plan")
 
     def _wave_b_staged(self, sgs):
         """stage-by-stage form (one ABI call per kernel group; used when the stages are timed separately)"""
@@ -544,47 +556,49 @@ class SwiftlyForward(WavePrefetch):
                                     placed=self._placed())
 
     def _wave_Q(self, off1):
-        """(Q workspace, rowmap, n_rows, needs computing) of wave ``off1`` (LRU cached like _get_wave_columns)"""
-        torch = _torch()
-        self._take_prefetched(off1)
-        hit = self.lru.get(("b", off1))
+        """(Q workspace, rowmap, n_rows, needs computing) of wave ``off1``: registered here, computed by the facet-side call"""
+        hit, rowmap, n_rows = self._lookup_Q(off1)
         if hit is not None:
-            return hit[0], hit[1], hit[0].shape[1], False
-        if self._plan is not None and int(off1) not in self._planned_keys:
-            raise ValueError(f"subgrid wave off1={off1} was not in the subgrid_configs plan")
-        rowmap, n_rows = self._wave_rows(off1)
+            return hit[0], rowmap, n_rows, False
         core = self.core
-        Q = torch.empty((len(self.facet_configs), n_rows, core.xM_yN_size), dtype=self.dtype, device=core.device)
+        Q = _torch().empty((len(self.facet_configs), n_rows, core.xM_yN_size), dtype=self.dtype, device=core.device)
         self.lru.set(("b", off1), (Q, rowmap))
         return Q, rowmap, n_rows, True
-    def _wave_b(self, sgs):
-        """One wave = two native calls: facet side (K2 + K3 + K4a) and subgrid side (K4b + K5).  (r3's grouped subgrid
-        side -- axis 0 finished first per off1 group, 79 -> 49 MB per subgrid at the same speed -- lives in
-        tools/experiments/ since r4.)  With a plan, K2 of the next planned wave is issued on the side stream before
-        this wave's subgrid side (_prefetch_wave)."""
-        torch = _torch()
-        core = self.core
-        self._check_planned(sgs)
+
+    def _facet_side(self, sgs, g_out=None, g_layout=None):
+        """Facet side of one wave (K2 + K3 + K4a) in one native call: the blocks ``G[F, S, m, m]`` (returned), or placed by
+        ``g_layout`` inside the flat buffer ``g_out`` (wave_blocks_into).  K2 of the next waves of the announced order
+        (set_wave_order; the plan's own order otherwise) goes to the side stream before this wave's K3 (_prefetch_wave), for
+        both callers (r6: the multi-GPU pass used to compute every K2 on the caller's stream, 41.4 against 35.5 ms at world 1)."""
+        core, off1 = self.core, sgs[0].off1
         bands = self.prepare_all_facets()
-        Q, rowmap, n_rows, compute = self._wave_Q(sgs[0].off1)
-        nxt = self._predict_next_waves(sgs[0].off1, _knobs()._PREFETCH_DEPTH)
+        Q, rowmap, n_rows, compute = self._wave_Q(off1)
+        nxt = self._predict_next_waves(off1, _knobs()._PREFETCH_DEPTH)
         if not compute:
             self._prefetch_waves(nxt)
-        m = core.xM_yN_size
-        G = torch.empty((len(self.facet_configs), len(sgs), m, m), dtype=self.dtype, device=core.device)
+        if g_out is None:
+            m = core.xM_yN_size
+            g_out = _torch().empty((len(self.facet_configs), len(sgs), m, m), dtype=self.dtype, device=core.device)
         band = self._band
         if compute:
-            bands, band = self._k2_source(sgs[0].off1)
+            bands, band = self._k2_source(off1)
         try:
-            core.wave_facet_side(bands, [cfg.off0 for cfg in self.facet_configs], band, sgs[0].off1, rowmap,
-                                 n_rows, Q, compute, [sg.off0 for sg in sgs], G)
+            core.wave_facet_side(bands, [cfg.off0 for cfg in self.facet_configs], band, off1, rowmap, n_rows, Q, compute,
+                                 [sg.off0 for sg in sgs], g_out, g_layout=g_layout)
         except Exception:
-            if compute:
-                self.lru._items.pop(("b", sgs[0].off1), None)  # pylint: disable=protected-access
+            if compute:  # Q was registered before it was computed: a later request must not find garbage
+                self.lru.discard(("b", off1))
             raise
         if compute:  # (this wave's own K2 was enqueued on the current stream just now: the next one goes behind it)
             self._prefetch_waves(nxt)
-        return _finish_from_G(core, G, self.facet_configs, sgs, placed=self._placed())
+        return g_out
+
+    def _wave_b(self, sgs):
+        """One wave = two native calls: facet side (K2 + K3 + K4a, _facet_side) and subgrid side (K4b + K5).  (r3's grouped
+        subgrid side -- axis 0 finished first per off1 group, 79 -> 49 MB per subgrid at the same speed -- lives in
+        tools/experiments/ since r4.)"""
+        self._check_planned(sgs)
+        return _finish_from_G(self.core, self._facet_side(sgs), self.facet_configs, sgs, placed=self._placed())
 
 
 def axis1_first_active(core, wave_axis, dtype):

@@ -4,11 +4,16 @@ plan will ask for next, enqueued on the core's side stream while the subgrid sid
 mix-in of :class:`SwiftlyForward`; the multi-GPU classes drive the same object through ``wave_blocks_into``
 (distributed.DistributedForward), so they get the same free-running K2 chain.
 
+Where the state lives: the walk of the caller over its plan in a :class:`WavePredictor` (pure Python), the K2s in flight
+in the attributes :class:`WavePrefetch` declares, and what holds for one set of band buffers (the bands-ready event, the
+chain flag) with the band buffers, in :class:`SwiftlyForward`.
+
 The knobs live in the ``api`` module namespace (``api._PREFETCH`` ...; the tests switch them at run time).
 """
 import logging
 import os
 import sys
+from functools import cached_property
 
 from .tasks import _torch
 
@@ -40,65 +45,91 @@ def _knobs():
     return sys.modules[__package__ + ".api"]
 
 
+class WavePredictor:
+    """The walk of a caller over its planned waves: positions are those of ``keys`` (the wave keys in order of first
+    appearance in the plan, or the order announced with :py:meth:`set_order`): a caller that walks its own plan forwards
+    or backwards is predicted whatever the numeric order of the keys; a repeated key keeps the direction of the walk."""
+
+    def __init__(self, keys):
+        self.order = list(dict.fromkeys(int(k) for k in keys))
+        self.pos = {k: i for i, k in enumerate(self.order)}
+        self.last, self.step = None, 1  # position of the last request, direction of the walk
+        self.off, self.missed, self.streak = False, 0, 0
+
+    def set_order(self, keys, planned):
+        """the order the caller announces; keys outside ``planned`` and repeats are dropped, the walk restarts"""
+        self.order = [k for k in dict.fromkeys(int(k) for k in keys) if k in planned]
+        self.pos = {k: i for i, k in enumerate(self.order)}
+        self.last, self.step = None, 1
+
+    def next(self, key, depth):
+        """the waves asked for after ``key``, nearest first, at most ``depth`` of them ([]: end / unknown key / off)"""
+        pos, last, order = self.pos.get(int(key)), self.last, self.order
+        if self.off:
+            # switched off after two mispredictions (miss): a caller that follows the order again for _REARM_AFTER
+            # requests gets the prefetch back (r5 advisor: the switch used to be for the life of the object)
+            follows = pos is not None and last is not None and pos - last == self.step
+            self.streak = self.streak + 1 if follows else 0
+            if pos is not None:
+                self.last = last = pos
+            if self.streak < _REARM_AFTER:
+                return []
+            self.off, self.missed, self.streak = False, 0, 0
+        if pos is None:
+            return []
+        if last is not None and pos != last:
+            # a jump from one end of the order to the other is the next PASS of the same walk (an object that is reused
+            # for several passes), not a turn: the direction is kept (r5 advisor)
+            wrapped = len(order) > 2 and {pos, last} == {0, len(order) - 1} and (pos == 0) == (self.step > 0)
+            if not wrapped:
+                self.step = 1 if pos > last else -1
+        self.last = pos
+        ahead = range(pos + self.step, pos + (int(depth) + 1) * self.step, self.step)
+        return [order[i] for i in ahead if 0 <= i < len(order)]
+
+    def hit(self):
+        """a prefetched wave was asked for: the walk follows the order"""
+        self.missed = 0
+
+    def miss(self):
+        """a wave other than the prefetched ones had to be computed; True when this miss (the second in a row) switched
+        the predictor off"""
+        self.missed += 1
+        if self.missed < 2 or self.off:
+            return False
+        self.off = True
+        return True
+
+
 class WavePrefetch:
-    """prediction + side-stream K2 of the next planned waves; state lives in the host object's ``__dict__``"""
+    """Side-stream K2 of the next planned waves: the in-flight side.  The host class provides ``_plan`` /
+    ``_planned_keys``, ``lru``, ``core``, ``_wave_rows`` / ``_k2_source`` / ``_axis1`` and the band-lifetime fields
+    ``_bands_ready`` / ``_side_waited`` / ``_k2_chain_forked``, which it resets when band buffers are installed."""
+
+    def __init__(self):
+        self._prefetched = {}  # K2s in flight: {off1: (Q, rowmap, done event)}
+        self._prefetch_parked = []  # mispredicted ones, kept referenced until their done events have fired
+        self.prefetch_issued = 0  # K2s enqueued on the side stream so far
+
+    @cached_property
+    def _predictor(self):
+        """the walk over the plan's waves (built on first use: one walk over the plan, none for objects that never predict)"""
+        return WavePredictor(sg.off1 for sg in self._plan)
 
     # -- planned-wave prefetch (r4): K2 of the NEXT planned wave(s) on the core's side stream ------------------------
     def _predict_next_waves(self, off1, depth):
         """the planned waves a caller that walks the plan asks for after ``off1``, nearest first, at most ``depth`` of
-        them ([]: no plan / end / prefetch off).  Positions are those of the PLAN (order of first appearance of the wave
-        keys in ``subgrid_configs``): a caller that walks its own plan forwards or backwards is predicted whatever the
-        numeric order of the keys; a repeated key keeps the direction of the walk."""
+        them ([]: no plan / end / prefetch off; :py:meth:`WavePredictor.next`)"""
         if self._plan is None or not _knobs()._PREFETCH:
             return []
-        if self.__dict__.get("_prefetch_off"):
-            # switched off after two mispredictions (_take_prefetched): a caller that follows the order again for
-            # _REARM_AFTER requests gets the prefetch back (r5 advisor: the switch used to be for the life of the object)
-            pos, last = self.__dict__.get("_wave_pos", {}).get(int(off1)), self.__dict__.get("_last_wave_pos")
-            follows = pos is not None and last is not None and pos - last == self.__dict__.get("_wave_step", 1)
-            streak = self.__dict__["_prefetch_streak"] = (self.__dict__.get("_prefetch_streak", 0) + 1) if follows else 0
-            if pos is not None:
-                self.__dict__["_last_wave_pos"] = pos
-            if streak < _REARM_AFTER:
-                return []
-            self.__dict__["_prefetch_off"] = False
-            self.__dict__["_prefetch_missed"] = 0
-            self.__dict__["_prefetch_streak"] = 0
-        order = self.__dict__.get("_wave_order")
-        if order is None:
-            order = self.__dict__["_wave_order"] = list(dict.fromkeys(int(sg.off1) for sg in self._plan))
-            self.__dict__["_wave_pos"] = {k: i for i, k in enumerate(order)}
-        pos = self._wave_pos.get(int(off1))
-        if pos is None:
-            return []
-        last = self.__dict__.get("_last_wave_pos")
-        step = self.__dict__.get("_wave_step", 1)
-        if last is not None and pos != last:
-            # a jump from one end of the order to the other is the next PASS of the same walk (an object that is reused
-            # for several passes), not a turn: the direction is kept (r5 advisor)
-            wrapped = len(order) > 2 and {pos, last} == {0, len(order) - 1} and (pos == 0) == (step > 0)
-            if not wrapped:
-                step = 1 if pos > last else -1
-        self.__dict__["_last_wave_pos"] = pos
-        self.__dict__["_wave_step"] = step
-        out = []
-        for d in range(1, int(depth) + 1):
-            nxt = pos + d * step
-            if not 0 <= nxt < len(order):
-                break
-            out.append(order[nxt])
-        return out
+        return self._predictor.next(off1, depth)
 
     def set_wave_order(self, keys):
         """Tell the predictor the order in which the caller will ask for the planned waves (wave keys = ``off1``), when
         it is not the order of first appearance in ``subgrid_configs`` -- e.g. the group order of the multi-GPU pass
         (distributed.DistributedForward).  Keys outside the plan are ignored; the walk restarts."""
-        planned = getattr(self, "_planned_keys", None)
-        order = [int(k) for k in dict.fromkeys(int(k) for k in keys) if planned is None or int(k) in planned]
-        self.__dict__["_wave_order"] = order
-        self.__dict__["_wave_pos"] = {k: i for i, k in enumerate(order)}
-        self.__dict__.pop("_last_wave_pos", None)
-        self.__dict__["_wave_step"] = 1
+        if self._plan is not None:
+            self._predictor.set_order(keys, self._planned_keys)
 
     def _predict_next_wave(self, off1):
         """the nearest of :py:meth:`_predict_next_waves` (None: nothing to predict)"""
@@ -110,7 +141,7 @@ class WavePrefetch:
         wave that is neither prefetched nor cached has to be computed, the prefetched ones were mispredictions: their
         buffers are dropped, and after two such misses the prefetch is switched off for this object (a wasted K2 per
         wave costs more than the overlap gains)."""
-        pending = self.__dict__.get("_prefetched")
+        pending = self._prefetched
         if not pending:
             return
         pf = pending.pop(int(off1), None)
@@ -118,17 +149,15 @@ class WavePrefetch:
             if self.lru.get(("b", off1)) is None:  # a different wave has to be computed: the guess was wrong
                 # the K2 kernels of the dropped waves may still be running (they read the band buffers and write these Q
                 # blocks): keep the blocks referenced until their `done` events have fired
-                parked = self.__dict__.setdefault("_prefetch_parked", [])
+                parked = self._prefetch_parked
                 parked[:] = [p for p in parked if p[2] is not None and not p[2].query()]
                 parked.extend(pending.values())
                 pending.clear()
-                missed = self.__dict__["_prefetch_missed"] = self.__dict__.get("_prefetch_missed", 0) + 1
-                if missed >= 2 and not self.__dict__.get("_prefetch_off"):
-                    self.__dict__["_prefetch_off"] = True
+                if self._predictor.miss():
                     log.info("SwiftlyForward: two mispredicted waves in a row -- planned-wave prefetch switched off "
                              "until %d requests have followed the plan again", _REARM_AFTER)
             return
-        self.__dict__["_prefetch_missed"] = 0  # the walk follows the plan
+        self._predictor.hit()  # the walk follows the plan
         if self.lru.get(("b", off1)) is None:
             cur = _torch().cuda.current_stream(self.core.device)
             cur.wait_event(pf[2])
@@ -151,16 +180,16 @@ class WavePrefetch:
         written while the caller's stream still reads it."""
         torch = _torch()
         core = self.core
-        pending = self.__dict__.setdefault("_prefetched", {})
+        pending = self._prefetched
         if off1 is None or int(off1) in pending or self.lru.get(("b", off1)) is not None:
             return
         rowmap, n_rows = self._wave_rows(off1)
         side = core.side_stream()
-        ready = self.__dict__.get("_bands_ready")
+        ready = self._bands_ready
         if _knobs()._PREFETCH_DEPTH >= 2 and ready is not None:
-            if self.__dict__.get("_side_waited") is not ready:  # once per pass: the side stream is in order behind it
+            if self._side_waited is not ready:  # once per pass: the side stream is in order behind it
                 side.wait_event(ready)  # K1 of every facet (recorded by _prepare_all_bands)
-                self.__dict__["_side_waited"] = ready
+                self._side_waited = ready
         else:
             ev = torch.cuda.Event()
             # bands ready; every reader of a Q buffer that the allocator may hand out again has been enqueued
@@ -172,7 +201,7 @@ class WavePrefetch:
         # (axis-1-first pipeline with a row pass per wave: K2 reads rows that finish_axis1_rows has just written on the side
         # stream -- its chunk streams must fork behind them every time)
         chain = (_knobs()._PREFETCH_DEPTH >= 2 and ready is not None and _knobs()._CHAIN_K2
-                 and self.__dict__.get("_k2_chain_forked", False) and self._axis1() != 1)
+                 and self._k2_chain_forked and self._axis1() != 1)
         with torch.cuda.stream(side):
             Q = torch.empty((len(self.facet_configs), n_rows, core.xM_yN_size), dtype=self.dtype, device=core.device)
             src, band = self._k2_source(off1)
@@ -185,12 +214,13 @@ class WavePrefetch:
                 core.chain_chunk_streams(False)
             done = torch.cuda.Event()
             done.record(side)
-        self.__dict__["_k2_chain_forked"] = True
+        self._k2_chain_forked = True
         pending[int(off1)] = (Q, rowmap, done)
+        self.prefetch_issued += 1
 
     def _prefetch_waves(self, waves):
         """:py:meth:`_prefetch_wave` for the predicted waves, nearest first, at most SWIFTLY_PREFETCH_DEPTH in flight"""
         for off1 in waves:
-            if len(self.__dict__.get("_prefetched") or ()) >= _knobs()._PREFETCH_DEPTH:
+            if len(self._prefetched) >= _knobs()._PREFETCH_DEPTH:
                 break
             self._prefetch_wave(off1)

@@ -11,7 +11,8 @@ log = logging.getLogger("fourier-logger")
 class LRUCache:
     """Least-recently-used cache with the interface of reference
     api.py:525-590: ``get`` refreshes, ``set`` returns the evicted
-    ``(key, value)`` or ``(None, None)``, ``pop_all`` drains oldest first."""
+    ``(key, value)`` or ``(None, None)``, ``pop_all`` drains oldest first.  ``discard`` (extension) takes back a
+    registration."""
 
     def __init__(self, cache_size):
         self.cache_size = cache_size
@@ -33,6 +34,10 @@ class LRUCache:
             return None, None
         old_key = next(iter(self._items))
         return old_key, self._items.pop(old_key)
+
+    def discard(self, key):
+        """remove ``key`` if present; the recency of the other entries is unchanged"""
+        self._items.pop(key, None)
 
     def pop_all(self):
         """yield and remove all entries, least recently used first"""

@@ -339,7 +339,7 @@ def test_forward_planned_wave_prefetch_is_bit_identical(order):
         try:
             fwd = sw.SwiftlyForward(cfg, list(zip(facet_cfgs, facets)), subgrid_configs=sg_cfgs, wave_axis=1)
             out = {k: fwd.get_wave(waves[k]).cpu().numpy() for k in keys}
-            used = fwd.__dict__.get("_prefetched", "never") != "never"
+            used = fwd.prefetch_issued > 0
         finally:
             sw.api._PREFETCH = old
         torch.cuda.synchronize()
@@ -587,7 +587,7 @@ def test_chained_k2_with_a_trailing_unchunked_facet_group():
         try:
             fwd = sw.SwiftlyForward(cfg, list(zip(facet_cfgs, facets)), subgrid_configs=plan, wave_axis=1)
             out = [fwd.get_wave(waves[k]).cpu().numpy() for k in sorted(waves)]
-            used = fwd.__dict__.get("_prefetched", "never") != "never"
+            used = fwd.prefetch_issued > 0
         finally:
             sw.api._PREFETCH = old
         torch.cuda.synchronize()

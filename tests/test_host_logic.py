@@ -7,7 +7,7 @@ import numpy
 import pytest
 
 from oracle import swiftly_oracle as orc
-from ska_sdp_exec_swiftly_amd import api, api_helper
+from ska_sdp_exec_swiftly_amd import api, api_helper, prefetch
 from ska_sdp_exec_swiftly_amd.core_hip import calculate_pswf
 from ska_sdp_exec_swiftly_amd.swift_configs import SWIFT_CONFIGS
 
@@ -66,6 +66,21 @@ def test_lru_cache_semantics():
     assert lru.set("a", 10) == (None, None)  # update in place
     assert list(lru.pop_all()) == [("c", 3), ("a", 10)]
     assert list(lru.pop_all()) == []
+
+
+def test_lru_cache_discard():
+    """LRUCache.discard takes back a registration: a present key is removed, an absent key is a no-op, and the recency of
+    the other entries is unchanged."""
+    lru = api.LRUCache(3)
+    for k in "abc":
+        lru.set(k, k.upper())
+    lru.get("a")  # recency now b, c, a
+    lru.discard("c")
+    assert lru.get("c") is None
+    lru.discard("never there")
+    assert lru.set("d", "D") == (None, None)  # the discarded entry made room
+    assert lru.set("e", "E") == ("b", "B")  # and b is still the oldest
+    assert list(lru.pop_all()) == [("a", "A"), ("d", "D"), ("e", "E")]
 
 
 def test_unknown_backend():
@@ -242,14 +257,21 @@ def test_band_range_and_row_sources_for_a_padded_facet_of_3_times_2_to_the_k():
     numpy.testing.assert_array_equal(got, want)
 
 
+def _bare_forward(keys):
+    """a SwiftlyForward with nothing but the plan bookkeeping and the declared prefetch state (no device, no core)"""
+    fwd = object.__new__(api.SwiftlyForward)
+    prefetch.WavePrefetch.__init__(fwd)
+    fwd._plan = None if keys is None else [api.SubgridConfig(0, k, 8) for k in keys]
+    fwd._planned_keys = None if keys is None else set(keys)
+    return fwd
+
+
 def test_planned_wave_prediction_follows_the_walk_direction():
     """SwiftlyForward._predict_next_wave (host logic of the planned-wave prefetch): the successor IN PLAN ORDER (first
     appearance of the wave keys in subgrid_configs) of the wave being served, the predecessor once the caller walks
     the plan backwards, the same direction after a repeated key, nothing at either end, for an unplanned key, without
     a plan or with the prefetch switched off."""
-    fwd = object.__new__(api.SwiftlyForward)  # the predictor only reads the plan bookkeeping
-    fwd._plan = [api.SubgridConfig(0, k, 8) for k in (30, 10, 20, 10, 40)]  # plan order of the keys: 30, 10, 20, 40
-    fwd._planned_keys = {10, 20, 30, 40}
+    fwd = _bare_forward((30, 10, 20, 10, 40))  # the predictor only reads the plan; plan order of the keys: 30, 10, 20, 40
     assert fwd._predict_next_wave(30) == 10
     assert fwd._predict_next_wave(10) == 20
     assert fwd._predict_next_wave(10) == 20        # the same wave again (a partial request): direction kept
@@ -260,8 +282,7 @@ def test_planned_wave_prediction_follows_the_walk_direction():
     assert fwd._predict_next_wave(30) is None      # start of the plan, walking backwards
     assert fwd._predict_next_wave(10) == 20        # forwards again
     assert fwd._predict_next_wave(25) is None      # not a planned wave
-    off = object.__new__(api.SwiftlyForward)
-    off._plan = None
+    off = _bare_forward(None)
     assert off._predict_next_wave(10) is None
     old = api._PREFETCH
     api._PREFETCH = False
@@ -275,37 +296,33 @@ def test_mispredicted_prefetch_is_dropped_and_switches_the_prefetch_off():
     """SwiftlyForward._take_prefetched: a prefetched wave that is not the one asked for (and the one asked for is not
     cached) is a misprediction -- the buffer is dropped (parked until its K2 has finished); after two of them IN A ROW the
     predictor stops predicting, and a caller that follows the plan again for a few requests gets it back (r6)."""
-    fwd = object.__new__(api.SwiftlyForward)
-    fwd._plan = [api.SubgridConfig(0, k, 8) for k in (10, 20, 30, 40, 50, 60, 70)]
-    fwd._planned_keys = {10, 20, 30, 40, 50, 60, 70}
+    fwd = _bare_forward((10, 20, 30, 40, 50, 60, 70))
     fwd.lru = api.LRUCache(1)
-    fwd.__dict__["_prefetched"] = {20: ("Q20", None, None)}
+    fwd._prefetched = {20: ("Q20", None, None)}
     fwd._take_prefetched(40)                       # asked for 40, 20 was prefetched
-    assert not fwd.__dict__["_prefetched"] and fwd.__dict__["_prefetch_missed"] == 1
-    assert fwd.__dict__["_prefetch_parked"] == [("Q20", None, None)]
+    assert not fwd._prefetched and fwd._predictor.missed == 1
+    assert fwd._prefetch_parked == [("Q20", None, None)]
     assert fwd._predict_next_wave(10) == 20        # one miss: still predicting
-    fwd.__dict__["_prefetched"] = {20: ("Q20", None, None), 30: ("Q30", None, None)}
+    fwd._prefetched = {20: ("Q20", None, None), 30: ("Q30", None, None)}
     fwd.lru.set(("b", 30), ("Q30", None))
     fwd._take_prefetched(30)                       # a hit: the other prefetched wave stays, the miss count starts again
-    assert list(fwd.__dict__["_prefetched"]) == [20] and fwd.__dict__["_prefetch_missed"] == 0
+    assert list(fwd._prefetched) == [20] and fwd._predictor.missed == 0
     fwd._take_prefetched(40)
-    assert fwd.__dict__["_prefetch_missed"] == 1 and not fwd.__dict__.get("_prefetch_off")
-    fwd.__dict__["_prefetched"] = {20: ("Q20", None, None)}
+    assert fwd._predictor.missed == 1 and not fwd._predictor.off
+    fwd._prefetched = {20: ("Q20", None, None)}
     fwd._take_prefetched(50)
-    assert fwd.__dict__.get("_prefetch_off") and fwd._predict_next_wave(10) is None
+    assert fwd._predictor.off and fwd._predict_next_wave(10) is None
     # four requests in plan order switch it on again
     assert [fwd._predict_next_wave(k) for k in (20, 30, 40)] == [None, None, None]
-    assert fwd._predict_next_wave(50) == 60 and not fwd.__dict__["_prefetch_off"]
+    assert fwd._predict_next_wave(50) == 60 and not fwd._predictor.off
 
 
 def test_announced_wave_order_and_the_next_pass_of_a_reused_object():
     """set_wave_order: the predictor follows the order the caller announces (the multi-GPU pass packs its waves group
     by group); a jump from the last wave of the order back to the first is the next pass of the same walk, not a turn."""
-    fwd = object.__new__(api.SwiftlyForward)
-    fwd._plan = [api.SubgridConfig(0, k, 8) for k in (10, 20, 30, 40)]
-    fwd._planned_keys = {10, 20, 30, 40}
+    fwd = _bare_forward((10, 20, 30, 40))
     fwd.set_wave_order([30, 10, 99, 40, 20, 10])   # 99 is not planned, the second 10 is a repeat
-    assert fwd._wave_order == [30, 10, 40, 20]
+    assert fwd._predictor.order == [30, 10, 40, 20]
     assert fwd._predict_next_waves(30, 2) == [10, 40]
     assert fwd._predict_next_waves(10, 2) == [40, 20]
     assert fwd._predict_next_waves(20, 2) == []
@@ -316,15 +333,27 @@ def test_announced_wave_order_and_the_next_pass_of_a_reused_object():
 def test_planned_wave_prediction_depth():
     """SwiftlyForward._predict_next_waves: up to `depth` waves ahead in the walk direction, nearest first, cut at the
     ends of the plan (the r5 free-running K2 chain, SWIFTLY_PREFETCH_DEPTH)."""
-    fwd = object.__new__(api.SwiftlyForward)
-    fwd._plan = [api.SubgridConfig(0, k, 8) for k in (10, 20, 30, 40, 50)]
-    fwd._planned_keys = {10, 20, 30, 40, 50}
+    fwd = _bare_forward((10, 20, 30, 40, 50))
     assert fwd._predict_next_waves(10, 2) == [20, 30]
     assert fwd._predict_next_waves(30, 3) == [40, 50]
     assert fwd._predict_next_waves(50, 2) == []
     assert fwd._predict_next_waves(40, 2) == [30, 20]   # turned round
     assert fwd._predict_next_waves(20, 2) == [10]
     assert fwd._predict_next_waves(15, 2) == []          # not a planned wave
+
+
+def test_wave_predictor_reports_the_miss_that_switches_it_off():
+    """WavePredictor on its own, what the tests through SwiftlyForward do not see: only the second miss in a row reports
+    the switch-off (one log line), a hit in between starts the count again, and announcing an order leaves the switch alone."""
+    p = prefetch.WavePredictor([10, 20, 10, 30])
+    assert p.order == [10, 20, 30]
+    assert [p.miss(), p.miss(), p.miss()] == [False, True, False] and p.off
+    q = prefetch.WavePredictor([10, 20, 30])
+    assert not q.miss()
+    q.hit()
+    assert not q.miss() and q.miss() and q.next(10, 2) == []
+    q.set_order([30, 7, 30, 10], {10, 20, 30})
+    assert q.order == [30, 10] and q.off  # an announced order restarts the walk, it does not switch the predictor on
 
 
 def test_backward_wave_entry_points_check_the_wave_key():
