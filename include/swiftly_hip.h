@@ -540,6 +540,53 @@ int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, i
                                   int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
                                   int64_t facet_off, int64_t facet_size, const void* mask, void* stream);
 
+/* -- point-source truths and RMSE checks on the device (handle-free; work is enqueued on `stream` of the current device).
+ *    The reference checks itself with point sources: it builds facets with make_facet, and compares every subgrid with
+ *    the direct Fourier sum of the sources and every finished facet with the scattered sources
+ *    (fourier_algorithm.py:218-315, api_helper.py:15-70).  These entry points evaluate those truths natively, in float64
+ *    arithmetic whatever `dtype` (of out / approx: SWIFTLY_C64 is rounded once on store, widened exactly on load).
+ *    sources: device table of n_sources records { double re, im; int32_t c0, c1; } (24 bytes): complex intensity and
+ *    the integer image coordinates relative to the image centre, reduced into [-image_size/2, image_size/2), no two
+ *    records on one pixel (the caller merges them).  image_size <= 2^31.  n_sources = 0 is allowed (zeros).
+ *    The subgrid phases exp(2 pi i c u / N) are evaluated from (c * u) mod N taken in 64-bit integers: the double
+ *    formula of the reference carries a phase error that grows with c * u / N.
+ *    Errors: SWIFTLY_ERR_PARAM for non-positive sizes, image_size > 2^31, a null pointer where one is needed, an
+ *    unknown dtype.
+ *
+ * subgrids_from_sources: make_subgrid_from_sources (fourier_algorithm.py:267-315) / make_subgrid (api_helper.py:15-24)
+ *   for n_subgrids subgrids of one `size` in ONE launch:
+ *     out[b][i0, i1] = mask0s[b][i0] * mask1s[b][i1] * image_size^-2 *
+ *                      sum_s I_s exp(2 pi i (c0_s (off0s[b] - size/2 + i0) + c1_s (off1s[b] - size/2 + i1)) / image_size)
+ *   off0s / off1s: HOST arrays [n_subgrids]; mask0s / mask1s: device double [n_subgrids][size] or NULL (ones);
+ *   out[b] at out + b * out_sub_stride, rows out_row_stride apart (complex elements), columns contiguous.
+ * check_subgrids_from_sources: check_subgrid (api_helper.py:58-70) without storing the truth:
+ *     result[b] = { sum |truth_b - approx_b|^2, sum |truth_b|^2 }   (device double [n_subgrids][2]);
+ *   RMSE = sqrt(result[b][0]) / size.  Summed in a fixed order: bit-reproducible from run to run.
+ * facet_from_sources: make_facet_from_sources (fourier_algorithm.py:218-264) / make_facet (api_helper.py:27-36): out is
+ *   zeroed, then I_s * mask0[p0] * mask1[p1] stored at pixel p = (c_s - (off - size/2)) mod image_size of every
+ *   source with p0, p1 < size.  mask0 / mask1: device double [size] or NULL.
+ * check_facet_from_sources: check_facet (api_helper.py:39-48): result = { sum |truth - approx|^2, sum |truth|^2 }
+ *   (device double [2]), every pixel of the facet differenced on its own.  The sources of facet row r are
+ *   row_sources[row_start[r] .. row_start[r + 1]) (device int32; indices into the table, ascending in their facet column;
+ *   row_start has size + 1 entries), built by the caller for these offsets. */
+int swiftly_hip_subgrids_from_sources(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
+                                      int64_t size, const int64_t* off0s, const int64_t* off1s, int64_t n_subgrids,
+                                      const double* mask0s, const double* mask1s, void* out, int64_t out_sub_stride,
+                                      int64_t out_row_stride, void* stream);
+int swiftly_hip_check_subgrids_from_sources(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
+                                            int64_t size, const int64_t* off0s, const int64_t* off1s,
+                                            int64_t n_subgrids, const double* mask0s, const double* mask1s,
+                                            const void* approx, int64_t approx_sub_stride, int64_t approx_row_stride,
+                                            double* result, void* stream);
+int swiftly_hip_facet_from_sources(int dtype, const void* sources, int64_t n_sources, int64_t image_size, int64_t size,
+                                   int64_t off0, int64_t off1, const double* mask0, const double* mask1, void* out,
+                                   int64_t out_row_stride, void* stream);
+int swiftly_hip_check_facet_from_sources(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
+                                         int64_t size, int64_t off0, int64_t off1, const double* mask0,
+                                         const double* mask1, const void* approx, int64_t approx_row_stride,
+                                         const int32_t* row_start, const int32_t* row_sources, double* result,
+                                         void* stream);
+
 /* -- device memory helpers for callers that do not bring their own allocator
  *    (the Python mirror uses torch for device memory and never calls these) -- */
 int swiftly_hip_malloc(void** ptr, size_t bytes);

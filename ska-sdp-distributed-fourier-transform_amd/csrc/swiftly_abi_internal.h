@@ -1,7 +1,7 @@
 // Internals shared by the translation units of the C ABI (swiftly_abi.hip: handles + the eight primitives and their
 // batch forms; swiftly_abi_coltransform.hip: the strided-axis transform, col_transform; swiftly_abi_pipeline.hip: the
 // fused / per-wave entry points of the streaming classes; swiftly_abi_util.hip: device memory, stream and diagnostic
-// helpers).  Not installed: include/swiftly_hip.h is the public header.
+// helpers; swiftly_abi_sources.hip: point-source truths and RMSE checks).  Not installed: include/swiftly_hip.h is the public header.
 #pragma once
 
 #include <algorithm>

@@ -25,9 +25,11 @@ from .api_helper import (
     make_subgrid_from_sources,
 )
 from .core_hip import SwiftlyCoreHip, calculate_pswf
+from .device_sources import DeviceSources
 from .swift_configs import SWIFT_CONFIGS
 
 __all__ = [
+    "DeviceSources",
     "DeviceTask",
     "FacetConfig",
     "SubgridConfig",

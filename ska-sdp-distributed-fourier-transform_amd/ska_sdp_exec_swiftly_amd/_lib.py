@@ -151,6 +151,19 @@ def _declare(lib):
     lib.swiftly_hip_band_zero_untouched.argtypes = [vp, c_int, vp, i64, i64, i64, vp, vp]
     lib.swiftly_hip_finish_facet_band.restype = c_int
     lib.swiftly_hip_finish_facet_band.argtypes = [vp, c_int, vp, i64, i64, i64, i64, vp, i64, i64, i64, vp, vp]
+    # point-source truths (handle-free): (dtype, sources, n_sources, image_size, size, ...
+    src = [c_int, vp, i64, i64, i64]
+    for name, args in [
+        # ... off0s, off1s, n_subgrids, mask0s, mask1s, out / approx, sub_stride, row_stride, [result,] stream)
+        ("subgrids_from_sources", src + [pi64, pi64, i64, vp, vp, vp, i64, i64, vp]),
+        ("check_subgrids_from_sources", src + [pi64, pi64, i64, vp, vp, vp, i64, i64, vp, vp]),
+        # ... off0, off1, mask0, mask1, out / approx, row_stride, [row_start, row_sources, result,] stream)
+        ("facet_from_sources", src + [i64, i64, vp, vp, vp, i64, vp]),
+        ("check_facet_from_sources", src + [i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
+    ]:
+        fn = getattr(lib, "swiftly_hip_" + name)
+        fn.restype = c_int
+        fn.argtypes = args
     lib.swiftly_hip_malloc.restype = c_int
     lib.swiftly_hip_malloc.argtypes = [POINTER(vp), c_size_t]
     lib.swiftly_hip_free.restype = c_int

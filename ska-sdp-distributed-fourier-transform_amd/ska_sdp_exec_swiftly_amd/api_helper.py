@@ -4,7 +4,8 @@ Host-side helpers with the names and semantics of the reference's
 rely on: synthetic facet / subgrid generation from point sources, and RMSE
 checks (reference api_helper.py:15-70, fourier_algorithm.py:218-315).
 These run on the CPU with numpy -- they produce test *inputs* and *truths*,
-they are not part of the accelerated path.
+they are not part of the accelerated path.  ``device_sources.DeviceSources``
+evaluates the same truths and checks with native kernels on device arrays.
 """
 import numpy
 
