@@ -606,6 +606,10 @@ int swiftly_hip_stream_create_cu_mask(void** stream, const uint32_t* cu_mask, in
 int swiftly_hip_stream_destroy(void* stream);
 int swiftly_hip_cu_census(int32_t* out, int nblocks, void* stream);
 
+/* -- the kernels launched with dynamic LDS: how many instances the library registered when it was loaded (their
+ *    per-device attribute is set by swiftly_hip_create) and the largest LDS size in bytes among them.  No device needed. */
+int swiftly_hip_kernel_table(int64_t* count, int64_t* max_lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

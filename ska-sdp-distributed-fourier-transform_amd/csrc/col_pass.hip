@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "swiftly_colpass.h"
+#include "swiftly_launch.h"
 
 namespace swf {
 
@@ -24,9 +25,9 @@ static int launch_mode(const ColPassArgs& a, const ColZ& cz, int outer, int nbat
         if (a.tile32 && !a.gs && col512_tile32()) {
             using GH = CGeo512Half;
             dim3 hgrid((unsigned)((a.ncols + GH::COLS - 1) / GH::COLS), (unsigned)outer, (unsigned)nbatch);
-            hipLaunchKernelGGL((col_pass_kernel<GH, 2, true>), hgrid, dim3(GH::NT), GH::LDS_BYTES, s, a, a.in, a.out, a.ld_win,
-                               a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.tw, a.tw_full, cz);
-            return (int)hipGetLastError();
+            return launch_lds<col_pass_kernel<GH, 2, true>, GH::LDS_BYTES>(hgrid, dim3(GH::NT), s, a, a.in, a.out, a.ld_win,
+                                                                           a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.tw,
+                                                                           a.tw_full, cz);
         }
     }
     dim3 grid((unsigned)((a.ncols + G::COLS - 1) / G::COLS), (unsigned)outer, (unsigned)nbatch);
@@ -35,18 +36,16 @@ static int launch_mode(const ColPassArgs& a, const ColZ& cz, int outer, int nbat
     }
     if constexpr (MODE != 1 && !G::HALF) {
         if (a.gs) {  // gather-sum load (backward pass); the source contributions are small and re-read: cacheable
-            hipLaunchKernelGGL((col_pass_kernel<G, MODE, true, true>), grid, dim3(G::NT), G::LDS_BYTES, s, a, a.in, a.out,
-                               a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.tw, a.tw_full, cz);
-            return (int)hipGetLastError();
+            return launch_lds<col_pass_kernel<G, MODE, true, true>, G::LDS_BYTES>(grid, dim3(G::NT), s, a, a.in, a.out, a.ld_win,
+                                                                                  a.ld_win2, a.st_win, a.st_win2, a.st_rowmap,
+                                                                                  a.tw, a.tw_full, cz);
         }
     }
     if (MODE == 2 || a.scratch_nt)
-        hipLaunchKernelGGL((col_pass_kernel<G, MODE, true>), grid, dim3(G::NT), G::LDS_BYTES, s, a, a.in, a.out, a.ld_win,
-                           a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.tw, a.tw_full, cz);
-    else
-        hipLaunchKernelGGL((col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false>), grid, dim3(G::NT), G::LDS_BYTES, s, a, a.in,
-                           a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.tw, a.tw_full, cz);
-    return (int)hipGetLastError();
+        return launch_lds<col_pass_kernel<G, MODE, true>, G::LDS_BYTES>(grid, dim3(G::NT), s, a, a.in, a.out, a.ld_win, a.ld_win2,
+                                                                        a.st_win, a.st_win2, a.st_rowmap, a.tw, a.tw_full, cz);
+    return launch_lds<col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false>, G::LDS_BYTES>(
+        grid, dim3(G::NT), s, a, a.in, a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.tw, a.tw_full, cz);
 }
 // float64 arithmetic (ColPassArgs::f64): lengths 32 .. 512
 constexpr int kColF64MinLog = 5;
@@ -61,43 +60,19 @@ static int launch_mode_f64(const ColPassArgs& a, const ColZ& cz, int outer, int 
             using GG = typename CGeoFor<LOGN, double>::type_gs;
             if constexpr (MODE != 1 && !GG::HALF) {
                 dim3 ggrid((unsigned)((a.ncols + GG::COLS - 1) / GG::COLS), (unsigned)outer, (unsigned)nbatch);
-                hipLaunchKernelGGL((col_pass_kernel<GG, MODE, true, true, double>), ggrid, dim3(GG::NT), GG::LDS_BYTES, s, a, a.in,
-                                   a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
-                return (int)hipGetLastError();
+                return launch_lds<col_pass_kernel<GG, MODE, true, true, double>, GG::LDS_BYTES>(
+                    ggrid, dim3(GG::NT), s, a, a.in, a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd,
+                    a.twd_full, cz);
             } else {
                 return (int)hipErrorInvalidConfiguration;
             }
         }
         dim3 grid((unsigned)((a.ncols + G::COLS - 1) / G::COLS), (unsigned)outer, (unsigned)nbatch);
         if (MODE == 2 || a.scratch_nt)
-            hipLaunchKernelGGL((col_pass_kernel<G, MODE, true, false, double>), grid, dim3(G::NT), G::LDS_BYTES, s, a, a.in,
-                               a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
-        else
-            hipLaunchKernelGGL((col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double>), grid, dim3(G::NT),
-                               G::LDS_BYTES, s, a, a.in, a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd,
-                               a.twd_full, cz);
-        return (int)hipGetLastError();
-    }
-}
-template <int LOGN, int MODE>
-static int init_mode_f64() {
-    if constexpr (LOGN < kColF64MinLog || LOGN > kColPassMaxLogF64) {
-        return 0;
-    } else {
-        using G = typename CGeoFor<LOGN, double>::type;
-        int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<G, MODE, true, false, double>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-        if (!rc && MODE != 2)
-            rc = (int)hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-        using GG = typename CGeoFor<LOGN, double>::type_gs;
-        if constexpr (MODE != 1 && !GG::HALF) {
-            if (!rc)
-                rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<GG, MODE, true, true, double>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)GG::LDS_BYTES);
-        }
-        return rc;
+            return launch_lds<col_pass_kernel<G, MODE, true, false, double>, G::LDS_BYTES>(
+                grid, dim3(G::NT), s, a, a.in, a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
+        return launch_lds<col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double>, G::LDS_BYTES>(
+            grid, dim3(G::NT), s, a, a.in, a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
     }
 }
 
@@ -128,41 +103,17 @@ static int launch_mode_c128(const ColPassArgs& a, const ColZ& cz, int outer, int
         dim3 grid((unsigned)((a.ncols + G::COLS - 1) / G::COLS), (unsigned)outer, (unsigned)nbatch);
         if (a.gs) {  // never fall through to the plain load, which would read the encoded table as a row map
             if constexpr (kColC128HasGs<LOGN, MODE>) {
-                hipLaunchKernelGGL((col_pass_kernel<G, MODE, true, true, double, double>), grid, dim3(G::NT), G::LDS_BYTES, s,
-                                   a, in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
-                return (int)hipGetLastError();
+                return launch_lds<col_pass_kernel<G, MODE, true, true, double, double>, G::LDS_BYTES>(
+                    grid, dim3(G::NT), s, a, in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
             } else {
                 return (int)hipErrorInvalidConfiguration;
             }
         }
         if (MODE == 2 || a.scratch_nt)
-            hipLaunchKernelGGL((col_pass_kernel<G, MODE, true, false, double, double>), grid, dim3(G::NT), G::LDS_BYTES, s, a,
-                               in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
-        else
-            hipLaunchKernelGGL((col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double, double>), grid, dim3(G::NT),
-                               G::LDS_BYTES, s, a, in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd,
-                               a.twd_full, cz);
-        return (int)hipGetLastError();
-    }
-}
-template <int LOGN, int MODE>
-static int init_mode_c128() {
-    if constexpr (LOGN < kColF64MinLog || LOGN > kColPassMaxLogF64) {
-        return 0;
-    } else {
-        using G = CGeoC128<LOGN>;
-        int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<G, MODE, true, false, double, double>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-        if (!rc && MODE != 2)
-            rc = (int)hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double, double>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-        if constexpr (kColC128HasGs<LOGN, MODE>) {
-            if (!rc)
-                rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<G, MODE, true, true, double, double>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-        }
-        return rc;
+            return launch_lds<col_pass_kernel<G, MODE, true, false, double, double>, G::LDS_BYTES>(
+                grid, dim3(G::NT), s, a, in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
+        return launch_lds<col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false, false, double, double>, G::LDS_BYTES>(
+            grid, dim3(G::NT), s, a, in, out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.twd, a.twd_full, cz);
     }
 }
 
@@ -182,35 +133,6 @@ static int launch_one(int mode, const ColPassArgs& a, const ColZ& cz, int outer,
     if (mode == 1) return launch_mode<LOGN, 1>(a, cz, outer, nbatch, s);
     return launch_mode<LOGN, 2>(a, cz, outer, nbatch, s);
 }
-template <int LOGN, int MODE>
-static int init_mode() {
-    using G = typename CGeoFor<LOGN>::type;
-    if (G::LDS_BYTES == 0) return 0;
-    int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<G, MODE, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-    if (!rc && MODE != 2)
-        rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-    if constexpr (MODE != 1 && !G::HALF) {
-        if (!rc)
-            rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<G, MODE, true, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-    }
-    return rc;
-}
-template <int LOGN>
-static int init_one() {
-    int rc = init_mode<LOGN, 0>();
-    if (!rc) rc = init_mode<LOGN, 1>();
-    if (!rc) rc = init_mode<LOGN, 2>();
-    if (!rc) rc = init_mode_f64<LOGN, 0>();
-    if (!rc) rc = init_mode_f64<LOGN, 1>();
-    if (!rc) rc = init_mode_f64<LOGN, 2>();
-    if (!rc) rc = init_mode_c128<LOGN, 0>();
-    if (!rc) rc = init_mode_c128<LOGN, 1>();
-    if (!rc) rc = init_mode_c128<LOGN, 2>();
-    return rc;
-}
 
 template <int LO, int HI>
 struct CDispatch {
@@ -219,22 +141,10 @@ struct CDispatch {
         if constexpr (LO < HI) return CDispatch<LO + 1, HI>::launch(logn, mode, a, cz, outer, nbatch, s);
         return -1;
     }
-    static int init() {
-        int rc = init_one<LO>();
-        if (rc) return rc;
-        if constexpr (LO < HI) return CDispatch<LO + 1, HI>::init();
-        return 0;
-    }
 };
 
 int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
     return CDispatch<kColPassMinLog, kColPassMaxLog>::launch(logn, mode, a, cz, outer, nbatch, s);
-}
-int init_col_pass() {
-    int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&col_pass_kernel<CGeo512Half, 2, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)CGeo512Half::LDS_BYTES);
-    if (rc) return rc;
-    return CDispatch<kColPassMinLog, kColPassMaxLog>::init();
 }
 bool col_pass_f64_supported(int logn) { return logn >= kColF64MinLog && logn <= kColPassMaxLogF64; }
 

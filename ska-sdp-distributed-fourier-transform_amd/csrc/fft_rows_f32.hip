@@ -4,5 +4,4 @@ namespace swf {
 int launch_fft_rows(int logn, const RowsArgs<float>& a, const OffTab& tab, hipStream_t s) {
     return Dispatch<float, kMinLogN, kMaxLogNFloat>::launch(logn, a, tab, s);
 }
-int init_fft_rows_f32() { return Dispatch<float, kMinLogN, kMaxLogNFloat>::init(); }
 }  // namespace swf

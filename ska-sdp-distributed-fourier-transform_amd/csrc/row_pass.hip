@@ -1,6 +1,7 @@
 // instantiations + dispatch of the lean long-row kernel (complex64)
 #include <cstdlib>
 
+#include "swiftly_launch.h"
 #include "swiftly_rowpass.h"
 
 namespace swf {
@@ -21,28 +22,14 @@ struct RGeoFor {
 template <int LOGN, int MODE>
 static int launch_mode(const RowPassArgs& a, hipStream_t s) {
     using G = typename RGeoFor<LOGN>::type;
-    hipLaunchKernelGGL((row_pass_kernel<G, MODE>), dim3((unsigned)a.nrows), dim3(G::NT), G::LDS_BYTES, s, a, a.in,
-                       a.out, a.ld_win, a.st_win, a.st_win2, a.tw);
-    return (int)hipGetLastError();
+    return launch_lds<row_pass_kernel<G, MODE>, G::LDS_BYTES>(dim3((unsigned)a.nrows), dim3(G::NT), s, a, a.in, a.out, a.ld_win,
+                                                              a.st_win, a.st_win2, a.tw);
 }
 template <int LOGN>
 static int launch_one(int mode, const RowPassArgs& a, hipStream_t s) {
     if (mode == 0) return launch_mode<LOGN, 0>(a, s);
     if (mode == 1) return launch_mode<LOGN, 1>(a, s);
     return launch_mode<LOGN, 2>(a, s);
-}
-template <int LOGN, int MODE>
-static int init_mode() {
-    using G = typename RGeoFor<LOGN>::type;
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_pass_kernel<G, MODE>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-}
-template <int LOGN>
-static int init_one() {
-    int rc = init_mode<LOGN, 0>();
-    if (!rc) rc = init_mode<LOGN, 1>();
-    if (!rc) rc = init_mode<LOGN, 2>();
-    return rc;
 }
 
 int launch_row_pass(int logn, int mode, const RowPassArgs& a, hipStream_t s) {
@@ -58,12 +45,10 @@ template <class G, int LOGS>
 static int launch_split(const RowPassArgs& a, const cx<float>* tw_part, const cx<float>* tw_full, hipStream_t s) {
     const unsigned blocks = (unsigned)(((a.nrows + 7) / 8) * (8 << LOGS));
     if (a.ld_win)
-        hipLaunchKernelGGL((row_pass_split_kernel<G, LOGS, true>), dim3(blocks), dim3(G::NT), G::LDS_BYTES, s, a, a.in,
-                           a.out, a.ld_win, tw_part, tw_full);
-    else
-        hipLaunchKernelGGL((row_pass_split_kernel<G, LOGS, false>), dim3(blocks), dim3(G::NT), G::LDS_BYTES, s, a,
-                           a.in, a.out, a.ld_win, tw_part, tw_full);
-    return (int)hipGetLastError();
+        return launch_lds<row_pass_split_kernel<G, LOGS, true>, G::LDS_BYTES>(dim3(blocks), dim3(G::NT), s, a, a.in, a.out,
+                                                                              a.ld_win, tw_part, tw_full);
+    return launch_lds<row_pass_split_kernel<G, LOGS, false>, G::LDS_BYTES>(dim3(blocks), dim3(G::NT), s, a, a.in, a.out, a.ld_win,
+                                                                           tw_part, tw_full);
 }
 using SplitGeo2 = RGeo<14, 4, true>;   // 2 x 16384 points, 1024 threads x 16 (one workgroup per CU)
 // (4 x 8192 points in 512-thread workgroups and the interleaved-exchange forms were measured slower in r1-r2)
@@ -97,10 +82,10 @@ static int data_segment_run(const RowPassArgs& a, int n, int seglen, int* first)
 }
 
 template <class G, bool PAIR, bool WIN, int ST, int NSEG, int CJ = -1, bool W4 = false>
-static void launch_band_inst(const RowPassArgs& a, unsigned blocks, const cx<float>* tw14, const cx<float>* tw_full,
-                             hipStream_t s) {
-    hipLaunchKernelGGL((row_pass_band_kernel<G, WIN, ST, PAIR, NSEG, CJ, W4>), dim3(blocks), dim3(G::NT), G::LDS_BYTES, s, a,
-                       a.in, a.out, a.ld_win, tw14, tw_full);
+static int launch_band_inst(const RowPassArgs& a, unsigned blocks, const cx<float>* tw14, const cx<float>* tw_full,
+                            hipStream_t s) {
+    return launch_lds<row_pass_band_kernel<G, WIN, ST, PAIR, NSEG, CJ, W4>, G::LDS_BYTES>(dim3(blocks), dim3(G::NT), s, a, a.in,
+                                                                                          a.out, a.ld_win, tw14, tw_full);
 }
 
 // -- re-laid-out load windows (Win4Cache, swiftly_rowpass.h) ------------------------------------------------------
@@ -182,11 +167,10 @@ static int launch_band_geo(const RowPassArgs& a0, const cx<float>* tw14, const c
         constexpr int SEGLEN = PAIR ? 2 * G::T : G::T;
         int first = 0;
         const int run = data_segment_run(a, 2 * G::N, SEGLEN, &first);
-#define SWF_TRY_SEG(WIN, ST, NS, CJ)                                   \
-    if (run <= NS) {                                                   \
-        a.seg_rot = first;                                             \
-        launch_band_inst<G, PAIR, WIN, ST, NS, CJ>(a, blocks, tw14, tw_full, s); \
-        return (int)hipGetLastError();                                 \
+#define SWF_TRY_SEG(WIN, ST, NS, CJ)                                                    \
+    if (run <= NS) {                                                                    \
+        a.seg_rot = first;                                                              \
+        return launch_band_inst<G, PAIR, WIN, ST, NS, CJ>(a, blocks, tw14, tw_full, s); \
     }
         // these instances also have the conjugations compiled in (CJ): prepare_facet is an inverse transform (both
         // set), finish_facet a forward one (neither)
@@ -208,13 +192,9 @@ static int launch_band_geo(const RowPassArgs& a0, const cx<float>* tw14, const c
             const int ew_ = launch_row_pass_whole(a, NS, tw14, tw_full, s);                    \
             if (ew_ != -2 || a.win_full) return ew_;                                           \
         }                                                                                      \
-        if (a.twc)                                                                        \
-            launch_band_inst<GC, PAIR, true, 1, NS, 1, true>(a, blocks, tw14, tw_full, s);     \
-        else if (a.ld_win4)                                                                    \
-            launch_band_inst<GP, PAIR, true, 1, NS, 1, true>(a, blocks, tw14, tw_full, s);     \
-        else                                                                                   \
-            launch_band_inst<GP, PAIR, true, 1, NS, 1>(a, blocks, tw14, tw_full, s);           \
-        return (int)hipGetLastError();                                                         \
+        if (a.twc) return launch_band_inst<GC, PAIR, true, 1, NS, 1, true>(a, blocks, tw14, tw_full, s); \
+        if (a.ld_win4) return launch_band_inst<GP, PAIR, true, 1, NS, 1, true>(a, blocks, tw14, tw_full, s); \
+        return launch_band_inst<GP, PAIR, true, 1, NS, 1>(a, blocks, tw14, tw_full, s);        \
     }
                 SWF_TRY_SEG_PRE(16)
                 SWF_TRY_SEG_PRE(22)
@@ -225,11 +205,10 @@ static int launch_band_geo(const RowPassArgs& a0, const cx<float>* tw14, const c
                 // backward finish: compact twiddle sections when the caller owns the tables
                 using GB = RGeoC<G::LOGN, G::LOGP, G::SPLIT>;
                 a.twc = (w4cache && win4_enabled() >= 2) ? w4cache->twc : nullptr;
-#define SWF_TRY_SEG_C(NS)                                                              \
-    if (a.twc && run <= NS) {                                                          \
-        a.seg_rot = first;                                                             \
-        launch_band_inst<GB, PAIR, false, 2, NS, 0>(a, blocks, tw14, tw_full, s);      \
-        return (int)hipGetLastError();                                                 \
+#define SWF_TRY_SEG_C(NS)                                                                \
+    if (a.twc && run <= NS) {                                                            \
+        a.seg_rot = first;                                                               \
+        return launch_band_inst<GB, PAIR, false, 2, NS, 0>(a, blocks, tw14, tw_full, s); \
     }
                 SWF_TRY_SEG_C(13)
                 SWF_TRY_SEG_C(16)
@@ -245,17 +224,10 @@ static int launch_band_geo(const RowPassArgs& a0, const cx<float>* tw14, const c
 #undef SWF_TRY_SEG
     }
 #define SWF_LAUNCH_BAND(WIN, ST) launch_band_inst<G, PAIR, WIN, ST, 0>(a, blocks, tw14, tw_full, s)
-    if (a.band_len < 0) {  // mapped (crop + window) store: finish_* primitives
-        SWF_LAUNCH_BAND(false, 2);
-    } else if (a.ld_win) {
-        if (band) SWF_LAUNCH_BAND(true, 1);
-        else SWF_LAUNCH_BAND(true, 0);
-    } else {
-        if (band) SWF_LAUNCH_BAND(false, 1);
-        else SWF_LAUNCH_BAND(false, 0);
-    }
+    if (a.band_len < 0) return SWF_LAUNCH_BAND(false, 2);  // mapped (crop + window) store: finish_* primitives
+    if (a.ld_win) return band ? SWF_LAUNCH_BAND(true, 1) : SWF_LAUNCH_BAND(true, 0);
+    return band ? SWF_LAUNCH_BAND(false, 1) : SWF_LAUNCH_BAND(false, 0);
 #undef SWF_LAUNCH_BAND
-    return (int)hipGetLastError();
 }
 using BandGeo64k = RGeo<15, 5, true>;  // yN = 65536: 2 x 32768 points, 1024 threads x 32, 132 KB LDS, one workgroup per CU
 using BandGeo16k = RGeo<13, 4, true>;  // yN = 16384: 2 x  8192 points,  512 threads x 16, 33 KB LDS
@@ -291,79 +263,12 @@ int row_pass_band_occupancy() {
                                                        BandGeo5::LDS_BYTES);
     return n;
 }
-template <class G, bool WIN, int ST>
-static int init_band() {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_pass_band_kernel<G, WIN, ST>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-}
-template <class G, bool WIN, int ST, int NSEG = 0, bool PAIR = true, int CJ = -1, bool W4 = false>
-static int init_band_pair() {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_pass_band_kernel<G, WIN, ST, PAIR, NSEG, CJ, W4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-}
-template <class G>
-static int init_band_geo() {
-    int rc = init_band<G, true, 1>();
-    if (!rc) rc = init_band<G, true, 0>();
-    if (!rc) rc = init_band<G, false, 1>();
-    if (!rc) rc = init_band<G, false, 0>();
-    if (!rc) rc = init_band<G, false, 2>();
-    return rc;
-}
 // occupancy query (blocks per CU) for tuning / DESIGN.md
 int row_pass_half_occupancy(int lds_bytes) {
     int n = -1;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, row_pass_split_kernel<SplitGeo2, 1, false>, SplitGeo2::NT,
                                                        lds_bytes < 0 ? SplitGeo2::LDS_BYTES : (size_t)lds_bytes);
     return n;
-}
-template <class G, int LOGS>
-static int init_split() {
-    int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_pass_split_kernel<G, LOGS, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-    if (rc) return rc;
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_pass_split_kernel<G, LOGS, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-}
-int init_row_pass() {
-    {
-        int rcb = init_band_geo<BandGeo5>();
-        if (!rcb) rcb = init_band_pair<BandGeo5, true, 1>();
-        if (!rcb) rcb = init_band_pair<BandGeo5, true, 0>();
-        if (!rcb) rcb = init_band_pair<BandGeo5, false, 1>();
-        if (!rcb) rcb = init_band_pair<BandGeo5, false, 0>();
-        if (!rcb) rcb = init_band_pair<BandGeo5, false, 2>();
-        using BandGeo5Pre = RGeoPre<14, 5, true>;
-        if (!rcb) rcb = init_band_pair<BandGeo5Pre, true, 1, 16, true, 1>();
-        if (!rcb) rcb = init_band_pair<BandGeo5Pre, true, 1, 22, true, 1>();
-        if (!rcb) rcb = init_band_pair<BandGeo5Pre, true, 1, 24, true, 1>();
-        if (!rcb) rcb = init_band_pair<BandGeo5Pre, true, 1, 16, true, 1, true>();
-        if (!rcb) rcb = init_band_pair<BandGeo5Pre, true, 1, 22, true, 1, true>();
-        if (!rcb) rcb = init_band_pair<BandGeo5Pre, true, 1, 24, true, 1, true>();
-        using BandGeo5PreC = RGeoPreC<14, 5, true>;
-        if (!rcb) rcb = init_band_pair<BandGeo5PreC, true, 1, 16, true, 1, true>();
-        if (!rcb) rcb = init_band_pair<BandGeo5PreC, true, 1, 22, true, 1, true>();
-        if (!rcb) rcb = init_band_pair<BandGeo5PreC, true, 1, 24, true, 1, true>();
-        if (!rcb) rcb = init_band_pair<BandGeo5, false, 2, 13, true, 0>();
-        if (!rcb) rcb = init_band_pair<BandGeo5, false, 2, 16, true, 0>();
-        using BandGeo5C = RGeoC<14, 5, true>;
-        if (!rcb) rcb = init_band_pair<BandGeo5C, false, 2, 13, true, 0>();
-        if (!rcb) rcb = init_band_pair<BandGeo5C, false, 2, 16, true, 0>();
-        if (!rcb) rcb = init_band_pair<BandGeo64k, true, 1, 44, false, 1>();
-        if (!rcb) rcb = init_row_pass_whole();
-        if (!rcb) rcb = init_band_geo<BandGeo4>();
-        if (!rcb) rcb = init_band_geo<BandGeo64k>();
-        if (!rcb) rcb = init_band_geo<BandGeo16k>();
-        if (rcb) return rcb;
-    }
-    {
-        int rc0 = init_split<SplitGeo2, 1>();
-        if (rc0) return rc0;
-    }
-    int rc = init_one<13>();
-    if (!rc) rc = init_one<14>();
-    if (!rc) rc = init_one<15>();
-    return rc;
 }
 
 }  // namespace swf

@@ -4,6 +4,7 @@
 #if SWF_TRACE
 #define swf_trace_buf swf_wtrace_buf   // this translation unit's own stamp buffer (device symbols are per code object)
 #endif
+#include "swiftly_launch.h"
 #include "swiftly_rowwhole.h"
 
 namespace swf {
@@ -36,9 +37,8 @@ int row_pass_whole_grid() {  // one workgroup per CU (256 VGPRs x 512 threads: a
 template <int NSEG, bool WIN = false>
 static int launch_whole_inst(const RowPassArgs& a, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s) {
     const int grid = a.nrows < row_pass_whole_grid() ? a.nrows : row_pass_whole_grid();
-    hipLaunchKernelGGL((row_pass_whole_kernel<NSEG, WIN>), dim3((unsigned)grid), dim3(RGeoWhole::NT), WIN ? kWholeWinLds : RGeoWhole::LDS_BYTES, s, a,
-                       a.in, a.out, tw14, tw_full, a.row_win, a.in_rowmap);
-    return (int)hipGetLastError();
+    return launch_lds<row_pass_whole_kernel<NSEG, WIN>, (WIN ? kWholeWinLds : RGeoWhole::LDS_BYTES)>(
+        dim3((unsigned)grid), dim3(RGeoWhole::NT), s, a, a.in, a.out, tw14, tw_full, a.row_win, a.in_rowmap);
 }
 
 // forward K1 with the re-laid-out window (a.ld_win4) and the compact twiddle sections (a.twc) set, a.seg_rot chosen for
@@ -68,20 +68,6 @@ int launch_row_pass_whole(const RowPassArgs& a, int nseg, const cx<float>* tw14,
 int row_pass_whole_stage_columns() {
     using GM = Geo<float, 9, 3, RGeoWhole::NT, false>;
     return (int)((RGeoWhole::LDS_BYTES - GM::LDS_BYTES) / 8) & ~31;  // stage | m-point exchange rows
-}
-template <int NSEG, bool WIN>
-static int init_whole_inst() {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&row_pass_whole_kernel<NSEG, WIN>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(WIN ? kWholeWinLds : RGeoWhole::LDS_BYTES));
-}
-int init_row_pass_whole() {
-    int rc = init_whole_inst<16, false>();
-    if (!rc) rc = init_whole_inst<22, false>();
-    if (!rc) rc = init_whole_inst<24, false>();
-    if (!rc) rc = init_whole_inst<16, true>();
-    if (!rc) rc = init_whole_inst<22, true>();
-    if (!rc) rc = init_whole_inst<24, true>();
-    return rc;
 }
 
 }  // namespace swf

@@ -1,4 +1,5 @@
 // complex128 pass A of the contiguous-axis four-step for 16384 / 32768 points (swiftly_rowslong.h)
+#include "swiftly_launch.h"
 #include "swiftly_rowslong.h"
 namespace swf {
 int launch_fft_long_a(const RowsArgs<double>& a, const OffTab& tab, const LongArgs<double>& L, hipStream_t s) {
@@ -6,11 +7,6 @@ int launch_fft_long_a(const RowsArgs<double>& a, const OffTab& tab, const LongAr
     const int tiles = (1 << L.log_n2) / G::RB;
     if (L.nrows <= 0) return 0;
     const dim3 grid((unsigned)((long long)L.nrows * tiles), a.nbatch > 0 ? a.nbatch : 1);
-    hipLaunchKernelGGL((fft_long_a_kernel<G, double>), grid, dim3(G::NT), kLongALds, s, a, tab, L);
-    return (int)hipGetLastError();
-}
-int init_fft_long_a() {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&fft_long_a_kernel<LongAGeo, double>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLongALds);
+    return launch_lds<fft_long_a_kernel<G, double>, kLongALds>(grid, dim3(G::NT), s, a, tab, L);
 }
 }  // namespace swf

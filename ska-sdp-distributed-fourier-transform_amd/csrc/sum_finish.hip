@@ -1,4 +1,5 @@
 // instantiations of the fused sum + finish row kernel for the (m, xM) pairs of the catalogue families
+#include "swiftly_launch.h"
 #include "swiftly_sumfinish.h"
 
 namespace swf {
@@ -7,14 +8,7 @@ template <int LOGM, int LOGX>
 static int launch_one(const SumFinishArgs& a, int nbatch, hipStream_t s) {
     using S = SFGeo<LOGM, LOGX>;
     dim3 grid((unsigned)((a.nrows + S::RB - 1) / S::RB), (unsigned)nbatch);
-    hipLaunchKernelGGL((sum_finish_rows_kernel<LOGM, LOGX>), grid, dim3(S::NT), S::LDS_BYTES, s, a);
-    return (int)hipGetLastError();
-}
-template <int LOGM, int LOGX>
-static int init_one() {
-    using S = SFGeo<LOGM, LOGX>;
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&sum_finish_rows_kernel<LOGM, LOGX>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES);
+    return launch_lds<sum_finish_rows_kernel<LOGM, LOGX>, S::LDS_BYTES>(grid, dim3(S::NT), s, a);
 }
 
 template <int LOGM, int LOGX, typename R = float>
@@ -22,13 +16,7 @@ static int launch_one_f(const SumFinishFacetArgs& a, int nbatch, hipStream_t s) 
     using S = SFGeo<LOGM, LOGX, R>;
     dim3 grid((unsigned)((a.nrows + S::RB - 1) / S::RB), (unsigned)nbatch);
     constexpr size_t lds = sum_finish_facets_kernel_lds<LOGM, LOGX, R>();
-    hipLaunchKernelGGL((sum_finish_facets_kernel<LOGM, LOGX, R>), grid, dim3(S::NT), lds, s, a);
-    return (int)hipGetLastError();
-}
-template <int LOGM, int LOGX, typename R = float>
-static int init_one_f() {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&sum_finish_facets_kernel<LOGM, LOGX, R>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sum_finish_facets_kernel_lds<LOGM, LOGX, R>()));
+    return launch_lds<sum_finish_facets_kernel<LOGM, LOGX, R>, lds>(grid, dim3(S::NT), s, a);
 }
 // (complex128: exchange buffer of the m-point transforms + the prepared row, in doubles; never the wave-parallel geometry)
 template <int LOGM, int LOGX, typename R>
@@ -41,22 +29,14 @@ static int launch_one_s(const SplitFacetArgs& a, int nbatch, hipStream_t s) {
     using S = SFGeo<LOGM, LOGX, R>;
     dim3 grid((unsigned)((a.nrows + S::RB - 1) / S::RB), (unsigned)nbatch);
     constexpr size_t lds = split_prepare_lds<LOGM, LOGX, R>();
-    static_assert(lds <= 160 * 1024, "LDS per workgroup");
-    hipLaunchKernelGGL((split_prepare_facets_kernel<LOGM, LOGX, R>), grid, dim3(S::NT), lds, s, a);
-    return (int)hipGetLastError();
-}
-template <int LOGM, int LOGX, typename R = float>
-static int init_one_s() {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&split_prepare_facets_kernel<LOGM, LOGX, R>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(split_prepare_lds<LOGM, LOGX, R>()));
+    return launch_lds<split_prepare_facets_kernel<LOGM, LOGX, R>, lds>(grid, dim3(S::NT), s, a);
 }
 
 template <int LOGM>
 static int launch_axis1(const Axis1RowsArgs& a, int nfacets, hipStream_t s) {
     using GM = typename Axis1Geo<LOGM>::GM;
     dim3 grid((unsigned)((a.nrows + GM::RB - 1) / GM::RB), (unsigned)nfacets);
-    hipLaunchKernelGGL((axis1_rows_kernel<LOGM>), grid, dim3(kAxis1Threads), Axis1Geo<LOGM>::LDS_BYTES, s, a);
-    return (int)hipGetLastError();
+    return launch_lds<axis1_rows_kernel<LOGM>, Axis1Geo<LOGM>::LDS_BYTES>(grid, dim3(kAxis1Threads), s, a);
 }
 int launch_axis1_rows(int logm, const Axis1RowsArgs& a, int nfacets, hipStream_t s) {
     switch (logm) {
@@ -104,24 +84,6 @@ int launch_split_prepare_facets_c128(int logm, int logx, const SplitFacetArgs& a
     SPLIT_PAIRS_C128(SF_CASE_SD)
 #undef SF_CASE_SD
     return -1;
-}
-int init_sum_finish_rows() {
-    int rc = 0;
-#define SF_INIT(M, XX)               \
-    if (!rc) rc = init_one<M, XX>(); \
-    if (!rc) rc = init_one_f<M, XX>(); \
-    if (!rc) rc = init_one_s<M, XX>();
-    SF_PAIRS(SF_INIT)
-#undef SF_INIT
-#define SF_INIT_D(M, XX) \
-    if (!rc) rc = init_one_f<M, XX, double>();
-    SF_PAIRS_C128(SF_INIT_D)
-#undef SF_INIT_D
-#define SF_INIT_SD(M, XX) \
-    if (!rc) rc = init_one_s<M, XX, double>();
-    SPLIT_PAIRS_C128(SF_INIT_SD)
-#undef SF_INIT_SD
-    return rc;
 }
 
 }  // namespace swf

@@ -186,8 +186,9 @@ static int make_mixed(swiftly_hip* h, int64_t n) {
     return rc;
 }
 
-// Kernel attributes (max dynamic LDS) and the memory-pool release threshold are per DEVICE state: they are set
-// once for every device a handle is created on, under a lock (handles may be created from several host threads).
+// Kernel attributes (max dynamic LDS; the table of swiftly_launch.h) and the memory-pool release threshold are per DEVICE
+// state: they are set once for every device a handle is created on, under a lock (handles may be created from several
+// host threads).
 static std::mutex g_init_mutex;
 static std::vector<char> g_device_inited;
 
@@ -218,12 +219,9 @@ int swiftly_hip_create(swiftly_hip_t** out, int64_t N, int64_t yN, int64_t xM, d
     std::lock_guard<std::mutex> init_lock(g_init_mutex);
     if ((int)g_device_inited.size() < ndev) g_device_inited.resize(ndev, 0);
     if (!g_device_inited[device]) {
-        if (int rc = init_fft_rows_f32()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (f32): %d", rc);
-        if (int rc = init_fft_rows_f64()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (f64): %d", rc);
-        if (int rc = init_fft_long_a()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (f64 long rows): %d", rc);
-        if (int rc = init_col_pass()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (col pass): %d", rc);
-        if (int rc = init_row_pass()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (row pass): %d", rc);
-        if (int rc = init_sum_finish_rows()) return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (sum finish): %d", rc);
+        int lds = 0;
+        if (int rc = set_registered_kernel_attributes(&lds))
+            return fail(SWIFTLY_ERR_HIP, "kernel attribute setup failed (%d bytes of LDS): %d", lds, rc);
         // keep freed scratch (the four-step intermediate, up to yN*yB*8 bytes) in the stream-ordered pool instead of
         // returning it to the driver at every synchronisation point
         hipMemPool_t pool;

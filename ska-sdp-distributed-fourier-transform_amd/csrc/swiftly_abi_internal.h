@@ -1,7 +1,9 @@
 // Internals shared by the translation units of the C ABI (swiftly_abi.hip: handles + the eight primitives and their
 // batch forms; swiftly_abi_coltransform.hip: the strided-axis transform, col_transform; swiftly_abi_pipeline.hip: the
 // fused / per-wave entry points of the streaming classes; swiftly_abi_util.hip: device memory, stream and diagnostic
-// helpers; swiftly_abi_sources.hip: point-source truths and RMSE checks).  Not installed: include/swiftly_hip.h is the public header.
+// helpers, and the table of kernels launched with dynamic LDS (swiftly_launch.h), whose per-device attributes
+// swiftly_hip_create sets from it; swiftly_abi_sources.hip: point-source truths and RMSE checks).  Not installed:
+// include/swiftly_hip.h is the public header.
 #pragma once
 
 #include <algorithm>
@@ -19,6 +21,7 @@
 
 #include "../../include/swiftly_hip.h"
 #include "swiftly_colpass.h"
+#include "swiftly_launch.h"
 #include "swiftly_rowpass.h"
 #include "swiftly_sumfinish.h"
 #include "swiftly_rows.h"

@@ -18,6 +18,30 @@ __global__ void cu_census_kernel(int* __restrict__ out) {
 
 thread_local int g_chain_chunk_streams = 0;
 
+// the kernels launched with dynamic LDS (swiftly_launch.h): filled while the library is loaded, read afterwards
+namespace swf {
+struct KernelLdsEntry {
+    const void* host_fn;
+    int lds_bytes;
+};
+static std::vector<KernelLdsEntry>& kernel_lds_table() {
+    static std::vector<KernelLdsEntry> table;
+    return table;
+}
+bool register_kernel_lds(const void* host_fn, int lds_bytes) {
+    kernel_lds_table().push_back({host_fn, lds_bytes});
+    return true;
+}
+int set_registered_kernel_attributes(int* failed_lds_bytes) {
+    for (const KernelLdsEntry& e : kernel_lds_table())
+        if (const hipError_t rc = hipFuncSetAttribute(e.host_fn, hipFuncAttributeMaxDynamicSharedMemorySize, e.lds_bytes)) {
+            *failed_lds_bytes = e.lds_bytes;
+            return (int)rc;
+        }
+    return 0;
+}
+}  // namespace swf
+
 extern "C" {
 
 const char* swiftly_hip_build_id(void) { return SWF_SRC_HASH; }
@@ -114,6 +138,16 @@ int swiftly_hip_cu_census(int32_t* out, int nblocks, void* stream) {
     if (!out || nblocks <= 0) return fail(SWIFTLY_ERR_PARAM, "null argument");
     hipLaunchKernelGGL(cu_census_kernel, dim3((unsigned)nblocks), dim3(64), 0, (hipStream_t)stream, out);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+int swiftly_hip_kernel_table(int64_t* count, int64_t* max_lds_bytes) {
+    if (!count || !max_lds_bytes) return fail(SWIFTLY_ERR_PARAM, "null argument");
+    *count = 0;
+    *max_lds_bytes = 0;
+    for (const KernelLdsEntry& e : kernel_lds_table()) {
+        ++*count;
+        *max_lds_bytes = std::max<int64_t>(*max_lds_bytes, e.lds_bytes);
+    }
     return 0;
 }
 

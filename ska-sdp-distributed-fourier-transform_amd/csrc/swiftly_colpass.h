@@ -482,6 +482,5 @@ constexpr int kColPassMinLog = 2;
 constexpr int kColPassMaxLog = 10;  // 1024 points: 32-column tiles
 
 int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s);
-int init_col_pass();
 
 }  // namespace swf

@@ -779,7 +779,6 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
 constexpr int kRowPassMinLog = 13;
 constexpr int kRowPassMaxLog = 15;
 int launch_row_pass(int logn, int mode, const RowPassArgs& a, hipStream_t s);
-int init_row_pass();
 int row_pass_half_occupancy(int lds_bytes);
 // multi-workgroup form for N = 32768 (MODE 0 only); tw14 / tw13 = tables of length 16384 / 8192, tw_full of length N
 int launch_row_pass_split(const RowPassArgs& a, const cx<float>* tw14, const cx<float>* tw13, const cx<float>* tw_full,
@@ -812,7 +811,6 @@ int launch_row_pass_band_n(int logn, const RowPassArgs& a, const cx<float>* tw_h
                            Win4Cache* w4 = nullptr);
 int row_pass_band_occupancy();
 int launch_row_pass_whole(const RowPassArgs& a, int nseg, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s);
-int init_row_pass_whole();
 int row_pass_whole_grid();  // workgroups of a whole-row launch (one per CU)
 
 }  // namespace swf

@@ -273,7 +273,5 @@ constexpr int kMaxLogNDoubleRows = 15;
 // implemented in fft_rows_f32.hip / fft_rows_f64.hip
 int launch_fft_rows(int logn, const RowsArgs<float>& a, const OffTab& tab, hipStream_t s);
 int launch_fft_rows(int logn, const RowsArgs<double>& a, const OffTab& tab, hipStream_t s);
-int init_fft_rows_f32();
-int init_fft_rows_f64();
 
 }  // namespace swf

@@ -97,6 +97,5 @@ __global__ __launch_bounds__(G::NT) void fft_long_a_kernel(const RowsArgs<R> A, 
 
 // implemented in rows_long_f64.hip
 int launch_fft_long_a(const RowsArgs<double>& a, const OffTab& tab, const LongArgs<double>& L, hipStream_t s);
-int init_fft_long_a();
 
 }  // namespace swf

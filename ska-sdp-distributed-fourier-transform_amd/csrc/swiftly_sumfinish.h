@@ -736,7 +736,6 @@ int launch_split_prepare_facets_c128(int logm, int logx, const SplitFacetArgs& a
 int launch_sum_finish_facets(int logm, int logx, const SumFinishFacetArgs& a, int nbatch, hipStream_t s);
 int launch_sum_finish_facets_c128(int logm, int logx, const SumFinishFacetArgs& a, int nbatch, hipStream_t s);
 int launch_sum_finish_rows(int logm, int logx, const SumFinishArgs& a, int nbatch, hipStream_t s);
-int init_sum_finish_rows();
 int launch_axis1_rows(int logm, const Axis1RowsArgs& a, int nfacets, hipStream_t s);
 
 }  // namespace swf

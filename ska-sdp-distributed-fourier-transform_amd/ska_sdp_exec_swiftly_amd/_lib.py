@@ -182,6 +182,8 @@ def _declare(lib):
     lib.swiftly_hip_stream_destroy.argtypes = [vp]
     lib.swiftly_hip_cu_census.restype = c_int
     lib.swiftly_hip_cu_census.argtypes = [vp, c_int, vp]
+    lib.swiftly_hip_kernel_table.restype = c_int
+    lib.swiftly_hip_kernel_table.argtypes = [POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]
 
 
 def load():
