@@ -383,6 +383,20 @@ int swiftly_hip_prepare_facet_columns_waves(swiftly_hip_t* h, int dtype, const v
                                             int64_t rowmap_stride, void* workspace, int64_t workspace_bytes,
                                             void* stream);
 
+/* K2 on a column range: prepare_facet_columns_waves for ONE wave, but only the positions [col_first, col_first + ncols)
+ * of the m-wide window (both multiples of 16, 0 < ncols <= m): out keeps the [rows kept, m] layout and row stride, its
+ * other columns are not touched.  SWIFTLY_ERR_PARAM when one of the requested columns lies outside the band
+ * [band_start, band_start + band_len).  With subgrid_off1 = j*m*N/yN this fills (part of) column slab j of the padded
+ * axis -- the columns (yN/2 - m/2 + j*m + [0, m)) mod yN at positions 0 .. m-1, the positions every wave's Q keeps them
+ * at -- so that neighbouring waves, whose windows overlap, share it (transform_contributions_pieces).  Power-of-two
+ * yN_size. */
+int swiftly_hip_prepare_facet_columns_range(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                            int64_t in_facet_stride, int64_t nfacets, const int64_t* facet_off0s,
+                                            int64_t band_start, int64_t band_len, int64_t subgrid_off1, int64_t col_first,
+                                            int64_t ncols, void* out, int64_t out_row_stride, int64_t out_facet_stride,
+                                            const int32_t* out_rowmap, void* workspace, int64_t workspace_bytes,
+                                            void* stream);
+
 /* K3 + K4a: out[f][b][k, j] = Fn[k] * cfft_m(C_{f,b}[:, j])[(k + s'0_f) mod m]  --  add_to_subgrid(axis 0)
  * (core.py:744, numpy form core.py:274-285) of the [m, m] contribution C_{f,b} WITHOUT its placement into the
  * padded subgrid (row k belongs to padded row (k + xM/2 - m/2 + s'0_f) mod xM; sum_finish_facets resolves that).
@@ -398,6 +412,21 @@ int swiftly_hip_transform_contributions(swiftly_hip_t* h, int dtype, const void*
                                         int64_t band_start, int64_t band_len, int64_t nfacets,
                                         const int64_t* facet_off0s, int64_t nsub, const int64_t* subgrid_offs,
                                         void* out, int64_t out_facet_stride, int64_t out_sub_stride, void* stream);
+
+/* transform_contributions, layout 1, for a wave whose window lies in up to two Q buffers (npieces <= 2; host arrays of
+ * that length): piece i holds the window positions [first[i], first[i] + count[i]) (multiples of 16; together exactly
+ * [0, m), disjoint) at the SAME positions of its rows: q[i] + f*q_facet_strides[i] = [n_rows[i] kept rows, m] with row map
+ * rowmaps[i] (device int32[yN] or NULL; it may keep more rows than the subgrids read).  Column j of every output block
+ * comes from the piece that holds position j; a piece with count 0 is skipped.  Output placement as wave_facet_side:
+ * g_offsets / g_facet_strides (both or neither), else g_facet_stride / g_sub_stride.  Bit-identical to
+ * transform_contributions on a Q assembled from the pieces. */
+int swiftly_hip_transform_contributions_pieces(swiftly_hip_t* h, int dtype, int64_t npieces, const void* const* q,
+                                               const int64_t* q_facet_strides, const int32_t* const* rowmaps,
+                                               const int64_t* n_rows, const int64_t* first, const int64_t* count,
+                                               int64_t nfacets, const int64_t* facet_off0s, int64_t nsub,
+                                               const int64_t* sub_off0s, void* g_out, int64_t g_facet_stride,
+                                               int64_t g_sub_stride, const int64_t* g_offsets,
+                                               const int64_t* g_facet_strides, void* stream);
 
 /* K4b + K5a: for every padded row r < xM of every subgrid b:
  *   out[b][r, :] = mask_b * finish_subgrid_axis1( sum_f add_to_subgrid_axis1( G[f][b][k_f(r), :], facet_off1s[f] ) )

@@ -191,9 +191,9 @@ static int run_chunked(swiftly_hip* h, const ColPlan& p, const ColPassArgs& c, c
             // item z of the launch sits at slot + (z - z0) * n * Wc (raw_z0: the kernels address the scratch
             // with the item index relative to the launch's first item)
             cx<float>* slot = cx_at(scratch, (long long)((size_t)(i & 1) * slot_elems), p.c128);
-            ColPassArgs A = A0;  // the chunk's columns through col0 (`in` unchanged), into the chunk's slot; `cz` as given
+            ColPassArgs A = A0;  // the chunk's columns through col0 (`in` unchanged; behind the caller's first column), into the chunk's slot; `cz` as given
             A.scratch_nt = 0;
-            A.ncols = wc; A.col0 = c0; A.z0 = z0; A.raw_z0 = z0;
+            A.ncols = wc; A.col0 = c.col0 + c0; A.z0 = z0; A.raw_z0 = z0;
             A.out = slot; A.out_pitch = (unsigned)Wc; A.out_bs = (long long)(p.n * Wc);
             rc = launch_col_checked(p.l1, 0, A, cz, p.n2, nz, s2);
             if (rc) break;

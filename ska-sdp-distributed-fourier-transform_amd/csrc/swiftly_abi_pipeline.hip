@@ -226,8 +226,11 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
                                       int64_t band_start, int64_t band_len, int64_t nwaves, const int64_t* wave_off1s,
                                       void* out, int64_t out_row_stride, int64_t out_facet_stride,
                                       int64_t out_wave_stride, const int32_t* rowmaps, int64_t rowmap_stride,
-                                      void* stream, void* ws = nullptr, size_t ws_bytes = 0) {
+                                      void* stream, void* ws = nullptr, size_t ws_bytes = 0, int64_t col_first = 0,
+                                      int64_t ncols = -1) {
     if (!h || !in || !out || !facet_off0s || !wave_off1s) return fail(SWIFTLY_ERR_PARAM, "null argument");
+    const bool ranged = ncols >= 0;  // positions [col_first, col_first + ncols) of the window only, checked against the band
+    if (!ranged) ncols = h->m;       // (the whole window, as ever)
     const bool c128 = dtype == SWIFTLY_C128;
     if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
     if (c128 && !band_pipeline_c128_supported(h))
@@ -243,6 +246,21 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
     if (rows <= 0 || rows >= yN) return fail(SWIFTLY_ERR_PARAM, "facet size %lld must be in [1, yN_size - 1]", (long long)rows);
     if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN) return fail(SWIFTLY_ERR_PARAM, "bad band");
     if (nfacets <= 0 || nwaves <= 0) return 0;
+    if (ranged) {
+        if (col_first < 0 || ncols <= 0 || col_first + ncols > m || col_first % 16 || ncols % 16)
+            return fail(SWIFTLY_ERR_PARAM, "prepare_facet_columns: column range [%lld, +%lld) must be multiples of 16 inside [0, %d)",
+                        (long long)col_first, (long long)ncols, m);
+        if (h->log_yN < 0) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: a column range needs a power-of-two yN_size");
+        // every requested column has to come from the band (the whole-window form maps a stray column to band column 0)
+        for (int64_t w = 0; w < nwaves; w++) {
+            const int64_t s = floordiv(wave_off1s[w] * h->yN, h->N);
+            const int64_t rot = pmod(-s, m), base = pmod(yN / 2 - m / 2 + s, yN);
+            for (int64_t q = col_first; q < col_first + ncols; q++)
+                if (pmod(base + ((q + rot) & (m - 1)) - band_start, yN) >= band_len)
+                    return fail(SWIFTLY_ERR_PARAM, "prepare_facet_columns: position %lld of the window of off1 = %lld is outside the "
+                                "band [%lld, +%lld)", (long long)q, (long long)wave_off1s[w], (long long)band_start, (long long)band_len);
+        }
+    }
     if (h->log_yN < 0)
         return prepare_facet_columns_mixed(h, in, rows, in_row_stride, in_facet_stride, nfacets, facet_off0s, band_start,
                                            band_len, nwaves, wave_off1s, out, out_row_stride, out_facet_stride,
@@ -253,7 +271,8 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
     const int lo = yN / 2 - (int)(rows / 2);
     ColPassArgs c;
     std::memset(&c, 0, sizeof c);
-    c.ncols = m;
+    c.ncols = (int)ncols;
+    c.col0 = (int)col_first;  // the gather sees window position col_first + column; the output pointer is shifted below
     c.full_logn = h->log_yN;
     c.in_pitch = (unsigned)in_row_stride;
     c.out_pitch = (unsigned)out_row_stride;
@@ -271,7 +290,7 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
     const int per_f = kColZF;  // facets per launch group (smaller groups: no gain, r4)
     // keep the four-step scratch of one launch group below ~4 GB
     const int64_t group_cap = ws ? (int64_t)ws_bytes : (int64_t(4) << 30);
-    const int64_t per_w_cap = std::max<int64_t>(1, group_cap / ((int64_t)yN * m * esz) / std::min<int64_t>(per_f, nfacets));
+    const int64_t per_w_cap = std::max<int64_t>(1, group_cap / ((int64_t)yN * ncols * esz) / std::min<int64_t>(per_f, nfacets));
     const int per_w = (int)std::min<int64_t>(kColZB, per_w_cap);
     for (int64_t f0 = 0; f0 < nfacets; f0 += per_f) {
         const int nf = (int)std::min<int64_t>(per_f, nfacets - f0);
@@ -289,11 +308,11 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
             // item z = f*nw + w reads band buffer f, writes out[f][w]
             c.in = cx_at(in, f0 * in_facet_stride, c128);
             c.in_bdiv = nw; c.in_bs_hi = in_facet_stride; c.in_bs = 0;
-            c.out = cx_at(out, f0 * out_facet_stride + w0 * out_wave_stride, c128);
+            c.out = cx_at(out, f0 * out_facet_stride + w0 * out_wave_stride + col_first, c128);
             c.out_bdiv = nw; c.out_bs_hi = out_facet_stride; c.out_bs = out_wave_stride;
             c.st_rowmap = rowmaps ? rowmaps + w0 * rowmap_stride : nullptr;
             c.st_rowmap_bs = rowmaps ? rowmap_stride : 0;
-            const int rc = col_transform(h, h->log_yN, c, cz, m, nf * nw, (hipStream_t)stream, ws, ws_bytes);
+            const int rc = col_transform(h, h->log_yN, c, cz, (int)ncols, nf * nw, (hipStream_t)stream, ws, ws_bytes);
             if (rc == -1) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: padded facet size %d not supported", yN);
             if (rc) return rc;
         }
@@ -329,6 +348,23 @@ int swiftly_hip_prepare_facet_columns_waves(swiftly_hip_t* h, int dtype, const v
                                       rowmaps, rowmap_stride, stream, workspace, workspace ? (size_t)workspace_bytes : 0);
 }
 
+/* K2 on a column range: swiftly_hip_prepare_facet_columns_waves for one wave, positions [col_first, col_first + ncols) of
+ * the m-wide window only (multiples of 16; the other columns of `out` are not touched).  Refused when a requested column
+ * lies outside the band. */
+int swiftly_hip_prepare_facet_columns_range(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                            int64_t in_facet_stride, int64_t nfacets, const int64_t* facet_off0s,
+                                            int64_t band_start, int64_t band_len, int64_t subgrid_off1, int64_t col_first,
+                                            int64_t ncols, void* out, int64_t out_row_stride, int64_t out_facet_stride,
+                                            const int32_t* out_rowmap, void* workspace, int64_t workspace_bytes,
+                                            void* stream) {
+    if (!h) return fail(SWIFTLY_ERR_PARAM, "null argument");
+    DeviceGuard device_guard_(h->device);
+    if (ncols <= 0) return fail(SWIFTLY_ERR_PARAM, "prepare_facet_columns: empty column range");
+    return prepare_facet_columns_impl(h, dtype, in, rows, in_row_stride, in_facet_stride, nfacets, facet_off0s, band_start,
+                                      band_len, 1, &subgrid_off1, out, out_row_stride, out_facet_stride, 0, out_rowmap, 0,
+                                      stream, workspace, workspace ? (size_t)workspace_bytes : 0, col_first, ncols);
+}
+
 } // extern "C" (helper follows)
 // out_offs / out_fstrides (optional, per subgrid): item (f, b) is written at out + out_offs[b] + f*out_fstrides[b]
 // instead of out + f*out_facet_stride + b*out_sub_stride
@@ -337,8 +373,14 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
                                         int64_t band_start, int64_t band_len, int64_t nfacets,
                                         const int64_t* facet_off0s, int64_t nsub, const int64_t* subgrid_offs,
                                         void* out, int64_t out_facet_stride, int64_t out_sub_stride,
-                                        const int64_t* out_offs, const int64_t* out_fstrides, void* stream) {
+                                        const int64_t* out_offs, const int64_t* out_fstrides, void* stream,
+                                        int64_t col_first = 0, int64_t ncols = -1) {
     if (!h || !in || !out || !facet_off0s) return fail(SWIFTLY_ERR_PARAM, "null argument");
+    // columns [col_first, col_first + ncols) of the blocks only (layout 1, whose columns are read where they are written):
+    // both pointers are shifted, the other columns of `out` are not touched
+    if (ncols < 0) ncols = h->m;
+    if (col_first < 0 || ncols <= 0 || col_first + ncols > h->m || ((col_first || ncols != h->m) && layout != 1))
+        return fail(SWIFTLY_ERR_PARAM, "transform_contributions: bad column range [%lld, +%lld)", (long long)col_first, (long long)ncols);
     const bool c128 = dtype == SWIFTLY_C128;
     if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
     if (layout < 0 || layout > 2) return fail(SWIFTLY_ERR_PARAM, "bad layout %d", layout);
@@ -357,7 +399,7 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
         return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");
     ColPassArgs c;
     std::memset(&c, 0, sizeof c);
-    c.ncols = m;
+    c.ncols = (int)ncols;
     c.full_logn = h->log_m;
     c.in_pitch = (unsigned)in_row_stride;
     c.out_pitch = (unsigned)m;
@@ -397,13 +439,13 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
             if (layout == 0) cz.flags |= kZColGather;
             if (layout == 1) cz.flags |= kZLoadB;
             // item z = f*nb + b reads in + f*in_facet_stride (+ b*in_sub_stride for layout 2), writes out[f][b]
-            c.in = cx_at(in, f0 * in_facet_stride + (layout == 2 ? b0 * in_sub_stride : 0), c128);
+            c.in = cx_at(in, f0 * in_facet_stride + (layout == 2 ? b0 * in_sub_stride : 0) + col_first, c128);
             c.in_bdiv = nb; c.in_bs_hi = in_facet_stride; c.in_bs = layout == 2 ? in_sub_stride : 0;
-            c.out = cx_at(out, f0 * out_facet_stride + b0 * out_sub_stride, c128);
+            c.out = cx_at(out, f0 * out_facet_stride + b0 * out_sub_stride + col_first, c128);
             c.out_bdiv = nb; c.out_bs_hi = out_facet_stride; c.out_bs = out_sub_stride;
             if (out_offs) {
                 cz.flags |= kZOutB;
-                c.out = cx_at(out, 0, c128);
+                c.out = cx_at(out, col_first, c128);
                 for (int b = 0; b < nb; b++) {
                     cz.b_out_fs[b] = out_fstrides[b0 + b];
                     cz.b_out_off[b] = out_offs[b0 + b] + f0 * out_fstrides[b0 + b];
@@ -433,6 +475,46 @@ int swiftly_hip_transform_contributions(swiftly_hip_t* h, int dtype, const void*
     return transform_contributions_impl(h, dtype, in, layout, in_row_stride, in_facet_stride, in_sub_stride, in_rowmap,
                                         band_start, band_len, nfacets, facet_off0s, nsub, subgrid_offs, out,
                                         out_facet_stride, out_sub_stride, nullptr, nullptr, stream);
+}
+
+/* K3 + K4a of one wave whose window lies in up to two Q buffers (column slabs of the padded axis): piece i holds the
+ * positions [first[i], first[i] + count[i]) of the window, at the same positions of its rows, in q[i] (layout 1:
+ * [F, rows kept, m], facet stride q_facet_strides[i], row map rowmaps[i] over n_rows[i] kept rows).  The output is that
+ * of transform_contributions layout 1 (or, with g_offsets / g_facet_strides, of wave_facet_side with compute_q = 0) on a Q
+ * assembled from the pieces: one launch sequence per piece, a piece with count 0 is skipped. */
+int swiftly_hip_transform_contributions_pieces(swiftly_hip_t* h, int dtype, int64_t npieces, const void* const* q,
+                                               const int64_t* q_facet_strides, const int32_t* const* rowmaps,
+                                               const int64_t* n_rows, const int64_t* first, const int64_t* count,
+                                               int64_t nfacets, const int64_t* facet_off0s, int64_t nsub,
+                                               const int64_t* sub_off0s, void* g_out, int64_t g_facet_stride,
+                                               int64_t g_sub_stride, const int64_t* g_offsets,
+                                               const int64_t* g_facet_strides, void* stream) {
+    if (!h || !q || !q_facet_strides || !rowmaps || !n_rows || !first || !count || !g_out || !facet_off0s || !sub_off0s)
+        return fail(SWIFTLY_ERR_PARAM, "null argument");
+    if (npieces < 0 || npieces > 2) return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: 0..2 pieces, got %lld", (long long)npieces);
+    if (!g_offsets != !g_facet_strides) return fail(SWIFTLY_ERR_PARAM, "g_offsets and g_facet_strides go together");
+    DeviceGuard device_guard_(h->device);
+    const int64_t m = h->m;
+    int64_t covered = 0;
+    for (int64_t i = 0; i < npieces; i++) {
+        if (count[i] < 0 || first[i] < 0 || first[i] + count[i] > m || first[i] % 16 || count[i] % 16)
+            return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: piece %lld = [%lld, +%lld) must be multiples of 16 "
+                        "inside [0, %lld)", (long long)i, (long long)first[i], (long long)count[i], (long long)m);
+        if (count[i] && (!q[i] || n_rows[i] <= 0 || n_rows[i] > h->yN || q_facet_strides[i] < n_rows[i] * m))
+            return fail(SWIFTLY_ERR_PARAM, "bad row count %lld / facet stride %lld", (long long)n_rows[i], (long long)q_facet_strides[i]);
+        covered += count[i];
+    }
+    if (npieces == 2 && count[0] && count[1] && first[0] < first[1] + count[1] && first[1] < first[0] + count[0])
+        return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: the pieces overlap");
+    if (covered != m) return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: the pieces hold %lld of %lld positions", (long long)covered, (long long)m);
+    for (int64_t i = 0; i < npieces; i++) {
+        if (!count[i]) continue;
+        if (int rc = transform_contributions_impl(h, dtype, q[i], 1, m, q_facet_strides[i], 0, rowmaps[i], 0, 0, nfacets,
+                                                  facet_off0s, nsub, sub_off0s, g_out, g_facet_stride, g_sub_stride, g_offsets,
+                                                  g_facet_strides, stream, first[i], count[i]))
+            return rc;
+    }
+    return 0;
 }
 
 static int sum_finish_facets_impl(swiftly_hip_t* h, int dtype, const void* in, int64_t nfacets, int64_t in_facet_stride,

@@ -127,6 +127,14 @@ def _declare(lib):
     lib.swiftly_hip_prepare_facet_columns_waves.argtypes = [
         vp, c_int, vp, i64, i64, i64, i64, pi64, i64, i64, i64, pi64, vp, i64, i64, i64, vp, i64, vp, i64, vp,
     ]
+    lib.swiftly_hip_prepare_facet_columns_range.restype = c_int
+    lib.swiftly_hip_prepare_facet_columns_range.argtypes = [
+        vp, c_int, vp, i64, i64, i64, i64, pi64, i64, i64, i64, i64, i64, vp, i64, i64, vp, vp, i64, vp,
+    ]
+    lib.swiftly_hip_transform_contributions_pieces.restype = c_int
+    lib.swiftly_hip_transform_contributions_pieces.argtypes = [
+        vp, c_int, i64, POINTER(vp), pi64, POINTER(vp), pi64, pi64, pi64, i64, pi64, i64, pi64, vp, i64, i64, pi64, pi64, vp,
+    ]
     lib.swiftly_hip_wave_subgrid_side.restype = c_int
     lib.swiftly_hip_wave_subgrid_side.argtypes = [
         vp, c_int, vp, i64, i64, i64, pi64, pi64, i64, pi64, pi64, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp,

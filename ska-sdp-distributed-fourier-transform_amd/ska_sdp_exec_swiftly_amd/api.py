@@ -65,3 +65,5 @@ log = logging.getLogger("fourier-logger")
 _PREFETCH = _prefetch_mod.PREFETCH_DEFAULT
 _PREFETCH_DEPTH = _prefetch_mod.PREFETCH_DEPTH_DEFAULT
 _CHAIN_K2 = _prefetch_mod.CHAIN_K2_DEFAULT
+# SWIFTLY_K2_SLABS=0: K2 per wave on the wave's whole window instead of once per column slab (slabs.py; A/B runs)
+_K2_SLABS = _prefetch_mod.K2_SLABS_DEFAULT

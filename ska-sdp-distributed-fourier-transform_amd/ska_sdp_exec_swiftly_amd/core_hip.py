@@ -697,7 +697,55 @@ class SwiftlyCoreHip:
                 cvp(scr.data_ptr()), scr.numel(), self._stream(),
             )
         )
+        self.k2_columns_issued += m
         return out
+
+    #: window columns per facet handed to K2 so far, whatever the entry point (the tests and A/B runs read it)
+    k2_columns_issued = 0
+
+    def prepare_facet_columns_range(self, bands, facet_off0s, band, subgrid_off1, col_first, ncols, out, rowmap=None):
+        """K2 on a column range (``swiftly_hip_prepare_facet_columns_range``): :py:meth:`prepare_facet_columns` for the
+        positions ``[col_first, col_first + ncols)`` of the window only (multiples of 16), written into the same columns of
+        ``out[F, n_rows, xM_yN_size]``; the other columns of ``out`` are not touched.  A range that leaves the band is
+        refused (ValueError)."""
+        F, yB = bands.shape[0], bands.shape[1]
+        if out.dim() != 3 or out.shape[0] != F or out.shape[2] != self.xM_yN_size or out.stride(2) != 1:
+            raise ValueError(f"Output array has shape {tuple(out.shape)}, expected ({F}, rows, {self.xM_yN_size})!")
+        scr = self.scratch("k2", self._k2_scratch_bytes(F, bands.element_size()))
+        cvp = ctypes.c_void_p
+        _lib.check(
+            self._lib.swiftly_hip_prepare_facet_columns_range(
+                self._handle, self._code(bands), cvp(bands.data_ptr()), int(yB), bands.stride(1), bands.stride(0), F,
+                self._i64(facet_off0s), int(band[0]), int(band[1]), int(subgrid_off1), int(col_first), int(ncols),
+                cvp(out.data_ptr()), out.stride(1), out.stride(0), cvp(rowmap.data_ptr()) if rowmap is not None else None,
+                cvp(scr.data_ptr()), scr.numel(), self._stream(),
+            )
+        )
+        self.k2_columns_issued += int(ncols)
+        return out
+
+    def transform_contributions_pieces(self, pieces, facet_off0s, sub_off0s, g_out, g_layout=None):
+        """K3 + K4a of a wave whose window lies in up to two ``Q`` buffers (``swiftly_hip_transform_contributions_pieces``):
+        ``pieces = [(Q[F, n_rows, m], rowmap, n_rows, first position, number of positions)]``, together the whole window;
+        output as :py:meth:`wave_facet_side` -- ``g_out[F, S, m, m]``, or a flat buffer with ``g_layout``."""
+        n = len(pieces)
+        F, S = pieces[0][0].shape[0], len(sub_off0s)
+        cvp = ctypes.c_void_p
+        qs = (cvp * n)(*[pc[0].data_ptr() for pc in pieces])
+        maps = (cvp * n)(*[pc[1].data_ptr() if pc[1] is not None else None for pc in pieces])
+        if g_layout is None:
+            fs, ss, offs, fstr = g_out.stride(0), g_out.stride(1), None, None
+        else:
+            fs, ss, offs, fstr = 0, 0, self._i64(g_layout[0]), self._i64(g_layout[1])
+        _lib.check(
+            self._lib.swiftly_hip_transform_contributions_pieces(
+                self._handle, self._code(pieces[0][0]), n, qs, self._i64([pc[0].stride(0) for pc in pieces]), maps,
+                self._i64([pc[2] for pc in pieces]), self._i64([pc[3] for pc in pieces]),
+                self._i64([pc[4] for pc in pieces]), F, self._i64(facet_off0s), S, self._i64(sub_off0s),
+                cvp(g_out.data_ptr()), fs, ss, offs, fstr, self._stream(),
+            )
+        )
+        return g_out
 
     def transform_contributions(self, src, layout, facet_off0s, subgrid_offs, out=None, rowmap=None, band=None, nsub=None):
         """K3 + K4a: ``out[f, b] = Fn * cfft_m(contribution_{f,b}, axis 0)`` rotated by the facet's ``off0``
@@ -788,6 +836,8 @@ class SwiftlyCoreHip:
                 self._stream(),
             )
         )
+        if compute_q:
+            self.k2_columns_issued += self.xM_yN_size
 
     def chain_chunk_streams(self, chain):
         """``swiftly_hip_chain_chunk_streams`` for the calling thread: the next chunked strided-axis transforms skip the
@@ -829,6 +879,7 @@ class SwiftlyCoreHip:
                 workspace.numel() * workspace.element_size() if workspace is not None else 0, self._stream(),
             )
         )
+        self.k2_columns_issued += W * self.xM_yN_size
         return out
 
     def wave_subgrid_side(self, G, facet_off0s, facet_off1s, sub_off0s, sub_off1s, subgrid_size, mask0, mask1, tmp, out,

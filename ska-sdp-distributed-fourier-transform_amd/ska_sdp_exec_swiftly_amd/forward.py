@@ -9,7 +9,7 @@ from functools import cached_property
 
 import numpy
 
-from . import _lib
+from . import _lib, slabs
 from .core_hip import band_range
 from .ingest import _FacetIngest, _mask_table
 from .prefetch import WavePrefetch, _knobs
@@ -71,6 +71,14 @@ class SwiftlyForward(WavePrefetch):
         # mode 2's {wave key: window}; the event behind K1, the one the side stream waited for, "a prefetched K2 has forked"
         self.BF_Fs_persist, self._band, self._axis1_mode, self._window_of = None, None, None, None
         self._bands_ready, self._side_waited, self._k2_chain_forked = None, None, False
+        self._bands_own = False  # the band buffers are this object's own K1 output (not injected through install_bands)
+        # column slabs of K2 (slabs.py): a cache of their own, so that the two slabs of the wave being served fit whatever
+        # ``lru_forward`` is
+        self._slab_lru = LRUCache(max(1, int(lru_forward)) + 1)
+        # slabs the cache pushed out while a planned wave that reads them has not been served yet (the wave at the wrap of
+        # the cyclic axis shares a slab with the first one of the walk), and {slab: waves served from its present copy}
+        self._slab_kept, self._slab_served = {}, {}
+        self._slab_rowmaps = {}
         self._prewindowed = False
         torch = _torch()
         # facet ingestion (host <-> device edge): device tensors are used in place; host (numpy) facets are
@@ -451,6 +459,7 @@ class SwiftlyForward(WavePrefetch):
                 ready = torch.cuda.Event()
                 ready.record(torch.cuda.current_stream(core.device))
             self.install_bands(bands, ready)
+            self._bands_own = True
         return self.BF_Fs_persist
 
     def set_band(self, band):
@@ -467,6 +476,7 @@ class SwiftlyForward(WavePrefetch):
         per wave (_prefetch_wave); without it every prefetched K2 waits for the caller's stream and none is chained."""
         self.BF_Fs_persist, self._bands_ready = bands, ready
         self._k2_chain_forked = False  # new band buffers: the next prefetched K2 forks behind K1 again
+        self._bands_own = False  # (_prepare_all_bands says otherwise for its own)
 
     def _wave_rows(self, off1):
         """(rowmap, n_rows) of the axis-0 rows the planned subgrids of wave ``off1`` read (None = all rows)."""
@@ -565,6 +575,94 @@ class SwiftlyForward(WavePrefetch):
         self.lru.set(("b", off1), (Q, rowmap))
         return Q, rowmap, n_rows, True
 
+    # -- K2 once per column slab of the padded axis instead of once per wave (slabs.py; DESIGN.md sections 3 and 4) --
+    @cached_property
+    def _slab_plan(self):
+        """what the plan needs of every slab (None: no plan, or sizes / offsets the slab grid does not fit)"""
+        core = self.core
+        N, yN, m = core.N, core.yN_size, core.xM_yN_size
+        if self._plan is None or yN & (yN - 1) or not slabs.supported(N, yN, m, self._planned_keys):
+            return None
+        return slabs.SlabPlan(N, yN, m, ((sg.off0, sg.off1) for sg in self._plan))
+
+    def _slabs_on(self):
+        """does the facet side of this object run K2 per slab?  Only the configuration the benchmark's timed pass runs:
+        planned complex64 waves keyed by off1 in the default order, on band buffers of this object's own K1
+        (``api._K2_SLABS`` / SWIFTLY_K2_SLABS=0 switches it off); everything else keeps K2 per wave."""
+        return bool(
+            _knobs()._K2_SLABS and self.wave_axis == 1 and self._plan is not None and self._bands_own
+            and self.dtype == _torch().complex64 and self._axis1() == 0 and self._slab_plan is not None
+        )
+
+    def _slab_rows(self, j):
+        """(rowmap, n_rows) of slab ``j``: the rows the planned subgrids of EVERY planned wave that meets the slab read"""
+        if j not in self._slab_rowmaps:
+            self._slab_rowmaps[j] = self.core.subgrid_column_rows(self._slab_plan.off0s[j])
+        return self._slab_rowmaps[j]
+
+    def _slab_has(self, j):
+        """is slab ``j`` cached?  (no effect on the recency order)"""
+        return ("q", j) in self._slab_lru._items or j in self._slab_kept  # pylint: disable=protected-access
+
+    def _slab_cached(self, j):
+        """cached slab ``j`` as ``(Q, rowmap, n_rows)``, or None"""
+        hit = self._slab_lru.get(("q", j))
+        if hit is None and j in self._slab_kept:
+            hit = self._slab_kept.pop(j)
+            self._slab_store(j, hit, fresh=False)
+        return hit
+
+    def _slab_store(self, j, hit, fresh=True):
+        """Slab ``j`` enters the cache.  The slab this pushes out is kept aside while a planned wave that reads it has not
+        been served from it yet -- as many such slabs as the cache holds, the oldest dropped first: a walk along the axis
+        then computes every slab once although its first and last wave share one; any other order only recomputes."""
+        if fresh:
+            self._slab_served[j] = set()
+        key, old = self._slab_lru.set(("q", j), hit)
+        if key is not None and set(self._slab_plan.users[key[1]]) - self._slab_served.get(key[1], set()):
+            kept = self._slab_kept
+            kept[key[1]] = old
+            while len(kept) > self._slab_lru.cache_size:
+                kept.pop(next(iter(kept)))
+
+    def _compute_slab(self, j, Q, rowmap):
+        """K2 of the planned positions of slab ``j`` into ``Q`` on the current stream; returns the number of native calls"""
+        plan = self._slab_plan
+        off0s = [cfg.off0 for cfg in self.facet_configs]
+        for first, count in plan.ranges[j]:
+            self.core.prepare_facet_columns_range(self.BF_Fs_persist, off0s, self._band, plan.off1(j), first, count, Q, rowmap)
+        return len(plan.ranges[j])
+
+    def _facet_side_slabs(self, sgs, g_out, g_layout):
+        """:py:meth:`_facet_side` with K2 per slab: the wave's one or two slabs are taken from the cache or the prefetch
+        (a missing one is computed on the current stream), the slabs of the next predicted waves go to the side stream,
+        and K3 + K4a read the window from the two pieces."""
+        core, off1 = self.core, sgs[0].off1
+        if int(off1) not in self._planned_keys:
+            raise ValueError(f"subgrid wave off1={off1} was not in the subgrid_configs plan")
+        torch = _torch()
+        wanted = self._slab_plan.pieces(off1)
+        self._check_slab_prediction([j for j, _, _ in wanted])
+        nxt = self._predict_next_waves(off1, _knobs()._PREFETCH_DEPTH)
+        pieces = []
+        for j, first, count in wanted:
+            hit = self._slab_hit(j)
+            if hit is None:
+                rowmap, n_rows = self._slab_rows(j)
+                Q = torch.empty((len(self.facet_configs), n_rows, core.xM_yN_size), dtype=self.dtype, device=core.device)
+                self._compute_slab(j, Q, rowmap)
+                hit = (Q, rowmap, n_rows)
+                self._slab_store(j, hit)
+            self._slab_served.setdefault(j, set()).add(int(off1))
+            pieces.append((*hit, first, count))
+        self._prefetch_slabs_of(nxt)  # (behind this wave's own K2, if it had to run, and before its K3)
+        if g_out is None:
+            m = core.xM_yN_size
+            g_out = torch.empty((len(self.facet_configs), len(sgs), m, m), dtype=self.dtype, device=core.device)
+        core.transform_contributions_pieces(pieces, [cfg.off0 for cfg in self.facet_configs], [sg.off0 for sg in sgs], g_out,
+                                            g_layout=g_layout)
+        return g_out
+
     def _facet_side(self, sgs, g_out=None, g_layout=None):
         """Facet side of one wave (K2 + K3 + K4a) in one native call: the blocks ``G[F, S, m, m]`` (returned), or placed by
         ``g_layout`` inside the flat buffer ``g_out`` (wave_blocks_into).  K2 of the next waves of the announced order
@@ -572,6 +670,8 @@ class SwiftlyForward(WavePrefetch):
         both callers (r6: the multi-GPU pass used to compute every K2 on the caller's stream, 41.4 against 35.5 ms at world 1)."""
         core, off1 = self.core, sgs[0].off1
         bands = self.prepare_all_facets()
+        if self._slabs_on():
+            return self._facet_side_slabs(sgs, g_out, g_layout)
         Q, rowmap, n_rows, compute = self._wave_Q(off1)
         nxt = self._predict_next_waves(off1, _knobs()._PREFETCH_DEPTH)
         if not compute:

@@ -35,6 +35,8 @@ def _env_int(name, default, lowest):
 PREFETCH_DEPTH_DEFAULT = _env_int("SWIFTLY_PREFETCH_DEPTH", 2, 1)
 # SWIFTLY_CHAIN_K2=0: every prefetched K2 forks its chunk streams behind the side stream again (A/B runs)
 CHAIN_K2_DEFAULT = os.environ.get("SWIFTLY_CHAIN_K2", "1") != "0"
+# SWIFTLY_K2_SLABS=0: K2 on every wave's whole window, not once per column slab of the padded axis (slabs.py; A/B runs)
+K2_SLABS_DEFAULT = os.environ.get("SWIFTLY_K2_SLABS", "1") != "0"
 
 
 _REARM_AFTER = 4  # requests in plan order after which a switched-off prefetch is switched on again
@@ -104,10 +106,13 @@ class WavePredictor:
 class WavePrefetch:
     """Side-stream K2 of the next planned waves: the in-flight side.  The host class provides ``_plan`` /
     ``_planned_keys``, ``lru``, ``core``, ``_wave_rows`` / ``_k2_source`` / ``_axis1`` and the band-lifetime fields
-    ``_bands_ready`` / ``_side_waited`` / ``_k2_chain_forked``, which it resets when band buffers are installed."""
+    ``_bands_ready`` / ``_side_waited`` / ``_k2_chain_forked``, which it resets when band buffers are installed; for the
+    slab form of K2 also ``_slab_plan`` / ``_slab_rows`` / ``_compute_slab`` and the slab cache ``_slab_has`` / ``_slab_cached``
+    / ``_slab_store``."""
 
     def __init__(self):
         self._prefetched = {}  # K2s in flight: {off1: (Q, rowmap, done event)}
+        self._prefetched_slabs = {}  # the same for column slabs: {slab: (Q, rowmap, done event, n_rows)}
         self._prefetch_parked = []  # mispredicted ones, kept referenced until their done events have fired
         self.prefetch_issued = 0  # K2s enqueued on the side stream so far
 
@@ -184,6 +189,28 @@ class WavePrefetch:
         if off1 is None or int(off1) in pending or self.lru.get(("b", off1)) is not None:
             return
         rowmap, n_rows = self._wave_rows(off1)
+        side, chain = self._side_behind_bands()
+        with torch.cuda.stream(side):
+            Q = torch.empty((len(self.facet_configs), n_rows, core.xM_yN_size), dtype=self.dtype, device=core.device)
+            src, band = self._k2_source(off1)
+            core.chain_chunk_streams(chain)
+            try:
+                core.prepare_facet_columns(
+                    src, [cfg.off0 for cfg in self.facet_configs], band, off1, rowmap, n_rows, out=Q
+                )
+            finally:
+                core.chain_chunk_streams(False)
+            done = torch.cuda.Event()
+            done.record(side)
+        self._k2_chain_forked = True
+        pending[int(off1)] = (Q, rowmap, done)
+        self.prefetch_issued += 1
+
+    def _side_behind_bands(self):
+        """``(side stream, chain)``: the core's side stream put in order behind the band buffers, and whether the next K2
+        on it may run its chunk streams on from the previous one (see :py:meth:`_prefetch_wave`)"""
+        torch = _torch()
+        core = self.core
         side = core.side_stream()
         ready = self._bands_ready
         if _knobs()._PREFETCH_DEPTH >= 2 and ready is not None:
@@ -202,21 +229,65 @@ class WavePrefetch:
         # stream -- its chunk streams must fork behind them every time)
         chain = (_knobs()._PREFETCH_DEPTH >= 2 and ready is not None and _knobs()._CHAIN_K2
                  and self._k2_chain_forked and self._axis1() != 1)
+        return side, chain
+
+    # -- the slab form (slabs.py): the same side-stream chain, issued per column slab instead of per wave ---------------
+    def _slab_hit(self, j):
+        """cached slab ``j`` as ``(Q, rowmap, n_rows)``, a prefetched one taken over first (the current stream waits for
+        its K2; hand-over as in :py:meth:`_take_prefetched`); None when it has to be computed"""
+        pf = self._prefetched_slabs.pop(j, None)
+        if pf is not None and not self._slab_has(j):
+            cur = _torch().cuda.current_stream(self.core.device)
+            cur.wait_event(pf[2])
+            pf[0].record_stream(cur)
+            self._slab_store(j, (pf[0], pf[1], pf[3]))
+        return self._slab_cached(j)
+
+    def _check_slab_prediction(self, needed):
+        """the misprediction rule of :py:meth:`_take_prefetched` for a wave that needs the slabs ``needed``: when one of
+        them is neither cached nor in flight although slabs are in flight, the guess was wrong -- the slabs in flight that
+        this wave does not use are dropped, and two such misses in a row switch the prefetch off"""
+        pending = self._prefetched_slabs
+        if not pending:
+            return
+        if all(j in pending or self._slab_has(j) for j in needed):
+            self._predictor.hit()
+            return
+        parked = self._prefetch_parked  # (kept referenced until their K2 has run, as the waves' blocks are)
+        parked[:] = [p for p in parked if p[2] is not None and not p[2].query()]
+        for j in [j for j in pending if j not in needed]:
+            parked.append(pending.pop(j))
+        if self._predictor.miss():
+            log.info("SwiftlyForward: two mispredicted waves in a row -- planned-wave prefetch switched off "
+                     "until %d requests have followed the plan again", _REARM_AFTER)
+
+    def _prefetch_slab(self, j):
+        """K2 of slab ``j`` on the side stream (:py:meth:`_prefetch_wave` for a slab), unless cached or in flight"""
+        torch = _torch()
+        core = self.core
+        pending = self._prefetched_slabs
+        if j in pending or self._slab_has(j):
+            return
+        rowmap, n_rows = self._slab_rows(j)
+        side, chain = self._side_behind_bands()
         with torch.cuda.stream(side):
             Q = torch.empty((len(self.facet_configs), n_rows, core.xM_yN_size), dtype=self.dtype, device=core.device)
-            src, band = self._k2_source(off1)
             core.chain_chunk_streams(chain)
             try:
-                core.prepare_facet_columns(
-                    src, [cfg.off0 for cfg in self.facet_configs], band, off1, rowmap, n_rows, out=Q
-                )
+                calls = self._compute_slab(j, Q, rowmap)
             finally:
                 core.chain_chunk_streams(False)
             done = torch.cuda.Event()
             done.record(side)
         self._k2_chain_forked = True
-        pending[int(off1)] = (Q, rowmap, done)
-        self.prefetch_issued += 1
+        pending[j] = (Q, rowmap, done, n_rows)
+        self.prefetch_issued += calls
+
+    def _prefetch_slabs_of(self, waves):
+        """the slabs the predicted ``waves`` need, in the order the walk meets them"""
+        for off1 in waves:
+            for j, _, _ in self._slab_plan.pieces(off1):
+                self._prefetch_slab(j)
 
     def _prefetch_waves(self, waves):
         """:py:meth:`_prefetch_wave` for the predicted waves, nearest first, at most SWIFTLY_PREFETCH_DEPTH in flight"""
