@@ -373,9 +373,9 @@ static int run_modcopy(swiftly_hip* h, const void* in, int64_t rows, int64_t in_
         const int nb = (int)std::min<int64_t>(kMaxBatch, bt.n - b0);
         ModTab tab;
         for (int b = 0; b < nb; b++) {
-            const int64_t s = floordiv(bt.off_of(b0 + b, subgrid_off) * h->yN, h->N);
-            tab.s_m[b] = pmod(s, m);
-            tab.base_s[b] = pmod(yN / 2 - m / 2 + s, yN);
+            const Window w = window_of(*h, bt.off_of(b0 + b, subgrid_off));
+            tab.s_m[b] = pmod(w.s, m);
+            tab.base_s[b] = w.base;
         }
         dim3 grid((unsigned)((total + 255) / 256), nb);
         hipLaunchKernelGGL((modcopy_kernel<R, SCATTER>), grid, dim3(256), 0, st,
@@ -388,11 +388,6 @@ static int run_modcopy(swiftly_hip* h, const void* in, int64_t rows, int64_t in_
 }
 
 // ---------------------------------------------------------------------------
-template <typename R>
-static AxisMap<R> identity_map(int n) {
-    return AxisMap<R>{0, n, 0, n, nullptr, nullptr};
-}
-
 template <typename R>
 static int launch_checked(int logn, const RowsArgs<R>& a, const OffTab& tab, hipStream_t st) {
     return launch_status(launch_fft_rows(logn, a, tab, st));
@@ -409,23 +404,19 @@ static bool try_col_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
     // all element offsets inside one batch item are 32 bit
     if (n * (uint64_t)a.in_cs + W >= lim || n * (uint64_t)a.out_cs + W >= lim || n * W >= lim) return false;
     const int nb = a.nbatch > 0 ? a.nbatch : 1;
-    ColPassArgs c;
-    std::memset(&c, 0, sizeof c);
+    ColPassArgs c = col_pass_args(Map{a.ld.a, a.ld.len, a.ld.c, a.ld.mod}, Map{a.st.a, a.st.len, a.st.c, a.st.mod});
     c.ncols = a.nrows;
     c.full_logn = logn;
     c.in = a.in; c.out = a.out;
     c.in_pitch = a.in_cs; c.out_pitch = a.out_cs;
     c.in_bs = a.in_bs;
     c.out_bs = a.out_bs;
-    c.ld_a = a.ld.a; c.ld_len = a.ld.len; c.ld_c = a.ld.c; c.ld_mod = a.ld.mod;
     c.ld_win = a.ld.win; c.ld_win2 = a.ld.win2;
-    c.st_a = a.st.a; c.st_len = a.st.len; c.st_c = a.st.c; c.st_mod = a.st.mod;
     c.st_win = a.st.win; c.st_win2 = a.st.win2; c.st_win_bs = a.st_win_bs;
     c.st_rowmap = a.st_rowmap;
     c.col_win = a.row_win;
     c.scale = a.scale;
     c.conj_ld = a.conj_ld; c.conj_st = a.conj_st; c.accumulate = a.accumulate;
-    c.ld_mul = c.st_mul = 1;
     // per-item map offsets (OffTab) -> per-subgrid tables of the column pass (batch item z = b)
     ColZ cz = plain_colz();
     if (tab.use) {
@@ -796,8 +787,8 @@ static int run_rows_bluestein(swiftly_hip* h, int64_t n, RowsArgs<R>& a, const O
         f.in_rs = f.out_rs = L;
         f.in_cs = f.out_cs = 1;
         f.nrows = (int)rows_total;
-        f.ld = identity_map<R>((int)L);
-        f.st = identity_map<R>((int)L);
+        f.ld = axis_map<R>(whole(L));
+        f.st = axis_map<R>(whole(L));
         f.scale = inverse ? (R)(1.0 / (double)L) : (R)1;
         f.conj_ld = f.conj_st = inverse ? 1 : 0;
         f.nbatch = 1;
@@ -960,23 +951,22 @@ static int do_prepare_facet(swiftly_hip* h, const void* in, int64_t rows, int64_
                             void* out, int64_t out_rs, int64_t out_cs, int64_t off, int64_t row_gather_off,
                             const int32_t* out_rowmap, const int32_t* in_rowmap, int fold_other, int no_window,
                             hipStream_t st) {
-    const int yN = (int)h->yN, m = (int)h->m;
+    const int yN = (int)h->yN;
     RowsArgs<R> a;
     fill_io(a, in, rows, in_rs, in_cs, out, out_rs, out_cs);
-    const int lo = yN / 2 - (int)(yB / 2);
-    a.ld = AxisMap<R>{pmod(-(off + lo), yN), (int)yB, 0, (int)yB, invp<R>(h) + lo, nullptr};
-    a.st = identity_map<R>(yN);
+    a.ld = axis_map<R>(facet_in_padded_facet(*h, yB, off), invp<R>(h) + facet_lo(*h, yB));
+    a.st = axis_map<R>(whole(yN));
     a.conj_ld = a.conj_st = 1;
     a.scale = (R)(1.0 / yN);
     a.st_rowmap = out_rowmap;
     a.in_rowmap = in_rowmap;
     if (no_window) a.ld.win = nullptr;
-    if (fold_other) a.row_win = invp<R>(h) + (yN / 2 - (int)(rows / 2));  // the rows of this call are the other axis
+    if (fold_other) a.row_win = invp<R>(h) + facet_lo(*h, rows);  // the rows of this call are the other axis
     if (row_gather_off != INT64_MIN) {
-        const int64_t s = floordiv(row_gather_off * h->yN, h->N);
-        a.rm_mod = m;
-        a.rm_inner = pmod(-s, m);
-        a.rm_outer = pmod(yN / 2 - m / 2 + s, yN);
+        const Window w = window_of(*h, row_gather_off);
+        a.rm_mod = (int)h->m;
+        a.rm_inner = w.rot;
+        a.rm_outer = w.base;
         a.rm_full = yN;
     }
     return run_rows(h, h->yN, h->log_yN, a, Batch{}, 0, kNoFill, st);
@@ -985,21 +975,15 @@ static int do_prepare_facet(swiftly_hip* h, const void* in, int64_t rows, int64_
 template <typename R>
 static int do_add_to_subgrid(swiftly_hip* h, const void* in, int64_t rows, int64_t in_rs, int64_t in_cs, void* out,
                              int64_t out_rs, int64_t out_cs, int64_t off, const Batch& bt, hipStream_t st) {
-    const int m = (int)h->m, xM = (int)h->xM;
-    auto maps = [&](int64_t o, int& a_, int& c_) {
-        const int64_t sp = floordiv(o * h->xM, h->N);
-        a_ = pmod(-sp, m);
-        c_ = pmod(xM / 2 - m / 2 + sp, xM);
-    };
     RowsArgs<R> a;
     fill_io(a, in, rows, in_rs, in_cs, out, out_rs, out_cs);
-    a.ld = identity_map<R>(m);
-    int a0, c0;
-    maps(off, a0, c0);
-    a.st = AxisMap<R>{a0, m, c0, xM, fnwin<R>(h), nullptr};
+    a.ld = axis_map<R>(whole(h->m));
+    a.st = axis_map<R>(contribution_in_padded_subgrid(*h, off), fnwin<R>(h));
     a.accumulate = 1;
-    return run_rows(h, h->m, h->log_m, a, bt, 4 | 8,
-                    [&](int64_t gb, int b, OffTab& t) { maps(bt.offs[gb], t.st_a[b], t.st_c[b]); }, st);
+    return run_rows(h, h->m, h->log_m, a, bt, 4 | 8, [&](int64_t gb, int b, OffTab& t) {
+        const Map g = contribution_in_padded_subgrid(*h, bt.offs[gb]);
+        t.st_a[b] = g.a; t.st_c[b] = g.c;
+    }, st);
 }
 
 template <typename R>
@@ -1009,12 +993,12 @@ static int do_finish_subgrid(swiftly_hip* h, const void* in, int64_t rows, int64
     const int xM = (int)h->xM;
     RowsArgs<R> a;
     fill_io(a, in, rows, in_rs, in_cs, out, out_rs, out_cs);
-    a.ld = identity_map<R>(xM);
-    a.st = AxisMap<R>{pmod(-(xM / 2 - xA / 2 + off), xM), (int)xA, 0, (int)xA, (const R*)mask, nullptr};
+    a.ld = axis_map<R>(whole(xM));
+    a.st = axis_map<R>(subgrid_in_padded_subgrid(*h, xA, off), (const R*)mask);
     a.conj_ld = a.conj_st = 1;
     a.scale = (R)(1.0 / xM);
     return run_rows(h, h->xM, h->log_xM, a, bt, 4,
-                    [&](int64_t gb, int b, OffTab& t) { t.st_a[b] = pmod(-(xM / 2 - xA / 2 + bt.offs[gb]), xM); }, st);
+                    [&](int64_t gb, int b, OffTab& t) { t.st_a[b] = subgrid_in_padded_subgrid(*h, xA, bt.offs[gb]).a; }, st);
 }
 
 template <typename R>
@@ -1024,32 +1008,26 @@ static int do_prepare_subgrid(swiftly_hip* h, const void* in, int64_t rows, int6
     const int xM = (int)h->xM;
     RowsArgs<R> a;
     fill_io(a, in, rows, in_rs, in_cs, out, out_rs, out_cs);
-    a.ld = AxisMap<R>{pmod(-(xM / 2 - xA / 2 + off), xM), (int)xA, 0, (int)xA, nullptr, nullptr};
-    a.st = identity_map<R>(xM);
+    a.ld = axis_map<R>(subgrid_in_padded_subgrid(*h, xA, off));
+    a.st = axis_map<R>(whole(xM));
     return run_rows(h, h->xM, h->log_xM, a, bt, 1,
-                    [&](int64_t gb, int b, OffTab& t) { t.ld_a[b] = pmod(-(xM / 2 - xA / 2 + bt.offs[gb]), xM); }, st);
+                    [&](int64_t gb, int b, OffTab& t) { t.ld_a[b] = subgrid_in_padded_subgrid(*h, xA, bt.offs[gb]).a; }, st);
 }
 
 template <typename R>
 static int do_extract_from_subgrid(swiftly_hip* h, const void* in, int64_t rows, int64_t in_rs, int64_t in_cs,
                                    void* out, int64_t out_rs, int64_t out_cs, int64_t off, const Batch& bt,
                                    hipStream_t st) {
-    const int m = (int)h->m, xM = (int)h->xM;
-    auto maps = [&](int64_t o, int& a_, int& c_) {
-        const int64_t sp = floordiv(o * h->xM, h->N);
-        a_ = pmod(-sp, m);
-        c_ = pmod(xM / 2 - m / 2 + sp, xM);
-    };
     RowsArgs<R> a;
     fill_io(a, in, rows, in_rs, in_cs, out, out_rs, out_cs);
-    int a0, c0;
-    maps(off, a0, c0);
-    a.ld = AxisMap<R>{a0, m, c0, xM, fnwin<R>(h), nullptr};
-    a.st = identity_map<R>(m);
+    a.ld = axis_map<R>(contribution_in_padded_subgrid(*h, off), fnwin<R>(h));
+    a.st = axis_map<R>(whole(h->m));
     a.conj_ld = a.conj_st = 1;
-    a.scale = (R)(1.0 / m);
-    return run_rows(h, h->m, h->log_m, a, bt, 1 | 2,
-                    [&](int64_t gb, int b, OffTab& t) { maps(bt.offs[gb], t.ld_a[b], t.ld_c[b]); }, st);
+    a.scale = (R)(1.0 / (int)h->m);
+    return run_rows(h, h->m, h->log_m, a, bt, 1 | 2, [&](int64_t gb, int b, OffTab& t) {
+        const Map g = contribution_in_padded_subgrid(*h, bt.offs[gb]);
+        t.ld_a[b] = g.a; t.ld_c[b] = g.c;
+    }, st);
 }
 
 template <typename R>
@@ -1057,16 +1035,15 @@ static int do_finish_facet(swiftly_hip* h, const void* in, int64_t rows, int64_t
                            int64_t out_rs, int64_t out_cs, int64_t off, int64_t yB, const void* mask, const Batch& bt,
                            hipStream_t st, int64_t band_start = 0, int64_t band_len = -1) {
     const int yN = (int)h->yN;
-    const int lo = yN / 2 - (int)(yB / 2);
     RowsArgs<R> a;
     fill_io(a, in, rows, in_rs, in_cs, out, out_rs, out_cs);
-    a.ld = identity_map<R>(yN);
+    a.ld = axis_map<R>(whole(yN));
     // band input: element d of a row is column (band_start + d) mod yN of the padded facet, the rest is zero
-    if (band_len >= 0) a.ld = AxisMap<R>{pmod(-band_start, yN), (int)band_len, 0, (int)band_len, nullptr, nullptr};
+    if (band_len >= 0) a.ld = axis_map<R>(band_as_load_map(*h, band_start, band_len));
     // mask goes to `win` (it is the per-item one), the PSWF window to `win2`
-    a.st = AxisMap<R>{pmod(-(lo + off), yN), (int)yB, 0, (int)yB, (const R*)mask, invp<R>(h) + lo};
+    a.st = axis_map<R>(facet_in_padded_facet(*h, yB, off), (const R*)mask, invp<R>(h) + facet_lo(*h, yB));
     return run_rows(h, h->yN, h->log_yN, a, bt, 4,
-                    [&](int64_t gb, int b, OffTab& t) { t.st_a[b] = pmod(-(lo + bt.offs[gb]), yN); }, st);
+                    [&](int64_t gb, int b, OffTab& t) { t.st_a[b] = facet_in_padded_facet(*h, yB, bt.offs[gb]).a; }, st);
 }
 
 extern "C" {
@@ -1307,7 +1284,7 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
         return fail(SWIFTLY_ERR_PARAM, "rows [%lld, +%lld) are not inside a facet of %lld rows", (long long)other_axis_row0,
                     (long long)rows, (long long)other_axis_size);
     DeviceGuard device_guard_(h->device);
-    if (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     CHECK_FACET_SIZE();
     const int yN = (int)h->yN;
     if (dtype == SWIFTLY_C128) {
@@ -1329,8 +1306,7 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
     if (!mixed_yN && (h->log_yN < kMinLogN || h->log_yN > kBandMaxLogYN))
         return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: padded facet size %d not supported (power of two 8 .. 65536, or Q * 2^k with Q = 3, 5, 7, 9)", yN);
     if (rows < 0 || rows > 0x7fffffff) return fail(SWIFTLY_ERR_PARAM, "bad row count");
-    if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN)
-        return fail(SWIFTLY_ERR_PARAM, "band [%lld, +%lld) is not a cyclic range of [0, %d)", (long long)band_start, (long long)band_len, yN);
+    CHECK_BAND();
     if (fold_other_axis_window && (other_axis_size <= 0 || other_axis_size >= h->yN))
         return fail(SWIFTLY_ERR_PARAM, "other-axis facet size %lld must be in [1, yN_size - 1]", (long long)other_axis_size);
     if (rows == 0) return 0;
@@ -1343,18 +1319,18 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
         return do_prepare_facet<float>(h, in, rows, facet_size, in_row_stride, 1, out, out_row_stride, 1, facet_off, INT64_MIN,
                                        nullptr, nullptr, fold_other_axis_window, 0, (hipStream_t)stream);
     }
-    const int lo = yN / 2 - (int)(facet_size / 2);
+    const Map facet = facet_in_padded_facet(*h, facet_size, facet_off);
     RowPassArgs r;
     std::memset(&r, 0, sizeof r);
     r.in = (const cx<float>*)in; r.out = (cx<float>*)out;
     r.in_pitch = in_row_stride; r.out_pitch = out_row_stride;
     r.nrows = (int)rows;
-    r.ld_a = pmod(-(facet_off + lo), yN); r.ld_len = (int)facet_size; r.ld_c = 0; r.ld_mod = (int)facet_size;
-    r.ld_win = h->invp_f + lo;
+    r.ld_a = facet.a; r.ld_len = facet.len; r.ld_c = facet.c; r.ld_mod = facet.mod;
+    r.ld_win = h->invp_f + facet_lo(*h, facet_size);
     r.st_len = yN; r.st_mod = yN;
     r.scale = (float)(1.0 / yN);
     r.conj_ld = r.conj_st = 1;
-    r.row_win = fold_other_axis_window ? h->invp_f + (yN / 2 - (int)(other_axis_size / 2) + (int)other_axis_row0) : nullptr;
+    r.row_win = fold_other_axis_window ? h->invp_f + (facet_lo(*h, other_axis_size) + (int)other_axis_row0) : nullptr;
     r.band_start = (int)band_start; r.band_len = (int)band_len; r.band_half = (int)band_half_columns(band_len);
     const cx<float>* twh = twiddles<float>(h, h->log_yN - 1);
     const cx<float>* twf = twiddles<float>(h, h->log_yN);
@@ -1363,7 +1339,7 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
         r.win_full = 1;
         r.win_pitch = win_full;  // (the flag carries the window stride)
         r.win_d = win_d; r.nwin = (int)nwin; r.win_logm = h->log_m;
-        r.win_sp = pmod(floordiv(facet_off * h->xM, h->N), (int)h->m);
+        r.win_sp = pmod(facet_shift(*h, facet_off), h->m);
         r.win_fn = h->fn_f;
         r.win_tw_m = twiddles<float>(h, h->log_m);
         r.win_twc_m = h->log_m >= 6 ? compact_twiddles(h, h->log_m, h->log_m - 6) : nullptr;
@@ -1411,9 +1387,7 @@ int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, i
     // through do_finish_facet<double>, 64 .. 32768 points)
     if (const std::string why = why_not_backward_band(*h, dtype, true); !why.empty())
         return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band: %s", why.c_str());
-    if (band_len <= 0 || band_len > h->yN || band_start < 0 || band_start >= h->yN)
-        return fail(SWIFTLY_ERR_PARAM, "band [%lld, +%lld) is not a cyclic range of [0, %lld)", (long long)band_start,
-                    (long long)band_len, (long long)h->yN);
+    CHECK_BAND();
     Batch bt{1, 0, 0, nullptr, 0};
     return DISPATCH(do_finish_facet, h, in, rows, in_row_stride, in_cs, out, out_row_stride, out_cs, facet_off, facet_size,
                     mask, bt, (hipStream_t)stream, band_start, band_len);

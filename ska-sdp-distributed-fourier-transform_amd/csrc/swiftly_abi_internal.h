@@ -2,7 +2,9 @@
 // batch forms; swiftly_abi_coltransform.hip: the strided-axis transform, col_transform; swiftly_abi_pipeline.hip: the
 // fused / per-wave entry points of the streaming classes; swiftly_abi_util.hip: device memory, stream and diagnostic
 // helpers, and the table of kernels launched with dynamic LDS (swiftly_launch.h), whose per-device attributes
-// swiftly_hip_create sets from it; swiftly_abi_sources.hip: point-source truths and RMSE checks).  Not installed:
+// swiftly_hip_create sets from it; swiftly_abi_sources.hip: point-source truths and RMSE checks).  Two headers of pure host
+// functions of the sizes stand beside it: swiftly_caps.h (which kernels and pipelines exist) and swiftly_geometry.h (how an
+// offset becomes the integers of an index map); the launch sequences ask them and restate neither.  Not installed:
 // include/swiftly_hip.h is the public header.
 #pragma once
 
@@ -21,6 +23,7 @@
 
 #include "../../include/swiftly_hip.h"
 #include "swiftly_colpass.h"
+#include "swiftly_geometry.h"
 #include "swiftly_launch.h"
 #include "swiftly_rowpass.h"
 #include "swiftly_sumfinish.h"
@@ -75,17 +78,6 @@ struct ScratchLease {
         return (!rc && e != hipSuccess) ? fail(SWIFTLY_ERR_HIP, "hipFreeAsync: %s", hipGetErrorString(e)) : rc;
     }
 };
-
-static inline int64_t floordiv(int64_t a, int64_t b) {
-    int64_t q = a / b;
-    if ((a % b != 0) && ((a < 0) != (b < 0))) q--;
-    return q;
-}
-static inline int pmod(int64_t a, int64_t n) {
-    int64_t r = a % n;
-    if (r < 0) r += n;
-    return (int)r;
-}
 
 struct swiftly_hip : Sizes {  // N, yN, xM, m and log_yN, log_xM, log_m (swiftly_caps.h)
     double W;
@@ -215,15 +207,29 @@ static inline cx<float>* cx_at(void* p, int64_t k, bool c128) {
 }
 // column-tile passes (swiftly_abi_coltransform.hip)
 ColZ plain_colz();
-// single-pass launch of length 2^logn: float64 arithmetic when the handle asks for it and the instance exists
-inline void set_col_precision(const swiftly_hip* h, ColPassArgs& c, int logn) {
-    c.f64 = 0;
-    if (!h->col_f64 || !(h->col_f64_stages & 4) || !col_pass_f64_supported(logn) || c.gs) return;
+// single-pass launch of length 2^logn: float64 arithmetic when the handle asks for it and the instance exists; complex128
+// storage always takes that instance
+inline int set_col_precision(const swiftly_hip* h, ColPassArgs& c, int logn, bool c128) {
     const cx<double>* t = twiddles<double>(h, logn);
-    if (!t) return;
-    c.f64 = 1;
-    c.twd = t;
-    c.twd_full = t;
+    if (c128 && !t) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle table");
+    c.c128 = c128 ? 1 : 0;
+    c.f64 = t && (c128 || (h->col_f64 && (h->col_f64_stages & 4) && col_pass_f64_supported(logn) && !c.gs)) ? 1 : 0;
+    if (c.f64) c.twd = c.twd_full = t;
+    return 0;
+}
+// a map of swiftly_geometry.h with its windows, for the row kernels
+template <typename R>
+inline AxisMap<R> axis_map(const Map& g, const R* win = nullptr, const R* win2 = nullptr) {
+    return AxisMap<R>{g.a, g.len, g.c, g.mod, win, win2};
+}
+// the argument block of a plain (un-decomposed) column pass: everything zero but the unit multipliers and the two maps
+inline ColPassArgs col_pass_args(const Map& ld, const Map& st) {
+    ColPassArgs c;
+    std::memset(&c, 0, sizeof c);
+    c.ld_mul = c.st_mul = 1;
+    c.ld_a = ld.a; c.ld_len = ld.len; c.ld_c = ld.c; c.ld_mod = ld.mod;
+    c.st_a = st.a; c.st_len = st.len; c.st_c = st.c; c.st_mod = st.mod;
+    return c;
 }
 int launch_col_checked(int lg, int mode, const ColPassArgs& args, const ColZ& cz, int outer, int nb, hipStream_t st);
 // scratch handed down by an entry point for the duration of one ABI call on this host thread (see col_transform)
@@ -240,7 +246,6 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
 template <class Args>
 static inline void fill_facet_groups(Args& a, const swiftly_hip* h, int64_t nfacets, const int64_t* facet_off0s,
                                      const int64_t* facet_off1s) {
-    const int xM = (int)h->xM, m = (int)h->m;
     std::vector<int> order((size_t)nfacets);
     for (int f = 0; f < nfacets; f++) order[(size_t)f] = f;
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return facet_off1s[x] < facet_off1s[y]; });
@@ -249,12 +254,11 @@ static inline void fill_facet_groups(Args& a, const swiftly_hip* h, int64_t nfac
         const int f = order[(size_t)n];
         if (n == 0 || facet_off1s[f] != facet_off1s[order[(size_t)n - 1]]) {
             a.gstart[a.ngroups] = n;
-            a.gsp1[a.ngroups] = (int)floordiv(facet_off1s[f] * h->xM, h->N);
+            a.gsp1[a.ngroups] = (int)facet_shift(*h, facet_off1s[f]);
             a.ngroups++;
         }
         a.fidx[n] = f;
-        const int sp0 = (int)floordiv(facet_off0s[f] * h->xM, h->N);
-        a.base0[n] = pmod(xM / 2 - m / 2 + sp0, xM);  // first padded-subgrid row the facet contributes to
+        a.base0[n] = contribution_in_padded_subgrid(*h, facet_off0s[f]).c;  // first padded-subgrid row the facet contributes to
     }
     a.gstart[a.ngroups] = (int)nfacets;
 }
@@ -265,8 +269,7 @@ static inline void fill_group_rounds(SumFinishFacetArgs& a, const swiftly_hip* h
     const int xM = (int)h->xM, m = (int)h->m;
     std::vector<std::vector<int>> rounds;
     auto overlap = [&](int g1, int g2) {
-        const int s1 = pmod(xM / 2 - m / 2 + a.gsp1[g1], xM), s2 = pmod(xM / 2 - m / 2 + a.gsp1[g2], xM);
-        const int d = pmod(s2 - s1, xM);
+        const int d = pmod(placement_start(*h, a.gsp1[g2]) - placement_start(*h, a.gsp1[g1]), xM);
         return d < m || xM - d < m;
     };
     for (int g = 0; g < a.ngroups; g++) {
@@ -288,12 +291,31 @@ static inline void fill_group_rounds(SumFinishFacetArgs& a, const swiftly_hip* h
     a.rstart[rounds.size()] = k;
 }
 
+// The Fn, twiddle and compact twiddle tables of an argument block of the sum_finish family (swiftly_sumfinish.h), through
+// pointers to the fields the block has (null: it has none, or its instances read none).  complex128: the double Fn and
+// plain double twiddle tables, behind the float pointer types; the compact copies exist in float only.  m-point
+// transforms run 64 lanes each, rows 64 lanes and 256 from 4096 points on.
+static inline int fill_sum_finish_tables(const swiftly_hip* h, bool c128, const float** fn, const cx<float>** tw_m,
+                                         const cx<float>** tw_x, const cx<float>** twc_m, const cx<float>** twc_x) {
+    *fn = c128 ? (const float*)h->fn_d : h->fn_f;
+    *tw_m = c128 ? (const cx<float>*)twiddles<double>(h, h->log_m) : twiddles<float>(h, h->log_m);
+    if (tw_x) *tw_x = c128 ? (const cx<float>*)twiddles<double>(h, h->log_xM) : twiddles<float>(h, h->log_xM);
+    if (!*fn || !*tw_m || (tw_x && !*tw_x))
+        return fail(SWIFTLY_ERR_HIP, c128 ? "internal: missing double tables" : "internal: missing twiddle tables");
+    if (twc_m) *twc_m = compact_twiddles(h, h->log_m, h->log_m - 6);
+    if (twc_x) *twc_x = compact_twiddles(h, h->log_xM, h->log_xM - (h->log_xM >= 12 ? 8 : 6));
+    if ((twc_m && !*twc_m) || (twc_x && !*twc_x)) return fail(SWIFTLY_ERR_HIP, "internal: missing compact twiddle tables");
+    return 0;
+}
+
+#define CHECK_DTYPE() \
+    if (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
 #define CHECK_COMMON()                                                                       \
     if (!h || !in || !out) return fail(SWIFTLY_ERR_PARAM, "null argument");                  \
     DeviceGuard device_guard_(h->device);                                                    \
     if (device_guard_.rc) return fail(SWIFTLY_ERR_HIP, "hipSetDevice(%d) failed", h->device); \
     if (rows < 0) return fail(SWIFTLY_ERR_PARAM, "negative row count");                      \
-    if (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype); \
+    CHECK_DTYPE()                                                                            \
     if (in_cs < 0 || out_cs < 0 || in_cs >= (int64_t(1) << 32) || out_cs >= (int64_t(1) << 32)) \
         return fail(SWIFTLY_ERR_PARAM, "column strides must be in [0, 2^32)");                 \
     if (rows > 0x7fffffff) return fail(SWIFTLY_ERR_PARAM, "too many rows");
@@ -314,7 +336,14 @@ static inline void fill_group_rounds(SumFinishFacetArgs& a, const swiftly_hip* h
     if (subgrid_size <= 0 || subgrid_size > h->xM)                                                                \
         return fail(SWIFTLY_ERR_PARAM, "subgrid size %lld must be in [1, xM_size = %lld]", (long long)subgrid_size, \
                     (long long)h->xM);
-
+// (band_start, band_len) of the call is a cyclic range of the padded facet axis (band_valid, swiftly_geometry.h)
+#define CHECK_BAND()                                                                                              \
+    if (!band_valid(h->yN, band_start, band_len))                                                                 \
+        return fail(SWIFTLY_ERR_PARAM, "band [%lld, +%lld) is not a cyclic range of [0, %lld)", (long long)band_start, \
+                    (long long)band_len, (long long)h->yN);
+// every element offset inside one batch item fits 32 bits (offsets_fit_32, swiftly_geometry.h)
+#define CHECK_OFFSETS_32(fit) \
+    if (!(fit)) return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");
 
 // ---------------------------------------------------------------------------------------------------------
 // band buffers of the contiguous-axis-first pipeline

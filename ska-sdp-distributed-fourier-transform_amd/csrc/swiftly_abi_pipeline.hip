@@ -53,18 +53,15 @@ int swiftly_hip_sum_finish_rows(swiftly_hip_t* h, int dtype, const void* in, int
     a.nrows = xM;
     a.ngroups = (int)ngroups;
     a.xA = xA;
-    for (int g = 0; g < ngroups; g++) a.sp[g] = (int)floordiv(group_facet_offs[g] * h->xM, h->N);
-    a.fn = h->fn_f;
+    for (int g = 0; g < ngroups; g++) a.sp[g] = (int)facet_shift(*h, group_facet_offs[g]);
     a.mask_bs = mask ? mask_batch_stride : 0;
-    a.tw_m = twiddles<float>(h, h->log_m);
-    a.tw_x = twiddles<float>(h, h->log_xM);
-    if (!a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
+    if (int rc = fill_sum_finish_tables(h, false, &a.fn, &a.tw_m, &a.tw_x, nullptr, nullptr)) return rc;
     for (int64_t b0 = 0; b0 < nbatch; b0 += kSumFinishMaxBatch) {
         const int nb = (int)std::min<int64_t>(kSumFinishMaxBatch, nbatch - b0);
         a.in = (const cx<float>*)in + b0 * in_batch_stride;
         a.out = (cx<float>*)out + b0 * out_batch_stride;
         a.mask = mask ? (const float*)mask + b0 * mask_batch_stride : nullptr;
-        for (int b = 0; b < nb; b++) a.st_a[b] = pmod(-(xM / 2 - xA / 2 + subgrid_offs[b0 + b]), xM);
+        for (int b = 0; b < nb; b++) a.st_a[b] = subgrid_in_padded_subgrid(*h, xA, subgrid_offs[b0 + b]).a;
         if (int rc = launch_status(launch_sum_finish_rows(h->log_m, h->log_xM, a, nb, (hipStream_t)stream))) return rc;
     }
     return 0;
@@ -81,19 +78,12 @@ int swiftly_hip_add_to_subgrid_from_columns(swiftly_hip_t* h, int dtype, const v
     if (h->log_m < kColPassMinLog || h->log_m > kColPassMaxLog || h->log_yN < 0)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "add_to_subgrid_from_columns: contribution size %d not supported", m);
     if (nfacets <= 0 || nsub <= 0) return 0;
-    if ((uint64_t)m * (uint64_t)in_row_stride + (uint64_t)yN >= (uint64_t(1) << 32) ||
-        (uint64_t)xM * (uint64_t)out_col_stride + (uint64_t)m >= (uint64_t(1) << 32))
-        return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");
-    const int64_t sp = floordiv(facet_off0 * h->xM, h->N);
-    ColPassArgs c;
-    std::memset(&c, 0, sizeof c);
+    CHECK_OFFSETS_32(offsets_fit_32(m, in_row_stride, yN) && offsets_fit_32(xM, out_col_stride, m));
+    ColPassArgs c = col_pass_args(whole(m), contribution_in_padded_subgrid(*h, facet_off0));
     c.ncols = m;
     c.full_logn = h->log_m;
     c.in_pitch = (unsigned)in_row_stride;
     c.out_pitch = (unsigned)out_col_stride;
-    c.ld_mul = c.st_mul = 1;
-    c.ld_a = 0; c.ld_len = m; c.ld_c = 0; c.ld_mod = m;
-    c.st_a = pmod(-sp, m); c.st_len = m; c.st_c = pmod(xM / 2 - m / 2 + sp, xM); c.st_mod = xM;
     c.st_win = h->fn_f;
     c.scale = 1.f;
     c.accumulate = 1;
@@ -113,9 +103,9 @@ int swiftly_hip_add_to_subgrid_from_columns(swiftly_hip_t* h, int dtype, const v
         cz.flags = kZColGather;
         cz.nb = nb;
         for (int b = 0; b < nb; b++) {
-            const int64_t s = floordiv(subgrid_off1s[b0 + b] * h->yN, h->N);
-            cz.b_rot[b] = pmod(-s, m);
-            cz.b_base[b] = pmod(yN / 2 - m / 2 + s, yN);
+            const Window w = window_of(*h, subgrid_off1s[b0 + b]);
+            cz.b_rot[b] = w.rot;
+            cz.b_base[b] = w.base;
         }
         c.in = (const cx<float>*)in;
         c.in_bdiv = nb;
@@ -154,10 +144,7 @@ static int prepare_facet_columns_mixed(swiftly_hip_t* h, const void* in, int64_t
     if (band_is_split(h)) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: internal: split band layout");
     const int Q = it->second.Q, logM = it->second.logM;
     const long long M = 1ll << logM;
-    if ((uint64_t)rows * (uint64_t)in_row_stride >= (uint64_t(1) << 32) || (uint64_t)yN * (uint64_t)out_row_stride >= (uint64_t(1) << 32) ||
-        (uint64_t)yN * (uint64_t)m >= (uint64_t(1) << 32))
-        return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");
-    const int lo = yN / 2 - (int)(rows / 2);
+    CHECK_OFFSETS_32(offsets_fit_32(rows, in_row_stride) && offsets_fit_32(yN, out_row_stride) && offsets_fit_32(yN, m));
     hipStream_t st = (hipStream_t)stream;
     MixedArgs<float> X = mixed_args<float>(it->second, yN);
     X.s_row = 1; X.s_y = m; X.s_j = M * m; X.s_b = (long long)yN * m;
@@ -170,7 +157,7 @@ static int prepare_facet_columns_mixed(swiftly_hip_t* h, const void* in, int64_t
         X.scratch = (cx<float>*)lease.p;
         int rc = 0;
         for (int64_t w = 0; w < nwaves && !rc; w++) {
-            const int64_t s1 = floordiv(wave_off1s[w] * h->yN, h->N);
+            const Window win = window_of(*h, wave_off1s[w]);
             RowsArgs<float> a;
             std::memset(&a, 0, sizeof a);
             a.in = (const cx<float>*)in + f0 * in_facet_stride;
@@ -180,22 +167,21 @@ static int prepare_facet_columns_mixed(swiftly_hip_t* h, const void* in, int64_t
             a.nrows = m;
             a.nbatch = nf;
             a.rowfast = 1;
-            a.ld = AxisMap<float>{0, (int)rows, 0, (int)rows, nullptr, nullptr};  // window already applied by prepare_facet_band
+            a.ld = axis_map<float>(whole(rows));  // window already applied by prepare_facet_band
             a.conj_ld = 1;
             a.scale = 1.f;
             a.rm_mod = m;
-            a.rm_inner = pmod(-s1, m);
-            a.rm_outer = pmod(yN / 2 - m / 2 + s1 - band_start, yN);  // plain band: physical column = logical - band_start
+            a.rm_inner = win.rot;
+            a.rm_outer = pmod(win.base - band_start, yN);  // plain band: physical column = logical - band_start
             a.rm_full = yN;
             a.full_n = yN;
             OffTab tab;
             tab.use = 1;
-            for (int f = 0; f < nf; f++) tab.ld_a[f] = pmod(-(facet_off0s[f0 + f] + lo), yN);
+            for (int f = 0; f < nf; f++) tab.ld_a[f] = facet_in_padded_facet(*h, rows, facet_off0s[f0 + f]).a;
             rc = radix_launch_status(launch_mixed_pass(Q, a, tab, X, nf, st), Q);
             if (rc) break;
             for (int j = 0; j < Q && !rc; j++) {
-                ColPassArgs c;
-                std::memset(&c, 0, sizeof c);
+                ColPassArgs c = col_pass_args(Map{}, whole(yN));  // (plain load from the pass's scratch: no load map)
                 c.ncols = m;
                 c.in = X.scratch + (long long)j * X.s_j;
                 c.in_pitch = (unsigned)m;
@@ -203,8 +189,6 @@ static int prepare_facet_columns_mixed(swiftly_hip_t* h, const void* in, int64_t
                 c.out = (cx<float>*)out + f0 * out_facet_stride + w * out_wave_stride;
                 c.out_pitch = (unsigned)out_row_stride;
                 c.out_bs = out_facet_stride;
-                c.ld_mul = c.st_mul = 1;
-                c.st_a = 0; c.st_len = yN; c.st_c = 0; c.st_mod = yN;
                 c.scale = (float)(1.0 / yN);
                 c.conj_ld = 0; c.conj_st = 1;
                 c.st_rowmap = rowmaps ? rowmaps + w * rowmap_stride : nullptr;
@@ -232,7 +216,7 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
     const bool ranged = ncols >= 0;  // positions [col_first, col_first + ncols) of the window only, checked against the band
     if (!ranged) ncols = h->m;       // (the whole window, as ever)
     const bool c128 = dtype == SWIFTLY_C128;
-    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     if (c128 && !band_pipeline_c128_supported(h))
         return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: complex128 needs a power-of-two yN_size of 64 .. 32768 and "
                     "(m, xM) with a complex128 sum_finish_facets instance, got yN_size %lld, m %lld, xM %lld",
@@ -244,7 +228,7 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
         return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: padded facet size %d not supported (power of two %d .. %d, or "
                     "Q * 2^k with Q = 3, 5, 7, 9)", yN, 1 << kBandMinLog, 1 << kBandMaxLogYN);
     if (rows <= 0 || rows >= yN) return fail(SWIFTLY_ERR_PARAM, "facet size %lld must be in [1, yN_size - 1]", (long long)rows);
-    if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN) return fail(SWIFTLY_ERR_PARAM, "bad band");
+    CHECK_BAND();
     if (nfacets <= 0 || nwaves <= 0) return 0;
     if (ranged) {
         if (col_first < 0 || ncols <= 0 || col_first + ncols > m || col_first % 16 || ncols % 16)
@@ -252,33 +236,23 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
                         (long long)col_first, (long long)ncols, m);
         if (h->log_yN < 0) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns: a column range needs a power-of-two yN_size");
         // every requested column has to come from the band (the whole-window form maps a stray column to band column 0)
-        for (int64_t w = 0; w < nwaves; w++) {
-            const int64_t s = floordiv(wave_off1s[w] * h->yN, h->N);
-            const int64_t rot = pmod(-s, m), base = pmod(yN / 2 - m / 2 + s, yN);
-            for (int64_t q = col_first; q < col_first + ncols; q++)
-                if (pmod(base + ((q + rot) & (m - 1)) - band_start, yN) >= band_len)
-                    return fail(SWIFTLY_ERR_PARAM, "prepare_facet_columns: position %lld of the window of off1 = %lld is outside the "
-                                "band [%lld, +%lld)", (long long)q, (long long)wave_off1s[w], (long long)band_start, (long long)band_len);
-        }
+        for (int64_t w = 0; w < nwaves; w++)
+            if (const int64_t q = window_in_band(*h, window_of(*h, wave_off1s[w]), col_first, ncols, band_start, band_len); q >= 0)
+                return fail(SWIFTLY_ERR_PARAM, "prepare_facet_columns: position %lld of the window of off1 = %lld is outside the "
+                            "band [%lld, +%lld)", (long long)q, (long long)wave_off1s[w], (long long)band_start, (long long)band_len);
     }
     if (h->log_yN < 0)
         return prepare_facet_columns_mixed(h, in, rows, in_row_stride, in_facet_stride, nfacets, facet_off0s, band_start,
                                            band_len, nwaves, wave_off1s, out, out_row_stride, out_facet_stride,
                                            out_wave_stride, rowmaps, rowmap_stride, stream, ws, ws_bytes);
     // only `rows` input rows are ever read (the rest of the padded axis is zero fill)
-    if ((uint64_t)rows * (uint64_t)in_row_stride >= (uint64_t(1) << 32) || (uint64_t)yN * (uint64_t)out_row_stride >= (uint64_t(1) << 32))
-        return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");
-    const int lo = yN / 2 - (int)(rows / 2);
-    ColPassArgs c;
-    std::memset(&c, 0, sizeof c);
+    CHECK_OFFSETS_32(offsets_fit_32(rows, in_row_stride) && offsets_fit_32(yN, out_row_stride));
+    ColPassArgs c = col_pass_args(whole(rows), whole(yN));  // (load: window already applied by prepare_facet_band)
     c.ncols = (int)ncols;
     c.col0 = (int)col_first;  // the gather sees window position col_first + column; the output pointer is shifted below
     c.full_logn = h->log_yN;
     c.in_pitch = (unsigned)in_row_stride;
     c.out_pitch = (unsigned)out_row_stride;
-    c.ld_mul = c.st_mul = 1;
-    c.ld_a = 0; c.ld_len = (int)rows; c.ld_c = 0; c.ld_mod = (int)rows;  // window already applied by prepare_facet_band
-    c.st_a = 0; c.st_len = yN; c.st_c = 0; c.st_mod = yN;
     c.scale = (float)(1.0 / yN);
     c.conj_ld = c.conj_st = 1;
     c.cg_mod = m; c.cg_full = yN;
@@ -300,11 +274,11 @@ static int prepare_facet_columns_impl(swiftly_hip_t* h, int dtype, const void* i
             cz.flags = kZColGather | kZLoadAF;
             cz.nb = nw;
             for (int w = 0; w < nw; w++) {
-                const int64_t s = floordiv(wave_off1s[w0 + w] * h->yN, h->N);
-                cz.b_rot[w] = pmod(-s, m);
-                cz.b_base[w] = pmod(yN / 2 - m / 2 + s, yN);
+                const Window win = window_of(*h, wave_off1s[w0 + w]);
+                cz.b_rot[w] = win.rot;
+                cz.b_base[w] = win.base;
             }
-            for (int f = 0; f < nf; f++) cz.f_lda[f] = pmod(-(facet_off0s[f0 + f] + lo), yN);
+            for (int f = 0; f < nf; f++) cz.f_lda[f] = facet_in_padded_facet(*h, rows, facet_off0s[f0 + f]).a;
             // item z = f*nw + w reads band buffer f, writes out[f][w]
             c.in = cx_at(in, f0 * in_facet_stride, c128);
             c.in_bdiv = nw; c.in_bs_hi = in_facet_stride; c.in_bs = 0;
@@ -382,7 +356,7 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
     if (col_first < 0 || ncols <= 0 || col_first + ncols > h->m || ((col_first || ncols != h->m) && layout != 1))
         return fail(SWIFTLY_ERR_PARAM, "transform_contributions: bad column range [%lld, +%lld)", (long long)col_first, (long long)ncols);
     const bool c128 = dtype == SWIFTLY_C128;
-    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     if (layout < 0 || layout > 2) return fail(SWIFTLY_ERR_PARAM, "bad layout %d", layout);
     // complex128: the row-window layouts of the band pipeline (layout 0 gathers from the complex64-only column buffers)
     if (c128 && (layout == 0 || !band_pipeline_c128_supported(h)))
@@ -395,17 +369,12 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
     if (h->log_m < kColPassMinLog || h->log_m > kColPassMaxLog || (layout == 0 && h->log_yN < 0))
         return fail(SWIFTLY_ERR_UNSUPPORTED, "transform_contributions: contribution size %d not supported", m);
     if (nfacets <= 0 || nsub <= 0) return 0;
-    if ((uint64_t)yN * (uint64_t)in_row_stride + (uint64_t)yN >= (uint64_t(1) << 32))
-        return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");
-    ColPassArgs c;
-    std::memset(&c, 0, sizeof c);
+    CHECK_OFFSETS_32(offsets_fit_32(yN, in_row_stride, yN));
+    ColPassArgs c = col_pass_args(whole(m), whole(m));  // no placement: out[k] = Fn[k] * F[(k + s') mod m]
     c.ncols = (int)ncols;
     c.full_logn = h->log_m;
     c.in_pitch = (unsigned)in_row_stride;
     c.out_pitch = (unsigned)m;
-    c.ld_mul = c.st_mul = 1;
-    c.ld_a = 0; c.ld_len = m; c.ld_c = 0; c.ld_mod = m;
-    c.st_a = 0; c.st_len = m; c.st_c = 0; c.st_mod = m;   // no placement: out[k] = Fn[k] * F[(k + s') mod m]
     c.st_win = c128 ? (const float*)h->fn_d : h->fn_f;  // (complex128: the double table)
     c.scale = 1.f;
     c.tw = twiddles<float>(h, h->log_m);
@@ -425,15 +394,15 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
             ColZ cz = plain_colz();
             cz.nb = nb;
             cz.flags = kZStoreAF;
-            for (int f = 0; f < nf; f++) cz.f_sta[f] = pmod(-floordiv(facet_off0s[f0 + f] * h->xM, h->N), m);
+            for (int f = 0; f < nf; f++) cz.f_sta[f] = contribution_in_padded_subgrid(*h, facet_off0s[f0 + f]).a;
             for (int b = 0; b < nb && layout != 2; b++) {
-                const int64_t s = floordiv(subgrid_offs[b0 + b] * h->yN, h->N);
+                const Window w = window_of(*h, subgrid_offs[b0 + b]);
                 if (layout == 0) {
-                    cz.b_rot[b] = pmod(-s, m);
-                    cz.b_base[b] = pmod(yN / 2 - m / 2 + s, yN);
+                    cz.b_rot[b] = w.rot;
+                    cz.b_base[b] = w.base;
                 } else {
-                    cz.b_lda[b] = pmod(-s, m);
-                    cz.b_ldc[b] = pmod(yN / 2 - m / 2 + s, yN);
+                    cz.b_lda[b] = w.rot;
+                    cz.b_ldc[b] = w.base;
                 }
             }
             if (layout == 0) cz.flags |= kZColGather;
@@ -451,13 +420,7 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
                     cz.b_out_off[b] = out_offs[b0 + b] + f0 * out_fstrides[b0 + b];
                 }
             }
-            set_col_precision(h, c, h->log_m);
-            if (c128) {  // complex128 storage: always the float64-arithmetic instance
-                c.c128 = 1;
-                c.f64 = 1;
-                c.twd = c.twd_full = twiddles<double>(h, h->log_m);
-                if (!c.twd) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle table");
-            }
+            if (int rc = set_col_precision(h, c, h->log_m, c128)) return rc;
             if (int rc = launch_col_checked(h->log_m, 2, c, cz, 1, nf * nb, (hipStream_t)stream)) return rc;
         }
     }
@@ -526,7 +489,7 @@ static int sum_finish_facets_impl(swiftly_hip_t* h, int dtype, const void* in, i
     DeviceGuard device_guard_(h->device);
     CHECK_SUBGRID_SIZE();
     const bool c128 = dtype == SWIFTLY_C128;
-    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     if (nfacets <= 0 || nfacets > kSumFinishMaxFacets)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "sum_finish_facets: 1..%d facets supported", kSumFinishMaxFacets);
     if (c128 && (placed || !sum_finish_c128_supported(h->log_m, h->log_xM)))
@@ -550,28 +513,16 @@ static int sum_finish_facets_impl(swiftly_hip_t* h, int dtype, const void* in, i
     if (placed && h->log_xM > kPlacedMaxLogXM)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "axis-1-first pipeline: rows of %lld points run the wave-parallel sum_finish form, "
                     "which has no placed mode", (long long)h->xM);
-    a.fn = h->fn_f;
     a.mask_bs = mask ? mask_batch_stride : 0;
-    a.tw_m = twiddles<float>(h, h->log_m);
-    a.tw_x = twiddles<float>(h, h->log_xM);
-    if (!a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
-    // table values from the compact copies (m-point transforms: 64 lanes each; rows: 64 lanes, 256 from 4096 points on)
-    a.twc_m = compact_twiddles(h, h->log_m, h->log_m - 6);
-    a.twc_x = compact_twiddles(h, h->log_xM, h->log_xM - (h->log_xM >= 12 ? 8 : 6));
-    if (!a.twc_m || !a.twc_x) return fail(SWIFTLY_ERR_HIP, "internal: missing compact twiddle tables");
-    if (c128) {  // double Fn and plain double twiddle tables (the complex128 instances read no compact copies)
-        a.fn = (const float*)h->fn_d;
-        a.tw_m = (const cx<float>*)twiddles<double>(h, h->log_m);
-        a.tw_x = (const cx<float>*)twiddles<double>(h, h->log_xM);
-        if (!a.fn || !a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing double tables");
-    }
+    // (the complex128 instances read no compact copies; the block carries them all the same)
+    if (int rc = fill_sum_finish_tables(h, c128, &a.fn, &a.tw_m, &a.tw_x, &a.twc_m, &a.twc_x)) return rc;
     for (int64_t b0 = 0; b0 < nsub; b0 += kSumFinishMaxBatch) {
         const int nb = (int)std::min<int64_t>(kSumFinishMaxBatch, nsub - b0);
         a.in = cx_at(in, b0 * in_sub_stride, c128);
         a.out = cx_at(out, b0 * out_sub_stride, c128);
         // (mask: float, or double with complex128 data)
         a.mask = mask ? (const float*)((const char*)mask + b0 * mask_batch_stride * (c128 ? 8 : 4)) : nullptr;
-        for (int b = 0; b < nb; b++) a.st_a[b] = pmod(-(xM / 2 - xA / 2 + subgrid_off1s[b0 + b]), xM);
+        for (int b = 0; b < nb; b++) a.st_a[b] = subgrid_in_padded_subgrid(*h, xA, subgrid_off1s[b0 + b]).a;
         int e = c128 ? launch_sum_finish_facets_c128(h->log_m, h->log_xM, a, nb, (hipStream_t)stream)
                      : launch_sum_finish_facets(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
         if (int rc = launch_status(e)) return rc;
@@ -606,8 +557,7 @@ int swiftly_hip_finish_axis1_rows(swiftly_hip_t* h, int dtype, const void* bands
     if (nfacets <= 0 || nfacets > kSumFinishMaxFacets)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_axis1_rows: 1..%d facets supported", kSumFinishMaxFacets);
     const int yN = (int)h->yN, m = (int)h->m;
-    if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN)
-        return fail(SWIFTLY_ERR_PARAM, "band [%lld, +%lld) is not a cyclic range of [0, %d)", (long long)band_start, (long long)band_len, yN);
+    CHECK_BAND();
     if (rows <= 0) return 0;
     Axis1RowsArgs a;
     std::memset(&a, 0, sizeof a);
@@ -615,17 +565,14 @@ int swiftly_hip_finish_axis1_rows(swiftly_hip_t* h, int dtype, const void* bands
     a.in_fs = band_facet_stride; a.in_rs = band_row_stride; a.out_fs = out_facet_stride; a.out_rs = out_row_stride;
     a.nrows = (int)rows; a.yN = yN;
     a.band_start = (int)band_start; a.band_len = (int)band_len; a.band_half = (int)band_half_columns(band_len);
-    const int64_t s = floordiv(wave_off1 * h->yN, h->N);
-    a.c0 = (int)pmod(yN / 2 - m / 2 + s, yN);
-    a.s = (int)pmod(s, m);
+    const Window w = window_of(*h, wave_off1);
+    a.c0 = w.base;
+    a.s = pmod(w.s, m);
     // every column of the window must lie inside the band
-    if (pmod(a.c0 - band_start, yN) + m > band_len)
+    if (window_in_band(*h, w, 0, m, band_start, band_len) >= 0)
         return fail(SWIFTLY_ERR_PARAM, "finish_axis1_rows: the window of off1 = %lld is not inside the band", (long long)wave_off1);
-    for (int64_t f = 0; f < nfacets; f++) a.sp[f] = (int)pmod(floordiv(facet_off1s[f] * h->xM, h->N), m);
-    a.fn = h->fn_f;
-    a.tw_m = twiddles<float>(h, h->log_m);
-    a.twc_m = compact_twiddles(h, h->log_m, h->log_m - 6);
-    if (!a.tw_m || !a.twc_m) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
+    for (int64_t f = 0; f < nfacets; f++) a.sp[f] = pmod(facet_shift(*h, facet_off1s[f]), m);
+    if (int rc = fill_sum_finish_tables(h, false, &a.fn, &a.tw_m, nullptr, &a.twc_m, nullptr)) return rc;
     return launch_status(launch_axis1_rows(h->log_m, a, (int)nfacets, (hipStream_t)stream), nullptr, "no instance");
 }
 
@@ -641,7 +588,7 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
     DeviceGuard device_guard_(h->device);
     CHECK_SUBGRID_SIZE();
     const bool c128 = dtype == SWIFTLY_C128;
-    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     if (nfacets <= 0) return fail(SWIFTLY_ERR_UNSUPPORTED, "split_prepare_facets: 1..%d facets supported", kSumFinishMaxFacets);
     // (the gate of swiftly_hip_supports(SPLIT_PREPARE): a caller that asked it is never refused here)
     if (const std::string why = why_not_split_prepare(*h, dtype, nfacets); !why.empty())
@@ -656,40 +603,24 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
     a.nfacets = (int)nfacets;
     a.xA = xA;
     fill_facet_groups(a, h, nfacets, facet_off0s, facet_off1s);
-    a.fn = h->fn_f;
-    a.tw_m = twiddles<float>(h, h->log_m);
-    a.tw_x = twiddles<float>(h, h->log_xM);
-    if (!a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
-    if (c128) {  // double Fn and plain double twiddle tables (the complex128 instances read no compact copies)
-        a.fn = (const float*)h->fn_d;
-        a.tw_m = (const cx<float>*)twiddles<double>(h, h->log_m);
-        a.tw_x = (const cx<float>*)twiddles<double>(h, h->log_xM);
-        if (!a.fn || !a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing double tables");
-    } else {
-        // table values from the compact copies (m-point transforms: 64 lanes each; rows: 64 lanes, 256 from 4096 points on)
-        a.twc_m = compact_twiddles(h, h->log_m, h->log_m - 6);
-        a.twc_x = compact_twiddles(h, h->log_xM, h->log_xM - (h->log_xM >= 12 ? 8 : 6));
-        if (!a.twc_m || !a.twc_x) return fail(SWIFTLY_ERR_HIP, "internal: missing compact twiddle tables");
-    }
+    // (the complex128 instances read no compact copies)
+    if (int rc = fill_sum_finish_tables(h, c128, &a.fn, &a.tw_m, &a.tw_x, c128 ? nullptr : &a.twc_m, c128 ? nullptr : &a.twc_x))
+        return rc;
     for (int64_t b0 = 0; b0 < nsub; b0 += kSumFinishMaxBatch) {
         const int nb = (int)std::min<int64_t>(kSumFinishMaxBatch, nsub - b0);
         a.in = cx_at(in, b0 * in_sub_stride, c128);
         a.out = cx_at(out, b0 * out_sub_stride, c128);
-        for (int b = 0; b < nb; b++) a.ld_a[b] = pmod(-(xM / 2 - xA / 2 + subgrid_off1s[b0 + b]), xM);
+        for (int b = 0; b < nb; b++) a.ld_a[b] = subgrid_in_padded_subgrid(*h, xA, subgrid_off1s[b0 + b]).a;
         int e = c128 ? launch_split_prepare_facets_c128(h->log_m, h->log_xM, a, nb, (hipStream_t)stream)
                      : launch_split_prepare_facets(h->log_m, h->log_xM, a, nb, (hipStream_t)stream);
         if (int rc = launch_status(e, nullptr, "no instance")) return rc;
     }
     // axis-0 remainder of extract_from_subgrid, in place: out[f][b][:, j] = cifft_m( Fn[k] * E[f][b][(k - s'0_f) ..., j] )
-    ColPassArgs c;
-    std::memset(&c, 0, sizeof c);
+    ColPassArgs c = col_pass_args(whole(m), whole(m));
     c.ncols = m;
     c.full_logn = h->log_m;
     c.in_pitch = c.out_pitch = (unsigned)m;
-    c.ld_mul = c.st_mul = 1;
-    c.ld_a = 0; c.ld_len = m; c.ld_c = 0; c.ld_mod = m;
     c.ld_win = c128 ? (const float*)h->fn_d : h->fn_f;  // (complex128: the double table)
-    c.st_a = 0; c.st_len = m; c.st_c = 0; c.st_mod = m;
     c.conj_ld = c.conj_st = 1;
     c.scale = 1.f / (float)m;  // (a power of two: exact in either precision)
     c.tw = twiddles<float>(h, h->log_m);
@@ -700,19 +631,12 @@ int swiftly_hip_split_prepare_facets(swiftly_hip_t* h, int dtype, const void* in
             ColZ cz = plain_colz();
             cz.nb = nb;
             cz.flags = kZLoadAF;
-            for (int f = 0; f < nf; f++) cz.f_lda[f] = pmod(-floordiv(facet_off0s[f0 + f] * h->xM, h->N), m);
+            for (int f = 0; f < nf; f++) cz.f_lda[f] = contribution_in_padded_subgrid(*h, facet_off0s[f0 + f]).a;
             c.in = cx_at((const void*)out, f0 * out_facet_stride + b0 * out_sub_stride, c128);
             c.in_bdiv = nb; c.in_bs_hi = out_facet_stride; c.in_bs = out_sub_stride;
             c.out = cx_at(out, f0 * out_facet_stride + b0 * out_sub_stride, c128);
             c.out_bdiv = nb; c.out_bs_hi = out_facet_stride; c.out_bs = out_sub_stride;
-            if (c128) {  // complex128 storage: always the float64-arithmetic instance (m <= 512: one pass)
-                c.c128 = 1;
-                c.f64 = 1;
-                c.twd = twiddles<double>(h, h->log_m);
-                c.twd_full = c.twd;
-            } else {
-                set_col_precision(h, c, h->log_m);
-            }
+            if (int rc = set_col_precision(h, c, h->log_m, c128)) return rc;  // (complex128: m <= 512, one pass)
             if (int rc = launch_col_checked(h->log_m, 2, c, cz, 1, nf * nb, (hipStream_t)stream)) return rc;
         }
     }
@@ -731,7 +655,7 @@ int swiftly_hip_wave_split_subgrids(swiftly_hip_t* h, int dtype, const void* sub
     DeviceGuard device_guard_(h->device);
     CHECK_SUBGRID_SIZE();
     const bool c128 = dtype == SWIFTLY_C128;
-    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     // (refused before the first launch: the gate of split_prepare_facets)
     if (const std::string why = why_not_split_prepare(*h, dtype, nfacets); !why.empty())
         return fail(SWIFTLY_ERR_UNSUPPORTED, "wave_split_subgrids: %s", why.c_str());
@@ -741,15 +665,11 @@ int swiftly_hip_wave_split_subgrids(swiftly_hip_t* h, int dtype, const void* sub
     if (work_elems < 2 * half) return fail(SWIFTLY_ERR_PARAM, "work holds %lld elements, %lld needed", (long long)work_elems, (long long)(2 * half));
     void* tmp = work;
     const size_t esz = c128 ? sizeof(cx<double>) : sizeof(cx<float>);
-    ColPassArgs c;
-    std::memset(&c, 0, sizeof c);
+    ColPassArgs c = col_pass_args(whole(xA), whole(xM));
     c.c128 = c128 ? 1 : 0;
     c.ncols = xA;
     c.full_logn = h->log_xM;
     c.in_pitch = c.out_pitch = (unsigned)xA;
-    c.ld_mul = c.st_mul = 1;
-    c.ld_a = 0; c.ld_len = xA; c.ld_c = 0; c.ld_mod = xA;
-    c.st_a = 0; c.st_len = xM; c.st_c = 0; c.st_mod = xM;
     c.scale = 1.f;
     for (int64_t b0 = 0; b0 < nsub; b0 += kColZB) {
         const int nb = (int)std::min<int64_t>(kColZB, nsub - b0);
@@ -757,7 +677,7 @@ int swiftly_hip_wave_split_subgrids(swiftly_hip_t* h, int dtype, const void* sub
         cz.nb = nb;
         cz.flags = kZLoadB;
         for (int b = 0; b < nb; b++) {
-            cz.b_lda[b] = pmod(-(xM / 2 - xA / 2 + subgrid_off0s[b0 + b]), xM);
+            cz.b_lda[b] = subgrid_in_padded_subgrid(*h, xA, subgrid_off0s[b0 + b]).a;
             cz.b_ldc[b] = 0;
         }
         c.in = cx_at(subgrids, b0 * (int64_t)xA * xA, c128);
@@ -854,7 +774,7 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
         return fail(SWIFTLY_ERR_PARAM, "null argument");
     DeviceGuard device_guard_(h->device);
     const bool c128 = dtype == SWIFTLY_C128;
-    if (dtype != SWIFTLY_C64 && !c128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     CHECK_FACET_SIZE();
     const int yN = (int)h->yN, m = (int)h->m;
     const swiftly_hip::Mixed* mx = nullptr;  // yN = Q * 2^k: radix-Q pass with the gather-sum load + sub-transforms
@@ -870,25 +790,20 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
         return fail(SWIFTLY_ERR_UNSUPPORTED, "accumulate_facet_columns: yN %lld = Q * 2^k has no complex64 radix-Q table "
                     "(2^k above %d), or would need the split band layout", (long long)h->yN, 1 << kBandMixedMaxLog);
     if (nchunks <= 0 || nchunks > kColZC) return fail(SWIFTLY_ERR_PARAM, "1..%d source chunks", kColZC);
-    if (band_len <= 0 || band_len > yN || band_start < 0 || band_start >= yN) return fail(SWIFTLY_ERR_PARAM, "bad band");
+    CHECK_BAND();
     if (nfacets <= 0) return 0;
-    if ((uint64_t)facet_size * (uint64_t)band_row_stride >= (uint64_t(1) << 32) ||
-        (uint64_t)part_row_stride << kGsRowBits >= (uint64_t(1) << 32))
-        return fail(SWIFTLY_ERR_PARAM, "strides too large for 32-bit offsets");  // (ELEMENT offsets, of either storage type)
-    const int lo = yN / 2 - (int)(facet_size / 2);
-    ColPassArgs c;
-    std::memset(&c, 0, sizeof c);
+    // (ELEMENT offsets, of either storage type)
+    CHECK_OFFSETS_32(offsets_fit_32(facet_size, band_row_stride) && offsets_fit_32(uint64_t(1) << kGsRowBits, part_row_stride));
+    const int lo = facet_lo(*h, facet_size);
+    ColPassArgs c = col_pass_args(whole(yN), whole(facet_size));
     c.ncols = m;
     c.full_logn = h->log_yN;
     c.in = (const cx<float>*)parts;
     c.in_pitch = (unsigned)part_row_stride;
     c.out_pitch = (unsigned)band_row_stride;
-    c.ld_mul = c.st_mul = 1;
-    c.ld_a = 0; c.ld_len = yN; c.ld_c = 0; c.ld_mod = yN;
     c.ld_rowmap = row_sources; c.gs = 1;
     c.f64 = h->col_f64;  // (complex128 storage: always float64 arithmetic, the column_precision setting does not matter)
     c.c128 = c128 ? 1 : 0;
-    c.st_a = 0; c.st_len = (int)facet_size; c.st_c = 0; c.st_mod = (int)facet_size;
     // masks and 1/pswf: float tables, double ones with complex128 storage (the kernel reinterprets the pointers)
     const size_t rsz = c128 ? sizeof(double) : sizeof(float);
     c.st_win = (const float*)masks; c.st_win_bs = masks ? facet_size : 0;
@@ -901,15 +816,15 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
     const int64_t cap = workspace ? workspace_bytes : (int64_t(4) << 30);
     const int64_t per_item = mx ? (int64_t)MixedWorkspace(1, yN, 1ll << mx->logM, m).bytes() : (int64_t)yN * m * (c128 ? 16 : 8);
     const int per_f = (int)std::max<int64_t>(1, std::min<int64_t>(kColZF, cap / per_item));
-    const int64_t s1 = floordiv(subgrid_off1 * h->yN, h->N);
+    const Window win = window_of(*h, subgrid_off1);
     for (int64_t f0 = 0; f0 < nfacets; f0 += per_f) {
         const int nf = (int)std::min<int64_t>(per_f, nfacets - f0);
         ColZ cz = plain_colz();
         cz.flags = kZColScatter | kZStoreAF;
         cz.nb = 1;
-        cz.b_rot[0] = pmod(-s1, m);
-        cz.b_base[0] = pmod(yN / 2 - m / 2 + s1, yN);
-        for (int f = 0; f < nf; f++) cz.f_sta[f] = pmod(-(lo + facet_off0s[f0 + f]), yN);
+        cz.b_rot[0] = win.rot;
+        cz.b_base[0] = win.base;
+        for (int f = 0; f < nf; f++) cz.f_sta[f] = facet_in_padded_facet(*h, facet_size, facet_off0s[f0 + f]).a;
         for (int k = 0; k < nchunks; k++) {
             cz.c_base[k] = chunk_offsets[k] + f0 * chunk_facet_strides[k];
             cz.c_fs[k] = chunk_facet_strides[k];
@@ -958,7 +873,7 @@ int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void
     }
     if (touched) {
         hipLaunchKernelGGL(mark_columns_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, touched,
-                           m, pmod(-s1, m), pmod(yN / 2 - m / 2 + s1, yN), yN, (int)band_start, (int)band_len);
+                           m, win.rot, win.base, yN, (int)band_start, (int)band_len);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -968,7 +883,7 @@ int swiftly_hip_band_zero_untouched(swiftly_hip_t* h, int dtype, void* bands, in
                                     int64_t band_len, const unsigned char* touched, void* stream) {
     if (!h || !bands || !touched) return fail(SWIFTLY_ERR_PARAM, "null argument");
     DeviceGuard device_guard_(h->device);
-    if (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     if (rows <= 0 || band_len <= 0) return 0;
     dim3 grid((unsigned)((band_len + 63) / 64), (unsigned)std::min<int64_t>(rows, 1024));
     if (dtype == SWIFTLY_C128)

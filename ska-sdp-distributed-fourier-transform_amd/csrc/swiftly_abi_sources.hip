@@ -9,7 +9,7 @@ namespace {
 const int64_t kSrcMaxImage = int64_t(1) << 31;
 
 int check_sources_common(int dtype, const void* sources, int64_t n_sources, int64_t image_size, int64_t size) {
-    if (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128) return fail(SWIFTLY_ERR_PARAM, "bad dtype %d", dtype);
+    CHECK_DTYPE();
     if (image_size <= 0 || image_size > kSrcMaxImage)
         return fail(SWIFTLY_ERR_PARAM, "image size %lld must be in [1, 2^31]", (long long)image_size);
     if (size <= 0 || size > image_size)

@@ -5,7 +5,7 @@
 //   out[row, dst(i)] (+)= X[i] * scale * win(i)      (or skipped)
 //
 // Every SwiFTly primitive that contains a transform is an instance of this
-// with different AxisMaps (see swiftly_abi.hip for the table that maps the
+// with different AxisMaps (see swiftly_geometry.h for the table that maps the
 // reference's core.py:189-484 onto it).
 #pragma once
 #include "swiftly_caps.h"  // kMinLogN, kMaxLogNFloat
