@@ -419,7 +419,10 @@ int swiftly_hip_transform_contributions(swiftly_hip_t* h, int dtype, const void*
  * rowmaps[i] (device int32[yN] or NULL; it may keep more rows than the subgrids read).  Column j of every output block
  * comes from the piece that holds position j; a piece with count 0 is skipped.  Output placement as wave_facet_side:
  * g_offsets / g_facet_strides (both or neither), else g_facet_stride / g_sub_stride.  Bit-identical to
- * transform_contributions on a Q assembled from the pieces. */
+ * transform_contributions on a Q assembled from the pieces.  Two non-empty pieces are read by ONE launch sequence over the
+ * whole window (a single launch per batch of 32 facets x 64 subgrids), whose column tiles take each column from the piece
+ * that holds it -- for complex64 with m = 128, 256 (float32 column arithmetic) and 512 (either column precision); any other
+ * case, and every case after swiftly_hip_k3_one_launch(0), runs one launch sequence per piece, with the same bits. */
 int swiftly_hip_transform_contributions_pieces(swiftly_hip_t* h, int dtype, int64_t npieces, const void* const* q,
                                                const int64_t* q_facet_strides, const int32_t* const* rowmaps,
                                                const int64_t* n_rows, const int64_t* first, const int64_t* count,
@@ -427,6 +430,10 @@ int swiftly_hip_transform_contributions_pieces(swiftly_hip_t* h, int dtype, int6
                                                const int64_t* sub_off0s, void* g_out, int64_t g_facet_stride,
                                                int64_t g_sub_stride, const int64_t* g_offsets,
                                                const int64_t* g_facet_strides, void* stream);
+/* Process-wide switch of the one-launch form of transform_contributions_pieces (A/B runs and tests): sets it to on != 0
+ * and returns the previous value; on < 0 only queries.  Initial value 1, or 0 with the environment variable
+ * SWIFTLY_K3_ONE_LAUNCH=0.  (No reference counterpart: scheduling of this implementation.) */
+int swiftly_hip_k3_one_launch(int on);
 
 /* K4b + K5a: for every padded row r < xM of every subgrid b:
  *   out[b][r, :] = mask_b * finish_subgrid_axis1( sum_f add_to_subgrid_axis1( G[f][b][k_f(r), :], facet_off1s[f] ) )

@@ -18,6 +18,34 @@ static int col512_tile32() {
     return v;
 }
 
+// The piece-aware single pass (col_pass2_kernel, ColPassSrc2): the instances the forward slab path can reach -- complex64
+// storage, plain mapped load; float arithmetic at 128 and 256 points (64-column tiles) and at 512 points on 32-column
+// tiles, float64 arithmetic at 512 points.  Everything else has none: the caller launches once per piece.
+bool col_pass_pieces_supported(int logn, const ColPassArgs& a) {
+    if (a.c128 || a.gs || a.in_bdiv <= 0 || a.in_bs) return false;
+    if (a.f64) return logn == 9 && a.twd;
+    return logn == 7 || logn == 8 || (logn == 9 && a.tile32 && col512_tile32());
+}
+template <class G, typename RC>
+static int launch_pieces(const ColPassArgs& a, const ColPassSrc2& s2, const ColZ& cz, int outer, int nbatch, hipStream_t s,
+                         const cx<RC>* tw, const cx<RC>* tw_full) {
+    dim3 grid((unsigned)((a.ncols + G::COLS - 1) / G::COLS), (unsigned)outer, (unsigned)nbatch);
+    return launch_lds<col_pass2_kernel<G, RC>, G::LDS_BYTES>(grid, dim3(G::NT), s, a, s2, a.in, a.out, a.ld_win, a.ld_win2,
+                                                             a.st_win, a.st_win2, a.st_rowmap, tw, tw_full, cz);
+}
+template <int LOGN>
+static int launch_mode_pieces(const ColPassArgs& a, const ColPassSrc2& s2, const ColZ& cz, int outer, int nbatch,
+                              hipStream_t s) {
+    if (!col_pass_pieces_supported(LOGN, a)) return (int)hipErrorInvalidConfiguration;
+    if constexpr (LOGN == 9) {
+        if (a.f64) return launch_pieces<typename CGeoFor<9, double>::type, double>(a, s2, cz, outer, nbatch, s, a.twd, a.twd_full);
+        return launch_pieces<CGeo512Half, float>(a, s2, cz, outer, nbatch, s, a.tw, a.tw_full);
+    }
+    if constexpr (LOGN == 7 || LOGN == 8)
+        return launch_pieces<typename CGeoFor<LOGN>::type, float>(a, s2, cz, outer, nbatch, s, a.tw, a.tw_full);
+    return (int)hipErrorInvalidConfiguration;
+}
+
 template <int LOGN, int MODE>
 static int launch_mode(const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
     using G = typename CGeoFor<LOGN>::type;
@@ -118,7 +146,9 @@ static int launch_mode_c128(const ColPassArgs& a, const ColZ& cz, int outer, int
 }
 
 template <int LOGN>
-static int launch_one(int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
+static int launch_one(int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s,
+                      const ColPassSrc2* src2) {
+    if (src2) return mode == 2 ? launch_mode_pieces<LOGN>(a, *src2, cz, outer, nbatch, s) : (int)hipErrorInvalidConfiguration;
     if (a.c128) {
         if (mode == 0) return launch_mode_c128<LOGN, 0>(a, cz, outer, nbatch, s);
         if (mode == 1) return launch_mode_c128<LOGN, 1>(a, cz, outer, nbatch, s);
@@ -136,15 +166,17 @@ static int launch_one(int mode, const ColPassArgs& a, const ColZ& cz, int outer,
 
 template <int LO, int HI>
 struct CDispatch {
-    static int launch(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
-        if (logn == LO) return launch_one<LO>(mode, a, cz, outer, nbatch, s);
-        if constexpr (LO < HI) return CDispatch<LO + 1, HI>::launch(logn, mode, a, cz, outer, nbatch, s);
+    static int launch(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s,
+                      const ColPassSrc2* src2) {
+        if (logn == LO) return launch_one<LO>(mode, a, cz, outer, nbatch, s, src2);
+        if constexpr (LO < HI) return CDispatch<LO + 1, HI>::launch(logn, mode, a, cz, outer, nbatch, s, src2);
         return -1;
     }
 };
 
-int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
-    return CDispatch<kColPassMinLog, kColPassMaxLog>::launch(logn, mode, a, cz, outer, nbatch, s);
+int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s,
+                    const ColPassSrc2* src2) {
+    return CDispatch<kColPassMinLog, kColPassMaxLog>::launch(logn, mode, a, cz, outer, nbatch, s, src2);
 }
 bool col_pass_f64_supported(int logn) { return logn >= kColF64MinLog && logn <= kColPassMaxLogF64; }
 

@@ -10,8 +10,9 @@ ColZ plain_colz() {
     return z;
 }
 
-int launch_col_checked(int lg, int mode, const ColPassArgs& args, const ColZ& cz, int outer, int nb, hipStream_t st) {
-    return launch_status(launch_col_pass(lg, mode, args, cz, outer, nb, st));
+int launch_col_checked(int lg, int mode, const ColPassArgs& args, const ColZ& cz, int outer, int nb, hipStream_t st,
+                       const ColPassSrc2* src2) {
+    return launch_status(launch_col_pass(lg, mode, args, cz, outer, nb, st, src2));
 }
 
 // Scratch handed down by an entry point for the duration of one ABI call on this host thread (the batch entry

@@ -231,7 +231,8 @@ inline ColPassArgs col_pass_args(const Map& ld, const Map& st) {
     c.st_a = st.a; c.st_len = st.len; c.st_c = st.c; c.st_mod = st.mod;
     return c;
 }
-int launch_col_checked(int lg, int mode, const ColPassArgs& args, const ColZ& cz, int outer, int nb, hipStream_t st);
+int launch_col_checked(int lg, int mode, const ColPassArgs& args, const ColZ& cz, int outer, int nb, hipStream_t st,
+                       const ColPassSrc2* src2 = nullptr);
 // scratch handed down by an entry point for the duration of one ABI call on this host thread (see col_transform)
 extern thread_local void* t_call_ws;
 extern thread_local size_t t_call_ws_bytes;

@@ -342,19 +342,30 @@ int swiftly_hip_prepare_facet_columns_range(swiftly_hip_t* h, int dtype, const v
 } // extern "C" (helper follows)
 // out_offs / out_fstrides (optional, per subgrid): item (f, b) is written at out + out_offs[b] + f*out_fstrides[b]
 // instead of out + f*out_facet_stride + b*out_sub_stride
+// in_b (optional, layout 1 on the whole window): a second source [rows kept, m] per facet with its own facet stride and row
+// map, which holds the window positions below `split` (a multiple of 16); `in` holds the others.  One launch per batch reads
+// both (ColPassSrc2); SWIFTLY_ERR_UNSUPPORTED before anything is launched when the case has no such instance.
+struct SecondSource {
+    const void* in;
+    int64_t facet_stride;
+    const int32_t* rowmap;
+    int64_t split;
+};
 static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void* in, int layout, int64_t in_row_stride,
                                         int64_t in_facet_stride, int64_t in_sub_stride, const int32_t* in_rowmap,
                                         int64_t band_start, int64_t band_len, int64_t nfacets,
                                         const int64_t* facet_off0s, int64_t nsub, const int64_t* subgrid_offs,
                                         void* out, int64_t out_facet_stride, int64_t out_sub_stride,
                                         const int64_t* out_offs, const int64_t* out_fstrides, void* stream,
-                                        int64_t col_first = 0, int64_t ncols = -1) {
+                                        int64_t col_first = 0, int64_t ncols = -1, const SecondSource* in_b = nullptr) {
     if (!h || !in || !out || !facet_off0s) return fail(SWIFTLY_ERR_PARAM, "null argument");
     // columns [col_first, col_first + ncols) of the blocks only (layout 1, whose columns are read where they are written):
     // both pointers are shifted, the other columns of `out` are not touched
     if (ncols < 0) ncols = h->m;
     if (col_first < 0 || ncols <= 0 || col_first + ncols > h->m || ((col_first || ncols != h->m) && layout != 1))
         return fail(SWIFTLY_ERR_PARAM, "transform_contributions: bad column range [%lld, +%lld)", (long long)col_first, (long long)ncols);
+    if (in_b && (layout != 1 || col_first || ncols != h->m || !in_b->in || in_b->split <= 0 || in_b->split >= h->m || in_b->split % 16))
+        return fail(SWIFTLY_ERR_PARAM, "transform_contributions: bad second source (split %lld)", (long long)(in_b ? in_b->split : 0));
     const bool c128 = dtype == SWIFTLY_C128;
     CHECK_DTYPE();
     if (layout < 0 || layout > 2) return fail(SWIFTLY_ERR_PARAM, "bad layout %d", layout);
@@ -421,13 +432,29 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
                 }
             }
             if (int rc = set_col_precision(h, c, h->log_m, c128)) return rc;
-            if (int rc = launch_col_checked(h->log_m, 2, c, cz, 1, nf * nb, (hipStream_t)stream)) return rc;
+            ColPassSrc2 src2 = {};
+            if (in_b) {
+                if (!col_pass_pieces_supported(h->log_m, c))
+                    return fail(SWIFTLY_ERR_UNSUPPORTED, "transform_contributions: no two-source instance for m = %d", m);
+                src2.in = cx_at(in_b->in, f0 * in_b->facet_stride, c128);
+                src2.in_bs_hi = in_b->facet_stride;
+                src2.ld_rowmap = in_b->rowmap;
+                src2.split = (int)in_b->split;
+            }
+            if (int rc = launch_col_checked(h->log_m, 2, c, cz, 1, nf * nb, (hipStream_t)stream, in_b ? &src2 : nullptr)) return rc;
         }
     }
     return 0;
 }
 
+// SWIFTLY_K3_ONE_LAUNCH=0: K3 of a window in two pieces as one launch sequence per piece (A/B runs; swiftly_hip_k3_one_launch)
+static std::atomic<int> g_k3_one_launch{getenv("SWIFTLY_K3_ONE_LAUNCH") ? atoi(getenv("SWIFTLY_K3_ONE_LAUNCH")) != 0 : 1};
+
 extern "C" {
+int swiftly_hip_k3_one_launch(int on) {
+    return on < 0 ? g_k3_one_launch.load() : g_k3_one_launch.exchange(on ? 1 : 0);
+}
+
 int swiftly_hip_transform_contributions(swiftly_hip_t* h, int dtype, const void* in, int layout, int64_t in_row_stride,
                                         int64_t in_facet_stride, int64_t in_sub_stride, const int32_t* in_rowmap,
                                         int64_t band_start, int64_t band_len, int64_t nfacets,
@@ -444,7 +471,9 @@ int swiftly_hip_transform_contributions(swiftly_hip_t* h, int dtype, const void*
  * positions [first[i], first[i] + count[i]) of the window, at the same positions of its rows, in q[i] (layout 1:
  * [F, rows kept, m], facet stride q_facet_strides[i], row map rowmaps[i] over n_rows[i] kept rows).  The output is that
  * of transform_contributions layout 1 (or, with g_offsets / g_facet_strides, of wave_facet_side with compute_q = 0) on a Q
- * assembled from the pieces: one launch sequence per piece, a piece with count 0 is skipped. */
+ * assembled from the pieces.  Two non-empty pieces are read by ONE launch sequence over the whole window when the
+ * column pass has a two-source instance for the case (col_pass_pieces_supported) and swiftly_hip_k3_one_launch is on;
+ * otherwise one launch sequence per piece.  A piece with count 0 is skipped. */
 int swiftly_hip_transform_contributions_pieces(swiftly_hip_t* h, int dtype, int64_t npieces, const void* const* q,
                                                const int64_t* q_facet_strides, const int32_t* const* rowmaps,
                                                const int64_t* n_rows, const int64_t* first, const int64_t* count,
@@ -470,6 +499,14 @@ int swiftly_hip_transform_contributions_pieces(swiftly_hip_t* h, int dtype, int6
     if (npieces == 2 && count[0] && count[1] && first[0] < first[1] + count[1] && first[1] < first[0] + count[0])
         return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: the pieces overlap");
     if (covered != m) return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: the pieces hold %lld of %lld positions", (long long)covered, (long long)m);
+    if (npieces == 2 && count[0] && count[1] && g_k3_one_launch.load()) {
+        const int b = first[0] == 0 ? 0 : 1, a = 1 - b;  // piece b holds [0, split), piece a [split, m)
+        const SecondSource second = {q[b], q_facet_strides[b], rowmaps[b], count[b]};
+        const int rc = transform_contributions_impl(h, dtype, q[a], 1, m, q_facet_strides[a], 0, rowmaps[a], 0, 0, nfacets,
+                                                    facet_off0s, nsub, sub_off0s, g_out, g_facet_stride, g_sub_stride,
+                                                    g_offsets, g_facet_strides, stream, 0, -1, &second);
+        if (rc != SWIFTLY_ERR_UNSUPPORTED) return rc;  // (no instance: refused before its first launch -- once per piece)
+    }
     for (int64_t i = 0; i < npieces; i++) {
         if (!count[i]) continue;
         if (int rc = transform_contributions_impl(h, dtype, q[i], 1, m, q_facet_strides[i], 0, rowmaps[i], 0, 0, nfacets,

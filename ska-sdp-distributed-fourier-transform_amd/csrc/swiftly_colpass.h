@@ -139,6 +139,20 @@ struct ColPassArgs {
     int c128;
 };
 
+// Second source of a piece-aware mapped load (template PW of col_pass_body; the single pass of K3 whose m-wide window
+// lies in two Q buffers, column slabs of the padded axis): tile column c < split is read from `in` here (piece B, which
+// holds the window positions [0, split)), c >= split from ColPassArgs::in (piece A, [split, ncols)); both pieces keep
+// position c at column c of their rows, row pitch ColPassArgs::in_pitch.  Item z reads in + (z / in_bdiv) * in_bs_hi: the
+// two buffers keep different numbers of rows, so each has its facet stride and its row map.  split is a multiple of 16.
+// A block of its own, handed to col_pass2_kernel only, and not a part of ColPassArgs: a longer ColPassArgs moves the
+// kernel-argument offsets of every col_pass_kernel instance.
+struct ColPassSrc2 {
+    const cx<float>* in;
+    long long in_bs_hi;
+    const int* ld_rowmap;  // as ColPassArgs::ld_rowmap (optional; a negative entry = row absent from this piece: zero)
+    int split;
+};
+
 // Per-batch-item parameters (by value).  Batch item z = f * nb + b  (f: facet index, b: subgrid index of the
 // wave); what varies with the SUBGRID lives in the b_* tables, what varies with the FACET in the f_* tables.
 constexpr int kColZB = 64;   // subgrids per launch
@@ -246,16 +260,23 @@ __device__ __forceinline__ double slot_bcast_f(double val, int v, int hw) {
 // coalesced vector load per table instead of P dependent scalar loads), and
 // the main loops fetch the values with v_readlane.  The output-side
 // bookkeeping is issued before the butterflies so its latency hides under them.
-template <class G, int MODE, bool SNT, bool GS, class CZ, typename RC = float, typename ST = float>
+//
+// PW (piece-aware mapped load, single pass only; off by default): the columns below S2->split come from a second buffer
+// with a row map and a facet stride of its own (ColPassSrc2).  A tile that lies inside one piece -- workgroup-uniform --
+// selects that piece's base and map once and loads as ever.  A tile across the split (a boundary between two groups of 16
+// lanes) looks every row slot up in BOTH maps and selects row and base per lane; a row that one map marks absent is zero
+// for that piece's lanes only.
+template <class G, int MODE, bool SNT, bool GS, class CZ, typename RC = float, typename ST = float, bool PW = false>
 __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>* __restrict__ gin,
                                               cx<ST>* __restrict__ gout, const float* __restrict__ ld_win,
                                               const float* __restrict__ ld_win2, const float* __restrict__ st_win,
                                               const float* __restrict__ st_win2, const int* __restrict__ st_rowmap,
                                               const cx<RC>* __restrict__ tw, const cx<RC>* __restrict__ tw_full,
                                               const CZ& cz, const int wave, const int lane, const int bx, const int o,
-                                              const int z, unsigned char* smem) {
+                                              const int z, unsigned char* smem, const ColPassSrc2* S2 = nullptr) {
     constexpr int P = G::P, T = G::T;
     static_assert(P <= 64, "one lane per row slot");
+    static_assert(!PW || (MODE == 2 && !GS), "piece-aware load: the plain mapped load of a single pass");
     constexpr bool HALF = G::HALF;
     constexpr bool RAW_LD = MODE == 1, RAW_ST = MODE == 0;
     constexpr bool NT_LD = RAW_LD ? SNT : true, NT_ST = RAW_ST ? SNT : true;
@@ -301,7 +322,19 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>
         A.in_bdiv > 0 ? (long long)(z / A.in_bdiv) * A.in_bs_hi + (long long)(z % A.in_bdiv) * A.in_bs
                       : (long long)(RAW_LD ? z - A.raw_z0 : z) * A.in_bs;
     static_assert(sizeof(ST) <= sizeof(RC), "complex128 storage computes in double");
-    const cx<ST>* __restrict__ in = gin + (GS ? 0ll : in_off) + lcol;
+    // PW: which piece this lane's column lies in; `straddle` (uniform): the tile holds columns of both
+    bool from_b = false, straddle = false;
+    const int* __restrict__ ld_map = A.ld_rowmap;
+    long long in_off_b = 0;
+    if constexpr (PW) {
+        const int tile0 = bx * G::COLS;
+        from_b = col < S2->split;
+        straddle = tile0 < S2->split && tile0 + G::COLS > S2->split;
+        if (tile0 + G::COLS <= S2->split) ld_map = S2->ld_rowmap;
+        in_off_b = (long long)(z / A.in_bdiv) * S2->in_bs_hi;
+    }
+    const cx<ST>* __restrict__ in =
+        PW && from_b ? reinterpret_cast<const cx<ST>*>(S2->in) + in_off_b + lcol : gin + (GS ? 0ll : in_off) + lcol;
     const long long out_off =
         (cz.flags & kZOutB) ? cz.b_out_off[zb] + (long long)zf * cz.b_out_fs[zb]
         : A.out_bdiv > 0 ? (long long)(z / A.out_bdiv) * A.out_bs_hi + (long long)(z % A.out_bdiv) * A.out_bs
@@ -321,6 +354,7 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>
 
     // ---- input rows: lane `slot` describes row i = t + slot*T
     int in_row;         // element offset row*pitch is formed later; -1 = zero (padding)
+    int in_row_b = -1;  // PW, straddling tile: the same through the second source's map (in_row: through the first's)
     long long gs_off1 = -1, gs_off2 = -1;  // GS: element offsets of the (up to) two source rows, -1 = none
     RC in_w = (RC)1;
     {
@@ -350,7 +384,15 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>
                 }
                 in_row = r1;
             } else {
-                if (A.ld_rowmap) idx = A.ld_rowmap[ok ? idx : 0];
+                if constexpr (PW) {
+                    if (straddle) {  // uniform
+                        const int idx_b = S2->ld_rowmap ? S2->ld_rowmap[ok ? idx : 0] : idx;
+                        in_row_b = ok ? idx_b : -1;
+                    }
+                    if (ld_map) idx = ld_map[ok ? idx : 0];
+                } else {
+                    if (A.ld_rowmap) idx = A.ld_rowmap[ok ? idx : 0];
+                }
                 in_row = ok ? idx : -1;
             }
             const int qs = ok ? q : 0;
@@ -390,7 +432,19 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>
     // Issue ALL loads first (nothing in this loop consumes a loaded value, so the
     // P loads of a lane are in flight together), then apply windows / conjugation.
     cx<RC> x[P];
-    static_for<0, P>([&](auto vI) {
+    if constexpr (PW) {
+        if (straddle) {  // uniform: row and base per lane
+            static_for<0, P>([&](auto vI) {
+                constexpr int v = decltype(vI)::value;
+                const int row_a = slot_bcast<HALF>(in_row, v, hw), row_b = slot_bcast<HALF>(in_row_b, v, hw);
+                const int row = from_b ? row_b : row_a;
+                cx<ST> val = {(ST)0, (ST)0};
+                if (row >= 0 && live) val = cp_load<NT_LD>(in + (unsigned)row * A.in_pitch);
+                x[v] = cx<RC>{(RC)val.x, (RC)val.y};
+            });
+        }
+    }
+    if (!straddle) static_for<0, P>([&](auto vI) {
         constexpr int v = decltype(vI)::value;
         const int row = slot_bcast<HALF>(in_row, v, hw);
         cx<ST> val = {(ST)0, (ST)0};
@@ -478,9 +532,33 @@ __global__ __launch_bounds__(G::NT, G::MINW) void col_pass_kernel(const ColPassA
                                     blockIdx.y, blockIdx.z + A.z0, smem);
 }
 
+// the piece-aware single pass: col_pass_kernel<G, 2, true> with the second source (columns below S2.split)
+template <class G, typename RC = float>
+__global__ __launch_bounds__(G::NT, G::MINW) void col_pass2_kernel(const ColPassArgs A, const ColPassSrc2 S2,
+                                                          const cx<float>* __restrict__ gin,
+                                                          cx<float>* __restrict__ gout,
+                                                          const float* __restrict__ ld_win,
+                                                          const float* __restrict__ ld_win2,
+                                                          const float* __restrict__ st_win,
+                                                          const float* __restrict__ st_win2,
+                                                          const int* __restrict__ st_rowmap,
+                                                          const cx<RC>* __restrict__ tw,
+                                                          const cx<RC>* __restrict__ tw_full, const ColZ cz) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    col_pass_body<G, 2, true, false, ColZ, RC, float, true>(A, gin, gout, ld_win, ld_win2, st_win, st_win2, st_rowmap, tw,
+                                                            tw_full, cz, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6),
+                                                            threadIdx.x & 63, blockIdx.x, blockIdx.y, blockIdx.z + A.z0, smem,
+                                                            &S2);
+}
+
 constexpr int kColPassMinLog = 2;
 constexpr int kColPassMaxLog = 10;  // 1024 points: 32-column tiles
 
-int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s);
+// src2 (optional): the piece-aware load of a single pass (mode 2); hipErrorInvalidConfiguration without launching anything
+// when the case has no such instance (col_pass_pieces_supported)
+int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s,
+                    const ColPassSrc2* src2 = nullptr);
+// is there a piece-aware instance for the single pass launch_col_pass(logn, 2, a, ...) would run?
+bool col_pass_pieces_supported(int logn, const ColPassArgs& a);
 
 }  // namespace swf

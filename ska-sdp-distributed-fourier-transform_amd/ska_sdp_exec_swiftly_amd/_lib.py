@@ -49,6 +49,8 @@ def _declare(lib):
     lib.swiftly_hip_mixed_factor.argtypes = [i64, POINTER(c_int), POINTER(c_int)]
     lib.swiftly_hip_build_id.restype = ctypes.c_char_p
     lib.swiftly_hip_build_id.argtypes = []
+    lib.swiftly_hip_k3_one_launch.restype = c_int
+    lib.swiftly_hip_k3_one_launch.argtypes = [c_int]
     lib.swiftly_hip_chain_chunk_streams.restype = None
     lib.swiftly_hip_chain_chunk_streams.argtypes = [ctypes.c_int]
     lib.swiftly_hip_set_column_precision.restype = ctypes.c_int

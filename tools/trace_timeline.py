@@ -23,6 +23,9 @@ def short(name):
     m = re.search(r"col_pass_kernelINS_4CGeoILi(\d+)ELi(\d+)ELb[01]ELi(\d+)ELi\d+EEELi(\d)", name)
     if m:
         return f"col_pass<{1 << int(m.group(1))},c{m.group(3)},mode{m.group(4)}>"
+    m = re.search(r"col_pass2_kernelINS_4CGeoILi(\d+)ELi(\d+)ELb[01]ELi(\d+)", name)
+    if m:
+        return f"col_pass2<{1 << int(m.group(1))},c{m.group(3)}>"
     m = re.search(r"(sum_finish_facets_kernel|split_prepare_facets_kernel)ILi(\d+)ELi(\d+)", name)
     if m:
         return f"{m.group(1)}<{m.group(2)},{m.group(3)}>"
