@@ -107,9 +107,12 @@ enum {
                                                    BACKWARD_BAND; also answers for complex128 (xM, m powers of two, yN_size a
                                                    power of two 64 .. 32768, no Q * 2^k).  The gate accumulate_facet_columns
                                                    and finish_facet_band refuse through */
-    SWIFTLY_FEATURE_SPLIT_PREPARE = 7           /* split_prepare_facets + wave_split_subgrids (dtype, n_facets): complex64 as
+    SWIFTLY_FEATURE_SPLIT_PREPARE = 7,          /* split_prepare_facets + wave_split_subgrids (dtype, n_facets): complex64 as
                                                    FUSED_SUBGRID; complex128 for (m, xM) = (128, 256), (128, 1024), (256, 512),
                                                    (256, 1024), (512, 1024), up to 64 facets */
+    SWIFTLY_FEATURE_REAL_FACETS = 8             /* prepare_facet_band_real / prepare_facet_band_rows_real (dtype = the OUTPUT
+                                                   type): the sizes of BAND_PIPELINE in complex64 with a power-of-two yN_size;
+                                                   no complex128, no Q * 2^k.  The gate both entry points refuse through */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -357,6 +360,24 @@ int swiftly_hip_prepare_facet_band_rows(swiftly_hip_t* h, int dtype, const void*
                                         int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                         int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                         int64_t other_axis_row0, void* stream);
+/* K1 of a REAL-VALUED facet (a Stokes image): the two entry points above with `in` pointing to FLOAT32, in_row_stride
+ * counting real elements, and `dtype` the type of the OUTPUT (SWIFTLY_C64).  The row kernels load the reals (half the bytes
+ * of the promoted facet) and set the imaginary parts to zero in registers; `out` holds the values the complex entry points
+ * give for the same facet promoted to a contiguous complex64 copy (every operation on a zero imaginary part is exact), whatever
+ * in_row_stride and the alignment of `in`: the transform is chosen as for that copy.  Sizes: SWIFTLY_FEATURE_REAL_FACETS
+ * (complex64 band pipeline, power-of-two yN_size), SWIFTLY_ERR_UNSUPPORTED otherwise; every call the complex entry points
+ * take at those sizes is taken.  At yN_size 32768 the 8-byte loads of the tuned instances need an even in_row_stride and an
+ * 8-byte-aligned `in`; anything else fetches the same elements with 4-byte loads (same values, slower).
+ * Exception to "the same values": at yN_size 32768 a facet_size above 23552 (the row can cover more than 24 of the 32 load
+ * segments) runs all-segment instances that agree with the complex ones to the last bit or two, not bit for bit (the
+ * compiler contracts their products differently); a caller that needs the bits of the complex path promotes such facets. */
+int swiftly_hip_prepare_facet_band_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                        int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                        int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream);
+int swiftly_hip_prepare_facet_band_rows_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                             int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                             int64_t band_start, int64_t band_len, int64_t other_axis_size,
+                                             int64_t other_axis_row0, void* stream);
 
 /* K2: for every facet f < nfacets: extract_from_facet(P_f, subgrid_off1, axis=1) (core.py:715) folded into the load
  * of prepare_facet(., facet_off0s[f], axis=0) WITHOUT its window (pre-applied by prepare_facet_band).

@@ -18,6 +18,14 @@ static int launch_one(const RowsArgs<R>& a, const OffTab& tab, hipStream_t s) {
         const long long rowblocks = ((long long)a.nrows + G::RB - 1) / G::RB;
         grid = (unsigned)(((rowblocks + 7) / 8) * 8 * a.outer);
     }
+    if (a.real_in) {
+        // real input: complex64 prepare_facet of the plain band layout (swiftly_caps.h, why_not_real_facets), 64 .. 4096 points
+        // (8192: the lean row kernel, row_pass.hip)
+        if constexpr (sizeof(R) == 4 && LOGN >= kBandMinLog && LOGN < 13)
+            return launch_lds<fft_rows_kernel<G, R, true>, G::LDS_BYTES>(dim3(grid, a.nbatch > 0 ? a.nbatch : 1), dim3(G::NT), s, a, tab);
+        else
+            return -1;
+    }
     return launch_lds<fft_rows_kernel<G, R>, G::LDS_BYTES>(dim3(grid, a.nbatch > 0 ? a.nbatch : 1), dim3(G::NT), s, a, tab);
 }
 

@@ -34,6 +34,12 @@ static int launch_one(int mode, const RowPassArgs& a, hipStream_t s) {
 
 int launch_row_pass(int logn, int mode, const RowPassArgs& a, hipStream_t s) {
     if (a.nrows <= 0) return 0;
+    if (a.in_real) {  // real input: the 8192-point mapped load of the plain band layout (longer rows: launch_row_pass_band_n)
+        using G = typename RGeoFor<13>::type;
+        if (logn != 13 || mode != 0) return -1;
+        return launch_lds<row_pass_kernel<G, 0, true>, G::LDS_BYTES>(dim3((unsigned)a.nrows), dim3(G::NT), s, a, a.in, a.out, a.ld_win,
+                                                                    a.st_win, a.st_win2, a.tw);
+    }
     switch (logn) {
         case 13: return launch_one<13>(mode, a, s);
         case 14: return launch_one<14>(mode, a, s);
@@ -81,11 +87,11 @@ static int data_segment_run(const RowPassArgs& a, int n, int seglen, int* first)
     return run == count ? run : nseg;  // two runs cannot happen for one cyclic range; be safe
 }
 
-template <class G, bool PAIR, bool WIN, int ST, int NSEG, int CJ = -1, bool W4 = false>
+template <class G, bool PAIR, bool WIN, int ST, int NSEG, int CJ = -1, bool W4 = false, int REAL = 0>
 static int launch_band_inst(const RowPassArgs& a, unsigned blocks, const cx<float>* tw14, const cx<float>* tw_full,
                             hipStream_t s) {
-    return launch_lds<row_pass_band_kernel<G, WIN, ST, PAIR, NSEG, CJ, W4>, G::LDS_BYTES>(dim3(blocks), dim3(G::NT), s, a, a.in,
-                                                                                          a.out, a.ld_win, tw14, tw_full);
+    return launch_lds<row_pass_band_kernel<G, WIN, ST, PAIR, NSEG, CJ, W4, REAL>, G::LDS_BYTES>(dim3(blocks), dim3(G::NT), s, a,
+                                                                                                a.in, a.out, a.ld_win, tw14, tw_full);
 }
 
 // -- re-laid-out load windows (Win4Cache, swiftly_rowpass.h) ------------------------------------------------------
@@ -234,10 +240,74 @@ using BandGeo16k = RGeo<13, 4, true>;  // yN = 16384: 2 x  8192 points,  512 thr
 int launch_row_pass_band(const RowPassArgs& a, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s, Win4Cache* w4) {
     return launch_row_pass_band_n(15, a, tw14, tw_full, s, w4);
 }
+// Forward K1 of a REAL row (RowPassArgs::in_real; window, band store, inverse transform).  The instance is chosen the way
+// launch_row_pass_band_n chooses it for the same row promoted to a contiguous complex64 copy -- same geometry, same segment
+// count and rotation -- so that the values are that call's: at 32768 points the pair geometry whenever the shift and the
+// length are even, whatever the pitch and the base of the caller's rows, which only decide how a lane fetches its two
+// adjacent reals (one 8-byte load, or two 4-byte loads: REAL = 2).  Tuned: 8-byte loads with 16 / 22 / 24 data segments
+// (W4 window table, compact twiddles, load pipeline -- the instances the complex K1 of the benchmark runs) and the
+// 44-segment form of the 65536-point rows.  Without the window table (SWIFTLY_K1_WIN4 < 2, cache full) and for 4-byte
+// loads: the same instances with the plain window loads, whose products and twiddles are the same numbers.
+static int launch_band_real(int logn, const RowPassArgs& a0, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s,
+                            Win4Cache* w4cache) {
+    RowPassArgs a = a0;
+    a.seg_rot = 0;
+    if (!a.ld_win || a.band_len <= 0 || a.win_full || a.ld_c != 0 || a.ld_mod != a.ld_len) return -1;
+    const unsigned blocks = (unsigned)(((a.nrows + 7) / 8) * 16);
+    const bool inv = a.conj_ld && a.conj_st;
+    if (logn == 15) {
+        using G = BandGeo5;
+        using GP = RGeoPre<G::LOGN, G::LOGP, G::SPLIT>;
+        using GC = RGeoPreC<G::LOGN, G::LOGP, G::SPLIT>;
+        constexpr int n = 2 * G::N, SEGLEN = 2 * G::T;
+        // odd shift or length: the 512 x 32 geometry without pair loads, as for the promoted row
+        if ((a.ld_a & 1) || (a.ld_len & 1)) return launch_band_inst<G, false, true, 1, 0, -1, false, 1>(a, blocks, tw_half, tw_full, s);
+        // adjacent reals through ONE 8-byte load: even pitch (in reals), 8-byte-aligned base
+        const bool load8 = !(a.in_pitch & 1) && (reinterpret_cast<uintptr_t>(a.in) & 7) == 0;
+        int first = 0;
+        const int run = data_segment_run(a, n, SEGLEN, &first);
+        const int ns = !inv ? 0 : run <= 16 ? 16 : run <= 22 ? 22 : run <= 24 ? 24 : 0;
+        if (!ns)
+            return load8 ? launch_band_inst<G, true, true, 1, 0, -1, false, 1>(a, blocks, tw_half, tw_full, s)
+                         : launch_band_inst<G, true, true, 1, 0, -1, false, 2>(a, blocks, tw_half, tw_full, s);
+        a.seg_rot = first;
+        if (load8 && w4cache && win4_enabled() >= 2 && w4cache->twc) {
+            const int c = (int)(((long long)a.ld_a + n / 2 + (long long)first * SEGLEN) % n);
+            a.ld_win4 = w4cache->get(a.ld_win, c, a.ld_len, ns, n, SEGLEN, s);
+            if (a.ld_win4) {
+                a.twc = w4cache->twc;
+                if (ns == 16) return launch_band_inst<GC, true, true, 1, 16, 1, true, 1>(a, blocks, tw_half, tw_full, s);
+                if (ns == 22) return launch_band_inst<GC, true, true, 1, 22, 1, true, 1>(a, blocks, tw_half, tw_full, s);
+                return launch_band_inst<GC, true, true, 1, 24, 1, true, 1>(a, blocks, tw_half, tw_full, s);
+            }
+        }
+#define SWF_REAL_PLAIN(NS)                                                                                   \
+    if (ns == NS)                                                                                            \
+        return load8 ? launch_band_inst<GP, true, true, 1, NS, 1, false, 1>(a, blocks, tw_half, tw_full, s)  \
+                     : launch_band_inst<GP, true, true, 1, NS, 1, false, 2>(a, blocks, tw_half, tw_full, s);
+        SWF_REAL_PLAIN(16)
+        SWF_REAL_PLAIN(22)
+        SWF_REAL_PLAIN(24)
+#undef SWF_REAL_PLAIN
+        return -1;
+    }
+    if (logn == 16) {
+        using G = BandGeo64k;
+        int first = 0;
+        if (inv && data_segment_run(a, 2 * G::N, G::T, &first) <= 44) {
+            a.seg_rot = first;
+            return launch_band_inst<G, false, true, 1, 44, 1, false, 1>(a, blocks, tw_half, tw_full, s);
+        }
+        return launch_band_inst<G, false, true, 1, 0, -1, false, 1>(a, blocks, tw_half, tw_full, s);
+    }
+    if (logn == 14) return launch_band_inst<BandGeo16k, false, true, 1, 0, -1, false, 1>(a, blocks, tw_half, tw_full, s);
+    return -1;
+}
 // logn = log2 of the full row length (14, 15 or 16); tw_half = table of length 2^(logn-1), tw_full of length 2^logn
 int launch_row_pass_band_n(int logn, const RowPassArgs& a, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s,
                            Win4Cache* w4) {
     if (a.nrows <= 0) return 0;
+    if (a.in_real) return launch_band_real(logn, a, tw_half, tw_full, s, w4);
     if (a.win_full) {
         // window-rows store (whole-row kernel): 32768-point rows, 512-column windows, 16-byte loads
         if (logn != 15 || a.win_logm != 9 || a.nwin <= 0 || !a.win_d || a.band_len <= 0) return -2;

@@ -481,6 +481,7 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
     r.nrows = a.nrows;
     r.rm_mod = a.rm_mod; r.rm_inner = a.rm_inner; r.rm_outer = a.rm_outer; r.rm_full = a.rm_full;
     r.in_rowmap = a.in_rowmap;
+    r.in_real = a.real_in;
     if (a.st_rowmap) return false;
     r.row_win = a.row_win;
     if (a.row_win && logn > kRowPassMaxLog) return false;  // the two-workgroup kernels take it through prepare_facet_band only
@@ -490,6 +491,11 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
     if (!r.tw) return false;
     r.scale = a.scale; r.conj_ld = a.conj_ld; r.conj_st = a.conj_st; r.accumulate = a.accumulate;
     const int mode = ident_st ? 0 : (ident_ld ? 1 : 2);
+    if (a.real_in) {  // real input: 8192-point rows of the plain band layout only (longer ones: prepare_facet_band_rows_impl)
+        if (logn != kRowPassMinLog || mode != 0) return false;
+        *rc_out = launch_status(launch_row_pass(logn, mode, r, st));
+        return true;
+    }
     // N = 32768: the two-workgroup band kernel for the load map of a prepare_* primitive, else the r1 split kernel
     const bool prep_ld = r.ld_c == 0 && r.ld_mod == r.ld_len;    // load map of a prepare_* primitive (or identity)
     const bool fin_st = r.st_c == 0 && r.st_mod == r.st_len;     // store map of a finish_* primitive
@@ -652,6 +658,9 @@ static int run_rows_chunk(swiftly_hip* h, int logn, RowsArgs<R>& a, const OffTab
         int rc = 0;
         if (!sub && try_col_pass(h, logn, a, tab, st, &rc)) return rc;
         if (!sub && try_row_pass(h, logn, a, tab, st, &rc)) return rc;
+        // real input: only the single-launch generic kernel is left (launch_fft_rows refuses lengths without a real instance)
+        if (a.real_in && (sub || a.rowfast || a.raw_ld))
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: real input reaches a decomposed transform of 2^%d points", logn);
     }
     if (logn > kMaxLogNFloat && sizeof(R) == 4)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "transform length 65536 is only supported for complex64 prepare_* / finish_* "
@@ -950,10 +959,11 @@ template <typename R>
 static int do_prepare_facet(swiftly_hip* h, const void* in, int64_t rows, int64_t yB, int64_t in_rs, int64_t in_cs,
                             void* out, int64_t out_rs, int64_t out_cs, int64_t off, int64_t row_gather_off,
                             const int32_t* out_rowmap, const int32_t* in_rowmap, int fold_other, int no_window,
-                            hipStream_t st) {
+                            hipStream_t st, bool real_in = false) {
     const int yN = (int)h->yN;
     RowsArgs<R> a;
     fill_io(a, in, rows, in_rs, in_cs, out, out_rs, out_cs);
+    a.real_in = real_in ? 1 : 0;  // `in` points to R, in_rs / in_cs count real elements
     a.ld = axis_map<R>(facet_in_padded_facet(*h, yB, off), invp<R>(h) + facet_lo(*h, yB));
     a.st = axis_map<R>(whole(yN));
     a.conj_ld = a.conj_st = 1;
@@ -1277,7 +1287,7 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
                                         int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                         int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                         int64_t other_axis_row0, const int32_t* win_d, int64_t nwin, int64_t win_full,
-                                        void* stream) {
+                                        void* stream, bool real_in = false) {
     const int fold_other_axis_window = other_axis_size > 0;
     if (!h || !in || !out) return fail(SWIFTLY_ERR_PARAM, "null argument");
     if (fold_other_axis_window && (other_axis_row0 < 0 || other_axis_row0 + rows > other_axis_size))
@@ -1285,6 +1295,10 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
                     (long long)rows, (long long)other_axis_size);
     DeviceGuard device_guard_(h->device);
     CHECK_DTYPE();
+    if (real_in) {  // float32 rows: the capability rule of SWIFTLY_FEATURE_REAL_FACETS
+        if (const std::string why = why_not_real_facets(*h, dtype); !why.empty())
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_real: %s", why.c_str());
+    }
     CHECK_FACET_SIZE();
     const int yN = (int)h->yN;
     if (dtype == SWIFTLY_C128) {
@@ -1317,13 +1331,14 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
         if (fold_other_axis_window && (other_axis_row0 != 0 || other_axis_size != rows))
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rows: row blocks need the split band layout (yN_size 16384 .. 65536)");
         return do_prepare_facet<float>(h, in, rows, facet_size, in_row_stride, 1, out, out_row_stride, 1, facet_off, INT64_MIN,
-                                       nullptr, nullptr, fold_other_axis_window, 0, (hipStream_t)stream);
+                                       nullptr, nullptr, fold_other_axis_window, 0, (hipStream_t)stream, real_in);
     }
     const Map facet = facet_in_padded_facet(*h, facet_size, facet_off);
     RowPassArgs r;
     std::memset(&r, 0, sizeof r);
     r.in = (const cx<float>*)in; r.out = (cx<float>*)out;
     r.in_pitch = in_row_stride; r.out_pitch = out_row_stride;
+    r.in_real = real_in ? 1 : 0;  // `in` points to float32, in_pitch counts real elements
     r.nrows = (int)rows;
     r.ld_a = facet.a; r.ld_len = facet.len; r.ld_c = facet.c; r.ld_mod = facet.mod;
     r.ld_win = h->invp_f + facet_lo(*h, facet_size);
@@ -1357,6 +1372,20 @@ int swiftly_hip_prepare_facet_band_rows(swiftly_hip_t* h, int dtype, const void*
                                         int64_t other_axis_row0, void* stream) {
     return prepare_facet_band_rows_impl(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
                                         band_len, other_axis_size, other_axis_row0, nullptr, 0, 0, stream);
+}
+
+int swiftly_hip_prepare_facet_band_rows_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                             int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                             int64_t band_start, int64_t band_len, int64_t other_axis_size,
+                                             int64_t other_axis_row0, void* stream) {
+    return prepare_facet_band_rows_impl(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
+                                        band_len, other_axis_size, other_axis_row0, nullptr, 0, 0, stream, true);
+}
+int swiftly_hip_prepare_facet_band_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                        int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                        int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream) {
+    return swiftly_hip_prepare_facet_band_rows_real(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
+                                                    band_start, band_len, fold_other_axis_window ? rows : 0, 0, stream);
 }
 
 // (r6, axis-1-first pipeline) prepare_facet_band_rows that finishes the contiguous axis COMPLETELY inside K1: one persistent

@@ -227,6 +227,16 @@ inline std::string why_not_split_band(const Sizes& s) {
     return reason("yN %lld keeps the whole padded axis in the plain band layout (split: %d .. %d)", (long long)s.yN,
                   1 << kSplitBandMinLogYN, 1 << kSplitBandMaxLogYN);
 }
+// real-valued (float32) facets into the forward K1 (prepare_facet_band_real / prepare_facet_band_rows_real): the complex64 band
+// pipeline with a power-of-two yN -- the row kernels of both band layouts have a real-load form, the radix-Q pass in front of
+// the Q * 2^k lengths has none, and there is no float64 -> complex128 form
+inline std::string why_not_real_facets(const Sizes& s, int dtype) {
+    if (dtype == SWIFTLY_C128) return "real facets: complex64 output only (no float64 -> complex128 load in the complex128 row kernels)";
+    if (dtype != SWIFTLY_C64) return reason("real facets: unknown dtype %d", dtype);
+    if (std::string why = why_not_band_pipeline(s, SWIFTLY_C64, 0, false); !why.empty()) return "real facets: " + why;
+    if (s.log_yN < 0) return reason("real facets: yN %lld is Q * 2^k: the radix-Q pass has no real load", (long long)s.yN);
+    return {};
+}
 // size part of prepare_facet_window_rows (the band, the facets and the windows are per call)
 inline std::string why_not_window_rows(const Sizes& s) {
     if (s.log_yN == kWindowRowsLogYN && s.log_m == kWindowRowsLogM && s.xM <= (int64_t(1) << kPlacedMaxLogXM)) return {};

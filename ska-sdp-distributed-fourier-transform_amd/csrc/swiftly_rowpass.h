@@ -87,6 +87,10 @@ struct RowPassArgs {
     const float* win_fn;          // Fn[m]
     const cx<float>* win_tw_m;    // twiddle table of length m and its compact sections for m / 64 points per lane
     const cx<float>* win_twc_m;
+    // REAL input (forward K1 of real-valued facets): `in` points to float32, in_pitch counts real elements; the launchers
+    // pick the REAL instances of row_pass_kernel / row_pass_band_kernel, which load half the bytes and set the imaginary
+    // parts to zero in registers.  Every value is the one the complex instance computes from the promoted row.
+    int in_real;
 };
 
 // physical column of logical (centred) column ck in a parity-split band buffer, or -1
@@ -137,7 +141,8 @@ __device__ const float kRowOne = 1.f;
 // MODE 0: mapped load (window, pad, shift), identity store   -- prepare_facet / prepare_subgrid style
 // MODE 1: identity load, mapped store (shift, crop, windows)  -- finish_facet / finish_subgrid style
 // MODE 2: both mapped
-template <class G, int MODE>
+// REAL (MODE 0 only): the input row is float32 (RowPassArgs::in_real), the imaginary parts are zeros in registers
+template <class G, int MODE, bool REAL = false>
 __global__ __launch_bounds__(G::NT) void row_pass_kernel(const RowPassArgs A, const cx<float>* __restrict__ gin,
                                                          cx<float>* __restrict__ gout,
                                                          const float* __restrict__ ld_win,
@@ -147,6 +152,7 @@ __global__ __launch_bounds__(G::NT) void row_pass_kernel(const RowPassArgs A, co
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int P = G::P, T = G::T, N = G::N;
     constexpr bool MAP_LD = MODE != 1, MAP_ST = MODE != 0;
+    static_assert(!REAL || MODE == 0, "real input: the mapped load of a prepare_* primitive");
     constexpr int CH = P < 8 ? P : 8;  // loads are issued in chunks of CH; products trail one chunk behind
     const int t = threadIdx.x;
     const int row = blockIdx.x;  // uniform
@@ -161,7 +167,8 @@ __global__ __launch_bounds__(G::NT) void row_pass_kernel(const RowPassArgs A, co
     if (A.in_rowmap) in_row = A.in_rowmap[in_row];
     const float alive = in_row < 0 ? 0.f : 1.f;  // a row absent from a compacted input (map entry < 0) reads as zeros
     if (in_row < 0) in_row = 0;
-    const cx<float>* __restrict__ in = gin + (long long)in_row * A.in_pitch;  // uniform base
+    const cx<float>* __restrict__ in = gin + (REAL ? 0ll : (long long)in_row * A.in_pitch);  // uniform base
+    const float* __restrict__ rin = reinterpret_cast<const float*>(gin) + (REAL ? (long long)in_row * A.in_pitch : 0ll);
     cx<float>* __restrict__ out = gout + (long long)row * A.out_pitch;
     const float sg_ld = A.conj_ld ? -1.f : 1.f;
     const float sg_st = A.conj_st ? -1.f : 1.f;
@@ -184,7 +191,10 @@ __global__ __launch_bounds__(G::NT) void row_pass_kernel(const RowPassArgs A, co
                     const int qs = ok ? q : 0;
                     unsigned idx = (unsigned)(qs + A.ld_c);
                     if (idx >= (unsigned)A.ld_mod) idx -= (unsigned)A.ld_mod;
-                    x[v] = in[idx];
+                    if constexpr (REAL)
+                        x[v] = cx<float>{rin[idx], 0.f};
+                    else
+                        x[v] = in[idx];
                     const float wv = lw[qs * lws];
                     w[v] = ok ? wv * alive : 0.f;
                 });
@@ -385,7 +395,14 @@ __global__ __launch_bounds__(G::NT) void row_pass_split_kernel(const RowPassArgs
 // per lane instead of NS of 8 bytes, the same bytes and bit-identical products; a shape probe of the kernel measured
 // 1.64 against 1.73 ms per facet (tools/k1_shape_probe.hip V=64: the load phase is bound by the NUMBER of vector-memory
 // instructions).
-template <class G, bool HAS_WIN, int ST, bool PAIR = false, int NSEG = 0, int CJ = -1, bool W4 = false>
+// REAL (forward K1 of real-valued facets, RowPassArgs::in_real): the row is float32.  Same element-to-lane map, segments,
+// window table and twiddles; every data load fetches half the bytes -- pair path: one 8-byte load of two adjacent reals over
+// a descriptor of ld_len * 4 bytes at half the byte offset (the addressing of the plain window load), else a 4-byte load --
+// and the window product is (x w, 0).  Operations on a zero imaginary part are exact, so the outputs are those of the
+// complex instance on the promoted row (up to the sign of a zero).  REAL = 2 (PAIR only): the pair geometry for a row whose
+// pitch is odd or whose base is only 4-byte aligned -- the lane's two adjacent reals through two 4-byte loads, everything
+// else as REAL = 1, so that the values do not depend on where the caller's rows lie in memory.
+template <class G, bool HAS_WIN, int ST, bool PAIR = false, int NSEG = 0, int CJ = -1, bool W4 = false, int REAL = 0>
 __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassArgs A, const cx<float>* __restrict__ gin,
                                                                  cx<float>* __restrict__ gout,
                                                                  const float* __restrict__ ld_win,
@@ -432,7 +449,9 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
     // space; rebuilding them from integers would turn every access into a FLAT one, and 64-bit per-lane
     // addresses cost two VGPRs and a v_lshl_add_u64 per access)
     in_row = __builtin_amdgcn_readfirstlane(in_row);
-    const char* __restrict__ inb = reinterpret_cast<const char*>(gin + (long long)in_row * A.in_pitch);
+    // (REAL: in_pitch counts 4-byte elements)
+    const char* __restrict__ inb = REAL ? reinterpret_cast<const char*>(reinterpret_cast<const float*>(gin) + (long long)in_row * A.in_pitch)
+                                        : reinterpret_cast<const char*>(gin + (long long)in_row * A.in_pitch);
     char* __restrict__ outb = reinterpret_cast<char*>(gout + (long long)__builtin_amdgcn_readfirstlane(row) * A.out_pitch);
     const char* __restrict__ winb = reinterpret_cast<const char*>(ld_win);
     const float sg_ld = A.conj_ld ? -1.f : 1.f;
@@ -450,7 +469,7 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
         static_assert(P == 32 && G::LOGN == 14, "pair loads: 512 threads x 32 points of a 16384-point half");
         constexpr int R1 = 16, SEG = H / R1;  // radix-16 first phase: points j + r*SEG, j = 2t + u
         const unsigned valid = dead ? 0u : (unsigned)A.ld_len;
-        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(inb), (short)0, (int)(valid << 3), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(inb), (short)0, (int)(valid << (REAL ? 2 : 3)), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(winb), (short)0, (int)(valid << 2), 0x00020000);
         const unsigned base8 = (unsigned)((2 * t + A.ld_a + (N >> 1) + rot) & (N - 1)) << 3;
         // W4: segment pairs of the re-laid-out window table, in the order of this loop -- (r, r + 16) while segment r + 16
@@ -467,9 +486,13 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
         // at once and every group consumed (window products, first-stage sum: 12 VGPRs shrink to 4 or 8) makes room for the
         // request of the next one, in program order pinned by scheduling barriers.
         constexpr bool PIPED = W4 && CJ == 1;
+        static_assert(!(PIPED && REAL == 2), "the load pipeline fetches two adjacent reals with one 8-byte load");
         if constexpr (PIPED) {
             constexpr int NGA = NB1, NG = NB1 + (R1 - NB1) / 2, PIPE = SWF_K1_PIPE < NG ? SWF_K1_PIPE : NG;
-            f32x4 gw[NG], g0[NG], g1[NG];
+            // (REAL: the data of a group is two 8-byte loads of two adjacent reals -- two VGPRs each instead of four)
+            using gdata = std::conditional_t<REAL, f32x2, f32x4>;
+            f32x4 gw[NG];
+            gdata g0[NG], g1[NG];
             auto issue = [&](auto gI) {
                 constexpr int g = decltype(gI)::value;
                 constexpr int r0 = g < NGA ? g : NGA + 2 * (g - NGA);           // first slot of the group
@@ -477,23 +500,36 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
                 gw[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w4, (g * T + t) << 4, 0, 0));
                 const unsigned o0 = (base8 + (unsigned)((s0 * SEG) << 3)) & (unsigned)((N << 3) - 1);
                 const unsigned o1 = (base8 + (unsigned)((s1 * SEG) << 3)) & (unsigned)((N << 3) - 1);
-                g0[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)o0, 0, 0));
-                g1[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)o1, 0, 0));
-            };
-            auto wmul = [&](f32x4 val, f32x2 w, cx<float>& e0, cx<float>& e1) {  // (x w, -y w) per point: window + conjugation
-                const f32x2 p0 = {val.x, val.y}, p1 = {val.z, val.w};
-                f32x2 q0, q1;
-                asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(q0) : "v"(p0), "v"(w));
-                asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_hi:[1,0]" : "=v"(q1) : "v"(p1), "v"(w));
-                e0 = pkc(q0);
-                e1 = pkc(q1);
+                if constexpr (REAL) {
+                    g0[g] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_in, (int)(o0 >> 1), 0, 0));
+                    g1[g] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_in, (int)(o1 >> 1), 0, 0));
+                } else {
+                    g0[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)o0, 0, 0));
+                    g1[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)o1, 0, 0));
+                }
             };
             auto consume = [&](auto gI) {
                 constexpr int g = decltype(gI)::value;
                 constexpr int r0 = g < NGA ? g : NGA + 2 * (g - NGA);
                 cx<float> a0[2], a1[2];
-                wmul(g0[g], f32x2{gw[g].x, gw[g].y}, a0[0], a0[1]);
-                wmul(g1[g], f32x2{gw[g].z, gw[g].w}, a1[0], a1[1]);
+                if constexpr (REAL) {  // (x w, 0) for the two points of each load
+                    const f32x2 p0 = g0[g] * f32x2{gw[g].x, gw[g].y}, p1 = g1[g] * f32x2{gw[g].z, gw[g].w};
+                    a0[0] = cx<float>{p0.x, 0.f};
+                    a0[1] = cx<float>{p0.y, 0.f};
+                    a1[0] = cx<float>{p1.x, 0.f};
+                    a1[1] = cx<float>{p1.y, 0.f};
+                } else {
+                    auto wmul = [](f32x4 val, f32x2 w, cx<float>& e0, cx<float>& e1) {  // (x w, -y w) per point: window + conjugation
+                        const f32x2 p0 = {val.x, val.y}, p1 = {val.z, val.w};
+                        f32x2 q0, q1;
+                        asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(q0) : "v"(p0), "v"(w));
+                        asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_hi:[1,0]" : "=v"(q1) : "v"(p1), "v"(w));
+                        e0 = pkc(q0);
+                        e1 = pkc(q1);
+                    };
+                    wmul(g0[g], f32x2{gw[g].x, gw[g].y}, a0[0], a0[1]);
+                    wmul(g1[g], f32x2{gw[g].z, gw[g].w}, a1[0], a1[1]);
+                }
                 static_for<0, 2>([&](auto uI) {
                     constexpr int u = decltype(uI)::value;
                     if constexpr (g < NGA) {
@@ -517,6 +553,9 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
 #endif
         static_for<0, R1>([&](auto rI) {
             constexpr int r = decltype(rI)::value;
+            // (all 32 segments of a real row: left alone the compiler requests all 64 two-VGPR loads at once and spills 12
+            // bytes; four iterations -- 16 loads -- at a time)
+            if constexpr (REAL == 1 && !SEGSKIP && r > 0 && r % 4 == 0) __builtin_amdgcn_sched_barrier(0);
             cx<float> a[2][2];  // [q][u]
             f32x2 w4[2] = {{0.f, 0.f}, {0.f, 0.f}};
             if constexpr (W4) {
@@ -535,14 +574,27 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
                 constexpr int q = decltype(qI)::value;
                 if constexpr (r + R1 * q < NS) {  // segment r + 16 q can hold data
                     const unsigned off8 = (base8 + (unsigned)((r * SEG + q * H) << 3)) & (unsigned)((N << 3) - 1);
-                    const f32x4 val = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)off8, 0, 0));
+                    f32x4 val;
+                    if constexpr (REAL == 2) {  // two adjacent reals of a row that is only 4-byte aligned: a load each
+                        const float re0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_in, (int)(off8 >> 1), 0, 0));
+                        const float re1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_in, (int)(off8 >> 1) + 4, 0, 0));
+                        val = f32x4{re0, 0.f, re1, 0.f};
+                    } else if constexpr (REAL) {  // two adjacent reals, imaginary parts zero
+                        const f32x2 re = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_in, (int)(off8 >> 1), 0, 0));
+                        val = f32x4{re.x, 0.f, re.y, 0.f};
+                    } else {
+                        val = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)off8, 0, 0));
+                    }
                     if constexpr (HAS_WIN) {
                         f32x2 w;
                         if constexpr (W4)
                             w = w4[q];
                         else
                             w = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_w, (int)(off8 >> 1), 0, 0));
-                        if constexpr (CJ >= 0) {  // one packed product per point; CJ = 1: (x w, -y w)
+                        if constexpr (REAL) {
+                            a[q][0] = cx<float>{val.x * w.x, 0.f};
+                            a[q][1] = cx<float>{val.z * w.y, 0.f};
+                        } else if constexpr (CJ >= 0) {  // one packed product per point; CJ = 1: (x w, -y w)
                             const f32x2 p0 = {val.x, val.y}, p1 = {val.z, val.w};
                             f32x2 r0, r1;
                             if constexpr (CJ == 1) {
@@ -601,7 +653,7 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
         }
     } else {
     const unsigned valid = dead ? 0u : (unsigned)A.ld_len;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(inb), (short)0, (int)(valid << 3), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(inb), (short)0, (int)(valid << (REAL ? 2 : 3)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(winb), (short)0, (int)(valid << 2), 0x00020000);
     // byte offset of plain index j = t (centred index j ^ N/2 = j + N/2 mod N), then + (v T + q H) * 8 mod 8 N
     const unsigned base8 = (unsigned)((t + A.ld_a + (N >> 1) + rot) & (N - 1)) << 3;
@@ -612,10 +664,14 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
             constexpr int q = decltype(qI)::value;
             if constexpr (v + P * q < NS) {  // segment v + P q can hold data
                 const unsigned off8 = (base8 + (unsigned)((v * T + q * H) << 3)) & (unsigned)((N << 3) - 1);
-                const f32x2 val = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_in, (int)off8, 0, 0));
+                f32x2 val;
+                if constexpr (REAL)
+                    val = f32x2{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_in, (int)(off8 >> 1), 0, 0)), 0.f};
+                else
+                    val = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_in, (int)off8, 0, 0));
                 if constexpr (HAS_WIN) {
                     const float w = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_w, (int)(off8 >> 1), 0, 0));
-                    a[q] = cx<float>{val.x * w, val.y * w};
+                    a[q] = cx<float>{val.x * w, REAL ? 0.f : val.y * w};
                 } else {
                     a[q] = cx<float>{val.x, val.y};
                 }

@@ -80,6 +80,9 @@ struct RowsArgs {
     // the next primitive would apply along the other axis: windows commute with transforms along the
     // orthogonal axis).
     const R* row_win;
+    // REAL input (prepare_facet of a real-valued facet, plain band layout): `in` points to R, the input strides count real
+    // elements; launch_fft_rows picks the REAL_IN instance, which sets the imaginary parts to zero in registers
+    int real_in;
 };
 
 // Per-batch-item overrides of the map offsets (passed by value as a kernel
@@ -97,7 +100,7 @@ struct kOneTable {
 template <typename R>
 __device__ const R kOneTable<R>::value = (R)1;
 
-template <class G, typename R>
+template <class G, typename R, bool REAL_IN = false>
 __global__ __launch_bounds__(G::NT) void fft_rows_kernel(const RowsArgs<R> A, const OffTab tab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int P = G::P, T = G::T, RB = G::RB;
@@ -143,7 +146,15 @@ __global__ __launch_bounds__(G::NT) void fft_rows_kernel(const RowsArgs<R> A, co
     const bool absent = in_row < 0;  // row absent from a compacted input (map entry < 0): reads as zeros
     if (absent) in_row = 0;
     const int b = blockIdx.y;
-    const cx<R>* __restrict__ in = A.in + in_row * A.in_rs + (long long)o * A.in_os + (long long)b * A.in_bs;
+    const long long in_base = in_row * A.in_rs + (long long)o * A.in_os + (long long)b * A.in_bs;
+    const cx<R>* __restrict__ in = A.in + (REAL_IN ? 0ll : in_base);
+    const R* __restrict__ rin = reinterpret_cast<const R*>(A.in) + (REAL_IN ? in_base : 0ll);
+    auto load_in = [&](size_t e) -> cx<R> {
+        if constexpr (REAL_IN)
+            return cx<R>{rin[e], (R)0};
+        else
+            return in[e];
+    };
     cx<R>* __restrict__ out = A.out + row * A.out_rs + (long long)o * A.out_os + (long long)b * A.out_bs;
     const int ld_a = (tab.use & 1) ? tab.ld_a[b] : A.ld.a;
     const int ld_c = (tab.use & 2) ? tab.ld_c[b] : A.ld.c;
@@ -166,7 +177,7 @@ __global__ __launch_bounds__(G::NT) void fft_rows_kernel(const RowsArgs<R> A, co
     if (A.raw_ld) {  // uniform over the launch
         static_for<0, P>([&](auto vI) {
             constexpr int v = decltype(vI)::value;
-            x[v] = in[(size_t)((unsigned)(t + v * T) * A.in_cs)];
+            x[v] = load_in((size_t)((unsigned)(t + v * T) * A.in_cs));
         });
         static_for<0, P>([&](auto vI) {
             constexpr int v = decltype(vI)::value;
@@ -184,7 +195,7 @@ __global__ __launch_bounds__(G::NT) void fft_rows_kernel(const RowsArgs<R> A, co
             const int qs = ok ? q : 0;
             int idx = qs + ld_c;
             if (idx >= A.ld.mod) idx -= A.ld.mod;
-            cx<R> val = in[(size_t)((unsigned)idx * A.in_cs)];
+            cx<R> val = load_in((size_t)((unsigned)idx * A.in_cs));
             R w = win1[qs * w1s] * win2[qs * w2s];
             w = ok ? w * live_f : (R)0;
             val.x *= w;

@@ -17,7 +17,7 @@ C64, C128 = 0, 1
 ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
 # swiftly_hip_supports / swiftly_hip_limit (include/swiftly_hip.h)
 (FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
- FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE) = range(8)
+ FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE, FEATURE_REAL_FACETS) = range(9)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None
@@ -110,6 +110,11 @@ def _declare(lib):
     lib.swiftly_hip_prepare_facet_band.argtypes = [vp, c_int, vp, i64, i64, i64, vp, i64, i64, i64, i64, c_int, vp]
     lib.swiftly_hip_prepare_facet_band_rows.restype = c_int
     lib.swiftly_hip_prepare_facet_band_rows.argtypes = [vp, c_int, vp, i64, i64, i64, vp, i64, i64, i64, i64, i64, i64, vp]
+    # float32 rows into the forward K1 (same arguments; `in` is real, the row stride counts reals, dtype = output type)
+    lib.swiftly_hip_prepare_facet_band_real.restype = c_int
+    lib.swiftly_hip_prepare_facet_band_real.argtypes = list(lib.swiftly_hip_prepare_facet_band.argtypes)
+    lib.swiftly_hip_prepare_facet_band_rows_real.restype = c_int
+    lib.swiftly_hip_prepare_facet_band_rows_real.argtypes = list(lib.swiftly_hip_prepare_facet_band_rows.argtypes)
     lib.swiftly_hip_prepare_facet_columns.restype = c_int
     lib.swiftly_hip_prepare_facet_columns.argtypes = [vp, c_int, vp, i64, i64, i64, i64, pi64, i64, i64, i64, vp, i64, i64, vp, vp]
     lib.swiftly_hip_transform_contributions.restype = c_int

@@ -577,6 +577,21 @@ class SwiftlyCoreHip:
         given, for ``n_facets`` facets); complex64: the answer of :py:meth:`supports_fused_subgrid`."""
         return self._supports(_lib.FEATURE_SPLIT_PREPARE, dtype, n_facets)
 
+    def supports_real_facets(self):
+        """True when the forward K1 takes real-valued (float32) facets as they are (``prepare_facet_band`` with a float32
+        tensor; ``swiftly_hip_prepare_facet_band_real``): the complex64 band pipeline with a power-of-two ``yN_size``.  After a
+        False ``_lib.last_error()`` says why."""
+        return self._supports(_lib.FEATURE_REAL_FACETS, _torch().complex64)
+
+    def _real_rows_match_promoted(self, facet_size):
+        """Does the real-load K1 give a row of ``facet_size`` reals bit for bit the values of the promoted row?  Not at
+        ``yN_size`` 32768 when the row can cover more than 24 of the 32 load segments of 1024 points (``facet_size`` above
+        23552): the all-segment instances leave the contraction of the window products to the compiler, which decides
+        differently for the real and the complex form (last-bit differences; DESIGN.md section 4, "K1 on real-valued
+        facets", the exception).  ``prepare_facet_band``
+        and ``SwiftlyForward`` promote such facets as before."""
+        return not (self.yN_size == 32768 and int(facet_size) > 23552)
+
     def band_for_offsets(self, subgrid_offs):
         """Smallest cyclic range ``(start, length)`` of centred indices of the padded facet axis that contains
         the ``xM_yN_size`` window of every given subgrid offset (core.py:243-253); ``(0, yN_size)`` = all."""
@@ -593,19 +608,35 @@ class SwiftlyCoreHip:
         device facet, keeping only the band of output columns (parity-split layout, see include/swiftly_hip.h),
         times the 1/PSWF window of axis 0 when ``fold_other_axis_window``.  ``rows_of=(size, row0)``: ``facet`` is
         the block of rows ``[row0, row0 + facet.shape[0])`` of a facet with ``size`` rows -- the axis-0 window is that
-        facet's (``swiftly_hip_prepare_facet_band_rows``)."""
+        facet's (``swiftly_hip_prepare_facet_band_rows``).
+
+        A real-valued facet may be passed as a float32 tensor where :py:meth:`supports_real_facets` says so: the kernel
+        loads the reals and the complex64 output holds the values the promoted facet gives (``NotImplementedError`` with
+        the library's reason elsewhere)."""
         torch = _torch()
         if facet.dim() != 2 or facet.stride(1) != 1:
             raise ValueError("prepare_facet_band needs a row-major 2-D device tensor")
+        if facet.dtype not in (torch.complex64, torch.complex128, torch.float32):
+            raise ValueError(f"prepare_facet_band takes complex64, complex128 or float32 facets, not {facet.dtype}")
+        real = facet.dtype == torch.float32
+        if real and self.supports_real_facets() and not self._real_rows_match_promoted(facet.shape[1]):
+            facet, real = facet.to(torch.complex64), False  # (keeps the values of the promoted facet: see there)
+        out_dtype = torch.complex64 if real else facet.dtype
+        code = _lib.C64 if real else self._code(facet)
+        lib = self._lib
+        band_rows = lib.swiftly_hip_prepare_facet_band_rows_real if real else lib.swiftly_hip_prepare_facet_band_rows
+        band_whole = lib.swiftly_hip_prepare_facet_band_real if real else lib.swiftly_hip_prepare_facet_band
         ncols = self.band_columns(band)
         if out is None:
-            out = torch.empty((facet.shape[0], ncols), dtype=facet.dtype, device=self._device)
+            out = torch.empty((facet.shape[0], ncols), dtype=out_dtype, device=self._device)
         elif tuple(out.shape) != (facet.shape[0], ncols) or out.stride(1) != 1:
             raise ValueError(f"Output array has shape {tuple(out.shape)}, expected {(facet.shape[0], ncols)}!")
+        elif real and out.dtype != out_dtype:
+            raise ValueError(f"Output array is {out.dtype}, a float32 facet needs {out_dtype}!")
         if rows_of is not None:
             _lib.check(
-                self._lib.swiftly_hip_prepare_facet_band_rows(
-                    self._handle, self._code(facet), ctypes.c_void_p(facet.data_ptr()), int(facet.shape[0]),
+                band_rows(
+                    self._handle, code, ctypes.c_void_p(facet.data_ptr()), int(facet.shape[0]),
                     int(facet.shape[1]), facet.stride(0), ctypes.c_void_p(out.data_ptr()), out.stride(0), int(facet_off),
                     int(band[0]), int(band[1]), int(rows_of[0]) if fold_other_axis_window else 0, int(rows_of[1]),
                     self._stream(),
@@ -613,8 +644,8 @@ class SwiftlyCoreHip:
             )
             return out
         _lib.check(
-            self._lib.swiftly_hip_prepare_facet_band(
-                self._handle, self._code(facet), ctypes.c_void_p(facet.data_ptr()), int(facet.shape[0]),
+            band_whole(
+                self._handle, code, ctypes.c_void_p(facet.data_ptr()), int(facet.shape[0]),
                 int(facet.shape[1]), facet.stride(0), ctypes.c_void_p(out.data_ptr()), out.stride(0), int(facet_off),
                 int(band[0]), int(band[1]), int(bool(fold_other_axis_window)), self._stream(),
             )

@@ -355,6 +355,7 @@ class DistributedForward:
     def __init__(self, swiftly_config, facet_configs, facet_data, lru_forward=1, group=None, subgrid_configs=None,
                  wave_axis=None, dtype=None, rank_world=None, cooperative=True, whole_waves=False):
         from .api import SwiftlyForward, preferred_wave_axis  # pylint: disable=import-outside-toplevel
+        from .forward import _PromotingForward  # pylint: disable=import-outside-toplevel
 
         torch = _torch()
         self.group = group
@@ -392,7 +393,8 @@ class DistributedForward:
         local = self.sharding.local_facets
         self.local = None
         if local or not self.sharding.coop:
-            self.local = SwiftlyForward(
+            # (float32 facets are promoted here as in pack_coop: no real form in the multi-GPU classes)
+            self.local = _PromotingForward(
                 swiftly_config,
                 [(self.facet_configs[j], facet_data[j]) for j in local],
                 lru_forward=lru_forward,

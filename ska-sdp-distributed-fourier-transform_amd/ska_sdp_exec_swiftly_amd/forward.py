@@ -41,7 +41,10 @@ class SwiftlyForward(WavePrefetch):
     :param swiftly_config: SwiftlyConfig
     :param facet_tasks: list of ``(FacetConfig, facet_data)``; data may be a
         numpy array or a torch tensor (complex64 or complex128; it is uploaded
-        once and stays in HBM)
+        once and stays in HBM).  Real-valued facets given as float32 stay float32 -- on the host, on the wire and in HBM,
+        half the bytes -- when every facet is float32, the object runs ``wave_axis == 1`` with a K1 that loads reals
+        (``core.supports_real_facets()``, not the whole-row K1 of ``axis1_first=True``); see :py:attr:`facet_dtype`.
+        In every other case they are promoted to complex64
     :param lru_forward: number of subgrid columns (distinct ``off0``) whose
         prepared facet columns ``NMBF_BF`` are kept
     :param queue_size: bound on unfinished subgrid tasks (reference
@@ -87,7 +90,6 @@ class SwiftlyForward(WavePrefetch):
         # the full-facet transform of facet j
         self._ingest = _FacetIngest(self.core)
         self._facet_info = [self._ingest.add(data) for _, data in facet_tasks]
-        self._ingest.prefetch(0)
         dtypes = {info[0] for info in self._facet_info}
         if len(dtypes) > 1:
             raise ValueError("all facets must have the same dtype")
@@ -116,6 +118,28 @@ class SwiftlyForward(WavePrefetch):
         self._results = {}
         self._result_bytes = 0
         self._result_budget = int(float(os.environ.get("SWIFTLY_RESULT_CACHE_GB", "16")) * 2**30)
+        # float32 facets: kept as they are when this object's K1 loads reals, promoted to complex64 otherwise -- decided
+        # before the first upload
+        self._ingest.settle(self._keep_real_facets and self._k1_loads_reals())
+        self._ingest.prefetch(0)
+
+    @property
+    def facet_dtype(self):
+        """dtype of the facets as they are resident: ``torch.float32`` when real-valued facets were kept real, else
+        :py:attr:`dtype` (the complex dtype everything downstream of K1 computes in)"""
+        return _torch().float32 if self._ingest.real else self.dtype
+
+    def _k1_loads_reals(self):
+        """would K1 of this object take float32 facets as they are?  Every facet float32, the contiguous-axis-first
+        pipeline (``wave_axis == 1``), a real-load form of its row kernel for these sizes (``core.supports_real_facets``),
+        and not axis-1-first mode 2, whose whole-row K1 has no real form."""
+        core = self.core
+        if not (self._ingest.all_float32 and self.wave_axis == 1 and core.supports_real_facets()):
+            return False
+        if not all(core._real_rows_match_promoted(info[1][1]) for info in self._facet_info):
+            return False
+        band = core.band_for_offsets([sg.off1 for sg in self._plan]) if self._plan is not None else (0, core.yN_size)
+        return self._axis1_mode_for(band, real=False) != 2
 
     # -- tables derived from the plan: each built on first use by ONE walk over the plan (505 configs x 25 waves on every
     # pass otherwise), and not at all for objects that never need it
@@ -490,15 +514,25 @@ class SwiftlyForward(WavePrefetch):
     #: may the axis-1-first pipeline fuse the contiguous-axis finish into K1?  The multi-GPU classes switch this off for the
     #: objects whose band buffers come from the band-row exchange (cooperative facets).
     axis1_fused = True
+    #: may float32 facets stay float32 (see the constructor)?  The multi-GPU classes, which have no real form, switch it off.
+    _keep_real_facets = True
 
     def _choose_axis1_mode(self):
+        """the axis-1-first mode for the installed band and the facets as they are resident"""
+        return self._axis1_mode_for(self._band, self._ingest.real)
+
+    def _axis1_mode_for(self, band, real):
         """0: default order; 1: axis-1-first with a row pass per wave (core.finish_axis1_rows; ``axis1_first="rows"``, or
         ``True`` where 2 is not available); 2: axis-1-first with the finish in the epilogue of K1 (``axis1_first=True``;
         needs a plan -- the windows are the plan's waves -- and a configuration with core.supports_window_rows)."""
         if not axis1_first_active(self.core, self.wave_axis, self.dtype):
             return 0
-        if (self.core.axis1_first is True and self.axis1_fused and self._plan is not None and self._band is not None and
-                self.core.supports_window_rows(self._band, self._facet_info[0][1][1], [cfg.off1 for cfg in self.facet_configs],
+        # (``real``: the facets are resident as float32.  The whole-row K1 of mode 2 has no real-load form: _k1_loads_reals
+        # keeps them real only when the plan's own band does not lead to mode 2, and band buffers installed from outside
+        # never get it)
+        if (self.core.axis1_first is True and self.axis1_fused and self._plan is not None and band is not None and
+                not real and
+                self.core.supports_window_rows(band, self._facet_info[0][1][1], [cfg.off1 for cfg in self.facet_configs],
                                                n_windows=len(self._planned_keys))):
             return 2
         return 1
@@ -699,6 +733,12 @@ class SwiftlyForward(WavePrefetch):
         tools/experiments/ since r4.)"""
         self._check_planned(sgs)
         return _finish_from_G(self.core, self._facet_side(sgs), self.facet_configs, sgs, placed=self._placed())
+
+
+class _PromotingForward(SwiftlyForward):
+    """``SwiftlyForward`` as the multi-GPU classes own it: float32 facets are always promoted to complex64"""
+
+    _keep_real_facets = False
 
 
 def axis1_first_active(core, wave_axis, dtype):

@@ -55,13 +55,21 @@ class _FacetIngest:
     a whole 4 GB facet would cost more than the copy): ``ready(j)`` makes the CURRENT stream wait for facet ``j``
     (a stream-side wait) and returns the tensor; ``prefetch(j)`` starts the upload of facet ``j`` -- the streaming
     classes call it for facet j+1 right after queueing the full-facet transform of facet j, so the transfer runs
-    under that kernel."""
+    under that kernel.
+
+    Real-valued facets: a float32 facet (host array or device tensor) is registered as it is and reported with the complex
+    dtype it computes in; ``settle(keep_real)`` -- called by the owner once all facets are registered, before the first upload
+    -- either keeps all of them float32 (the owner's K1 loads reals: half the resident bytes and half the upload) or promotes
+    them to complex64 the way every other real input is."""
 
     SLAB = 128 << 20
 
     def __init__(self, core):
         self.core = core
         self.host, self.tensors, self.events = [], [], []
+        self._float32 = []    # per facet: registered as float32 (promotion pending until settle)
+        self._settled = False
+        self.real = False     # the facets stay float32 (settle(True))
         self._stream = None
         self._staging = None
         self._staging_free = None
@@ -69,35 +77,76 @@ class _FacetIngest:
     def add(self, data):
         """register a facet; returns (dtype, shape, is_row_major)"""
         torch = _torch()
+        if self._settled:
+            raise RuntimeError("facets must be registered before settle()")
+        is_float32 = False
         if isinstance(data, torch.Tensor):
-            ten, _ = self.core._as_device(data)  # pylint: disable=protected-access
+            # (a float32 tensor K1 could not read in place -- not 2-D row-major -- is promoted at once, as it always was)
+            is_float32 = data.dtype == torch.float32 and data.dim() == 2 and data.stride(-1) == 1
+            ten = data if is_float32 else self.core._as_device(data)[0]  # pylint: disable=protected-access
             self.host.append(None)
             self.tensors.append(ten)
         else:
             arr = numpy.asarray(data)
-            if not numpy.iscomplexobj(arr):
-                arr = arr.astype(numpy.complex64 if arr.dtype == numpy.float32 else numpy.complex128)
+            is_float32 = arr.dtype == numpy.float32
+            if is_float32:
+                pass
+            elif not numpy.iscomplexobj(arr):
+                arr = arr.astype(numpy.complex128)
             elif arr.dtype not in (numpy.complex64, numpy.complex128):
                 arr = arr.astype(numpy.complex128)
-            self.host.append(numpy.ascontiguousarray(arr))
+            self.host.append(arr if is_float32 else numpy.ascontiguousarray(arr))
             self.tensors.append(None)
         self.events.append(None)
+        self._float32.append(is_float32)
         j = len(self.tensors) - 1
         src = self.tensors[j] if self.tensors[j] is not None else self.host[j]
-        tdt = src.dtype if self.tensors[j] is not None else (
-            torch.complex64 if src.dtype == numpy.complex64 else torch.complex128
-        )
+        if is_float32:
+            tdt = torch.complex64  # the dtype it computes in, kept real or not
+        else:
+            tdt = src.dtype if self.tensors[j] is not None else (
+                torch.complex64 if src.dtype == numpy.complex64 else torch.complex128
+            )
         row_major = src.stride(-1) == 1 if self.tensors[j] is not None else True
         return tdt, tuple(src.shape), row_major
+
+    @property
+    def all_float32(self):
+        """every registered facet is float32 (and there is one)"""
+        return bool(self._float32) and all(self._float32)
+
+    def settle(self, keep_real):
+        """Decide what the float32 facets become: with ``keep_real`` (all of them must be float32) they stay float32 -- a
+        device tensor in place, a host array staged and uploaded as float32; otherwise each is promoted to complex64 exactly as
+        a real input always was.  Idempotent; the first upload settles with ``False`` when the owner never asked."""
+        if self._settled:
+            return
+        self._settled = True
+        self.real = bool(keep_real) and self.all_float32
+        for j, is_float32 in enumerate(self._float32):
+            if not is_float32:
+                continue
+            if self.tensors[j] is not None:
+                ten = self.tensors[j]
+                if self.real:
+                    self.tensors[j] = ten if ten.device == self.core.device else ten.to(self.core.device)
+                else:
+                    self.tensors[j] = self.core._as_device(ten)[0]  # pylint: disable=protected-access
+            else:
+                arr = self.host[j] if self.real else self.host[j].astype(numpy.complex64)
+                self.host[j] = numpy.ascontiguousarray(arr)
 
     def prefetch(self, j):
         """start the upload of facet ``j`` (no-op for device facets / out of range / already started)"""
         torch = _torch()
+        self.settle(False)
         if j < 0 or j >= len(self.tensors) or self.tensors[j] is not None:
             return
         core = self.core
         arr = self.host[j]
-        tdt = torch.complex64 if arr.dtype == numpy.complex64 else torch.complex128
+        tdt = {numpy.dtype(numpy.float32): torch.float32, numpy.dtype(numpy.complex64): torch.complex64}.get(
+            arr.dtype, torch.complex128
+        )
         dev = torch.empty(arr.shape, dtype=tdt, device=core.device)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=core.device)
