@@ -110,9 +110,12 @@ enum {
     SWIFTLY_FEATURE_SPLIT_PREPARE = 7,          /* split_prepare_facets + wave_split_subgrids (dtype, n_facets): complex64 as
                                                    FUSED_SUBGRID; complex128 for (m, xM) = (128, 256), (128, 1024), (256, 512),
                                                    (256, 1024), (512, 1024), up to 64 facets */
-    SWIFTLY_FEATURE_REAL_FACETS = 8             /* prepare_facet_band_real / prepare_facet_band_rows_real (dtype = the OUTPUT
+    SWIFTLY_FEATURE_REAL_FACETS = 8,            /* prepare_facet_band_real / prepare_facet_band_rows_real (dtype = the OUTPUT
                                                    type): the sizes of BAND_PIPELINE in complex64 with a power-of-two yN_size;
                                                    no complex128, no Q * 2^k.  The gate both entry points refuse through */
+    SWIFTLY_FEATURE_REAL_FACETS_OUT = 9         /* finish_facet_band_real (dtype = the INPUT type): the sizes of BACKWARD_BAND
+                                                   in complex64 with a power-of-two yN_size; no complex128, no Q * 2^k.  The
+                                                   gate the entry point refuses through */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -596,6 +599,18 @@ int swiftly_hip_band_zero_untouched(swiftly_hip_t* h, int dtype, void* bands, in
 int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
                                   int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
                                   int64_t facet_off, int64_t facet_size, const void* mask, void* stream);
+/* finish_facet_band for a REAL-VALUED facet (an image): the entry point above with `out` pointing to FLOAT32, out_row_stride
+ * counting real elements, and `dtype` the type of the INPUT band rows (SWIFTLY_C64).  The row kernels compute what the complex
+ * entry point computes and store the real part only (4 bytes per pixel; the arithmetic that only feeds the imaginary part is
+ * not done): `out` holds, bit for bit, the real parts of what swiftly_hip_finish_facet_band gives for the same band rows,
+ * whatever out_row_stride and the alignment of `out` -- the transform is chosen from the arguments both entry points share,
+ * never from the destination.  Any out_row_stride >= facet_size (odd ones included) and any 4-byte-aligned `out` are taken;
+ * out_row_stride < facet_size (overlapping rows) is SWIFTLY_ERR_PARAM.
+ * Sizes: SWIFTLY_FEATURE_REAL_FACETS_OUT (complex64 backward band, power-of-two yN_size), SWIFTLY_ERR_UNSUPPORTED otherwise;
+ * the checks of the arguments are those of swiftly_hip_finish_facet_band. */
+int swiftly_hip_finish_facet_band_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                       int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
+                                       int64_t facet_off, int64_t facet_size, const void* mask, void* stream);
 
 /* -- point-source truths and RMSE checks on the device (handle-free; work is enqueued on `stream` of the current device).
  *    The reference checks itself with point sources: it builds facets with make_facet, and compares every subgrid with

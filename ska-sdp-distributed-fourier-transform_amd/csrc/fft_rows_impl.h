@@ -26,6 +26,16 @@ static int launch_one(const RowsArgs<R>& a, const OffTab& tab, hipStream_t s) {
         else
             return -1;
     }
+    if (a.real_out) {
+        // real output: complex64 finish_facet of the plain band layout (swiftly_caps.h, why_not_real_facets_out), 64 .. 4096
+        // points (8192 and longer: the lean row kernels, row_pass.hip); the mapped store only
+        if constexpr (sizeof(R) == 4 && LOGN >= kBackwardBandMinLogYN && LOGN < 13) {
+            if (a.raw_st || a.st_rowmap || a.accumulate) return -1;
+            return launch_lds<fft_rows_kernel<G, R, false, true>, G::LDS_BYTES>(dim3(grid, a.nbatch > 0 ? a.nbatch : 1), dim3(G::NT), s, a, tab);
+        } else {
+            return -1;
+        }
+    }
     return launch_lds<fft_rows_kernel<G, R>, G::LDS_BYTES>(dim3(grid, a.nbatch > 0 ? a.nbatch : 1), dim3(G::NT), s, a, tab);
 }
 

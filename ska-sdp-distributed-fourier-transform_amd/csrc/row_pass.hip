@@ -40,6 +40,21 @@ int launch_row_pass(int logn, int mode, const RowPassArgs& a, hipStream_t s) {
         return launch_lds<row_pass_kernel<G, 0, true>, G::LDS_BYTES>(dim3((unsigned)a.nrows), dim3(G::NT), s, a, a.in, a.out, a.ld_win,
                                                                     a.st_win, a.st_win2, a.tw);
     }
+    if (a.out_real) {  // real output: the mapped store of 8192- and 16384-point rows (longer rows: launch_row_pass_band_n)
+        if (mode == 0 || a.accumulate) return -1;
+#define SWF_REAL_ST(LOGN, MODE)                                                                                              \
+    if (logn == LOGN && mode == MODE) {                                                                                      \
+        using G = typename RGeoFor<LOGN>::type;                                                                              \
+        return launch_lds<row_pass_kernel<G, MODE, false, true>, G::LDS_BYTES>(dim3((unsigned)a.nrows), dim3(G::NT), s, a, a.in, \
+                                                                               a.out, a.ld_win, a.st_win, a.st_win2, a.tw); \
+    }
+        SWF_REAL_ST(13, 1)
+        SWF_REAL_ST(13, 2)
+        SWF_REAL_ST(14, 1)
+        SWF_REAL_ST(14, 2)
+#undef SWF_REAL_ST
+        return -1;
+    }
     switch (logn) {
         case 13: return launch_one<13>(mode, a, s);
         case 14: return launch_one<14>(mode, a, s);
@@ -92,6 +107,22 @@ static int launch_band_inst(const RowPassArgs& a, unsigned blocks, const cx<floa
                             hipStream_t s) {
     return launch_lds<row_pass_band_kernel<G, WIN, ST, PAIR, NSEG, CJ, W4, REAL>, G::LDS_BYTES>(dim3(blocks), dim3(G::NT), s, a,
                                                                                                 a.in, a.out, a.ld_win, tw14, tw_full);
+}
+// Mapped store (ST = 2, no load window) of the instance <G, PAIR, NSEG, CJ>: the complex form, or for RowPassArgs::out_real
+// its real-store twin.  Every mapped-store launch goes through here, so the instance -- geometry, segment count, rotation --
+// is chosen before, and never from, the type of the destination.
+template <class G, bool PAIR, int NSEG, int CJ = -1>
+static int launch_band_finish(const RowPassArgs& a, unsigned blocks, const cx<float>* tw14, const cx<float>* tw_full,
+                              hipStream_t s) {
+    if (!a.out_real) return launch_band_inst<G, PAIR, false, 2, NSEG, CJ>(a, blocks, tw14, tw_full, s);
+    // real twins exist where a finish can arrive: the 512 x 32 geometry of the 32768-point rows and the 65536-point geometry
+    if constexpr (G::LOGP == 5) {
+        if (a.accumulate) return -1;
+        return launch_lds<row_pass_band_kernel<G, false, 2, PAIR, NSEG, CJ, false, 0, true>, G::LDS_BYTES>(
+            dim3(blocks), dim3(G::NT), s, a, a.in, a.out, a.ld_win, tw14, tw_full);
+    } else {
+        return -1;
+    }
 }
 
 // -- re-laid-out load windows (Win4Cache, swiftly_rowpass.h) ------------------------------------------------------
@@ -214,13 +245,19 @@ static int launch_band_geo(const RowPassArgs& a0, const cx<float>* tw14, const c
 #define SWF_TRY_SEG_C(NS)                                                                \
     if (a.twc && run <= NS) {                                                            \
         a.seg_rot = first;                                                               \
-        return launch_band_inst<GB, PAIR, false, 2, NS, 0>(a, blocks, tw14, tw_full, s); \
+        return launch_band_finish<GB, PAIR, NS, 0>(a, blocks, tw14, tw_full, s);         \
     }
                 SWF_TRY_SEG_C(13)
                 SWF_TRY_SEG_C(16)
 #undef SWF_TRY_SEG_C
-                SWF_TRY_SEG(false, 2, 13, 0)
-                SWF_TRY_SEG(false, 2, 16, 0)
+#define SWF_TRY_SEG_FIN(NS)                                                         \
+    if (run <= NS) {                                                                \
+        a.seg_rot = first;                                                          \
+        return launch_band_finish<G, PAIR, NS, 0>(a, blocks, tw14, tw_full, s);     \
+    }
+                SWF_TRY_SEG_FIN(13)
+                SWF_TRY_SEG_FIN(16)
+#undef SWF_TRY_SEG_FIN
             }
         } else {
             if (a.band_len > 0 && a.ld_win && inv) {
@@ -230,7 +267,8 @@ static int launch_band_geo(const RowPassArgs& a0, const cx<float>* tw14, const c
 #undef SWF_TRY_SEG
     }
 #define SWF_LAUNCH_BAND(WIN, ST) launch_band_inst<G, PAIR, WIN, ST, 0>(a, blocks, tw14, tw_full, s)
-    if (a.band_len < 0) return SWF_LAUNCH_BAND(false, 2);  // mapped (crop + window) store: finish_* primitives
+    if (a.band_len < 0) return launch_band_finish<G, PAIR, 0>(a, blocks, tw14, tw_full, s);  // mapped (crop + window) store: finish_* primitives
+    if (a.out_real) return -1;  // real output: the mapped store only
     if (a.ld_win) return band ? SWF_LAUNCH_BAND(true, 1) : SWF_LAUNCH_BAND(true, 0);
     return band ? SWF_LAUNCH_BAND(false, 1) : SWF_LAUNCH_BAND(false, 0);
 #undef SWF_LAUNCH_BAND
@@ -308,6 +346,7 @@ int launch_row_pass_band_n(int logn, const RowPassArgs& a, const cx<float>* tw_h
                            Win4Cache* w4) {
     if (a.nrows <= 0) return 0;
     if (a.in_real) return launch_band_real(logn, a, tw_half, tw_full, s, w4);
+    if (a.out_real && (a.band_len >= 0 || a.win_full)) return -1;  // real output: the mapped store (launch_band_finish) only
     if (a.win_full) {
         // window-rows store (whole-row kernel): 32768-point rows, 512-column windows, 16-byte loads
         if (logn != 15 || a.win_logm != 9 || a.nwin <= 0 || !a.win_d || a.band_len <= 0) return -2;

@@ -482,6 +482,7 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
     r.rm_mod = a.rm_mod; r.rm_inner = a.rm_inner; r.rm_outer = a.rm_outer; r.rm_full = a.rm_full;
     r.in_rowmap = a.in_rowmap;
     r.in_real = a.real_in;
+    r.out_real = a.real_out;
     if (a.st_rowmap) return false;
     r.row_win = a.row_win;
     if (a.row_win && logn > kRowPassMaxLog) return false;  // the two-workgroup kernels take it through prepare_facet_band only
@@ -661,6 +662,9 @@ static int run_rows_chunk(swiftly_hip* h, int logn, RowsArgs<R>& a, const OffTab
         // real input: only the single-launch generic kernel is left (launch_fft_rows refuses lengths without a real instance)
         if (a.real_in && (sub || a.rowfast || a.raw_ld))
             return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: real input reaches a decomposed transform of 2^%d points", logn);
+        // ... and so for real output (every lean row kernel that takes it has launched above)
+        if (a.real_out && (sub || a.rowfast || a.raw_st || a.st_rowmap || a.accumulate || logn >= kRowPassMinLog))
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: real output reaches a transform of 2^%d points without a real store", logn);
     }
     if (logn > kMaxLogNFloat && sizeof(R) == 4)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "transform length 65536 is only supported for complex64 prepare_* / finish_* "
@@ -1043,10 +1047,11 @@ static int do_extract_from_subgrid(swiftly_hip* h, const void* in, int64_t rows,
 template <typename R>
 static int do_finish_facet(swiftly_hip* h, const void* in, int64_t rows, int64_t in_rs, int64_t in_cs, void* out,
                            int64_t out_rs, int64_t out_cs, int64_t off, int64_t yB, const void* mask, const Batch& bt,
-                           hipStream_t st, int64_t band_start = 0, int64_t band_len = -1) {
+                           hipStream_t st, int64_t band_start = 0, int64_t band_len = -1, bool real_out = false) {
     const int yN = (int)h->yN;
     RowsArgs<R> a;
     fill_io(a, in, rows, in_rs, in_cs, out, out_rs, out_cs);
+    a.real_out = real_out ? 1 : 0;  // `out` points to R, out_rs / out_cs count real elements
     a.ld = axis_map<R>(whole(yN));
     // band input: element d of a row is column (band_start + d) mod yN of the padded facet, the rest is zero
     if (band_len >= 0) a.ld = axis_map<R>(band_as_load_map(*h, band_start, band_len));
@@ -1406,12 +1411,20 @@ int swiftly_hip_prepare_facet_window_rows(swiftly_hip_t* h, int dtype, const voi
                                         band_len, other_axis_size, other_axis_row0, window_starts, nwindows, out_window_stride, stream);
 }
 
-int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+// finish_facet_band and its real-output twin (`out` float32, out_row_stride in reals; real_out): one implementation
+static int finish_facet_band_impl(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
                                   int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
-                                  int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
+                                  int64_t facet_off, int64_t facet_size, const void* mask, void* stream, bool real_out) {
     const int64_t in_cs = 1, out_cs = 1;
     CHECK_COMMON();
+    if (real_out) {  // float32 rows out: the capability rule of SWIFTLY_FEATURE_REAL_FACETS_OUT
+        if (const std::string why = why_not_real_facets_out(*h, dtype); !why.empty())
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band_real: %s", why.c_str());
+    }
     CHECK_FACET_SIZE();
+    if (real_out && out_row_stride < facet_size)
+        return fail(SWIFTLY_ERR_PARAM, "finish_facet_band_real: out_row_stride %lld is below facet_size %lld: the rows of the output overlap",
+                    (long long)out_row_stride, (long long)facet_size);
     // (the gate of swiftly_hip_supports(BACKWARD_BAND_EXPLICIT): identical to BACKWARD_BAND in complex64; complex128 rows run
     // through do_finish_facet<double>, 64 .. 32768 points)
     if (const std::string why = why_not_backward_band(*h, dtype, true); !why.empty())
@@ -1419,7 +1432,20 @@ int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, i
     CHECK_BAND();
     Batch bt{1, 0, 0, nullptr, 0};
     return DISPATCH(do_finish_facet, h, in, rows, in_row_stride, in_cs, out, out_row_stride, out_cs, facet_off, facet_size,
-                    mask, bt, (hipStream_t)stream, band_start, band_len);
+                    mask, bt, (hipStream_t)stream, band_start, band_len, real_out);
+}
+
+int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                  int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
+                                  int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
+    return finish_facet_band_impl(h, dtype, in, rows, in_row_stride, band_start, band_len, out, out_row_stride, facet_off,
+                                  facet_size, mask, stream, false);
+}
+int swiftly_hip_finish_facet_band_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                       int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
+                                       int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
+    return finish_facet_band_impl(h, dtype, in, rows, in_row_stride, band_start, band_len, out, out_row_stride, facet_off,
+                                  facet_size, mask, stream, true);
 }
 
 

@@ -237,6 +237,17 @@ inline std::string why_not_real_facets(const Sizes& s, int dtype) {
     if (s.log_yN < 0) return reason("real facets: yN %lld is Q * 2^k: the radix-Q pass has no real load", (long long)s.yN);
     return {};
 }
+// real-valued (float32) facets out of the backward band pass (finish_facet_band_real): the complex64 backward band with a
+// power-of-two yN -- the row kernels behind finish_facet_band have a real-store form, the radix-Q pass behind Q * 2^k and
+// the Bluestein kernel have none, and there is no complex128 -> float64 store
+inline std::string why_not_real_facets_out(const Sizes& s, int dtype) {
+    if (dtype == SWIFTLY_C128)
+        return "real facet output: complex64 input only (no complex128 -> float64 store in the complex128 row kernels)";
+    if (dtype != SWIFTLY_C64) return reason("real facet output: unknown dtype %d", dtype);
+    if (std::string why = why_not_backward_band(s, SWIFTLY_C64); !why.empty()) return "real facet output: " + why;
+    if (s.log_yN < 0) return reason("real facet output: yN %lld is Q * 2^k: the radix-Q pass has no real store", (long long)s.yN);
+    return {};
+}
 // size part of prepare_facet_window_rows (the band, the facets and the windows are per call)
 inline std::string why_not_window_rows(const Sizes& s) {
     if (s.log_yN == kWindowRowsLogYN && s.log_m == kWindowRowsLogM && s.xM <= (int64_t(1) << kPlacedMaxLogXM)) return {};

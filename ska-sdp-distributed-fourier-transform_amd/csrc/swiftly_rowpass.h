@@ -91,6 +91,10 @@ struct RowPassArgs {
     // pick the REAL instances of row_pass_kernel / row_pass_band_kernel, which load half the bytes and set the imaginary
     // parts to zero in registers.  Every value is the one the complex instance computes from the promoted row.
     int in_real;
+    // REAL output (backward finish of real-valued facets): `out` points to float32, out_pitch counts real elements; the
+    // launchers pick the real-STORE instances of the mapped store (row_pass_kernel MODE 1 / 2, row_pass_band_kernel ST = 2),
+    // which compute the stored value as the complex instance does and store its real part.  No accumulate.
+    int out_real;
 };
 
 // physical column of logical (centred) column ck in a parity-split band buffer, or -1
@@ -142,7 +146,9 @@ __device__ const float kRowOne = 1.f;
 // MODE 1: identity load, mapped store (shift, crop, windows)  -- finish_facet / finish_subgrid style
 // MODE 2: both mapped
 // REAL (MODE 0 only): the input row is float32 (RowPassArgs::in_real), the imaginary parts are zeros in registers
-template <class G, int MODE, bool REAL = false>
+// REAL_ST (MODE 1 / 2 only): the output row is float32 (RowPassArgs::out_real) -- the real part of the mapped store, 4 bytes
+// per element; no accumulate (host-refused)
+template <class G, int MODE, bool REAL = false, bool REAL_ST = false>
 __global__ __launch_bounds__(G::NT) void row_pass_kernel(const RowPassArgs A, const cx<float>* __restrict__ gin,
                                                          cx<float>* __restrict__ gout,
                                                          const float* __restrict__ ld_win,
@@ -153,6 +159,7 @@ __global__ __launch_bounds__(G::NT) void row_pass_kernel(const RowPassArgs A, co
     constexpr int P = G::P, T = G::T, N = G::N;
     constexpr bool MAP_LD = MODE != 1, MAP_ST = MODE != 0;
     static_assert(!REAL || MODE == 0, "real input: the mapped load of a prepare_* primitive");
+    static_assert(!REAL_ST || (MODE != 0 && !REAL), "real output: the mapped store of a finish_* primitive");
     constexpr int CH = P < 8 ? P : 8;  // loads are issued in chunks of CH; products trail one chunk behind
     const int t = threadIdx.x;
     const int row = blockIdx.x;  // uniform
@@ -169,7 +176,8 @@ __global__ __launch_bounds__(G::NT) void row_pass_kernel(const RowPassArgs A, co
     if (in_row < 0) in_row = 0;
     const cx<float>* __restrict__ in = gin + (REAL ? 0ll : (long long)in_row * A.in_pitch);  // uniform base
     const float* __restrict__ rin = reinterpret_cast<const float*>(gin) + (REAL ? (long long)in_row * A.in_pitch : 0ll);
-    cx<float>* __restrict__ out = gout + (long long)row * A.out_pitch;
+    cx<float>* __restrict__ out = gout + (REAL_ST ? 0ll : (long long)row * A.out_pitch);
+    float* __restrict__ rout = reinterpret_cast<float*>(gout) + (REAL_ST ? (long long)row * A.out_pitch : 0ll);
     const float sg_ld = A.conj_ld ? -1.f : 1.f;
     const float sg_st = A.conj_st ? -1.f : 1.f;
     const float* __restrict__ lw = ld_win ? ld_win : &kRowOne;
@@ -244,15 +252,19 @@ __global__ __launch_bounds__(G::NT) void row_pass_kernel(const RowPassArgs A, co
             if (idx >= (unsigned)A.st_mod) idx -= (unsigned)A.st_mod;
             const float w = rscale * sw1[ds * sw1s] * sw2[ds * sw2s];
             v.x *= w;
-            v.y *= w * sg_st;
-            if (ok) {
-                cx<float>* p = out + idx;
-                if (A.accumulate) {
-                    const cx<float> old = *p;
-                    v.x += old.x;
-                    v.y += old.y;
+            if constexpr (REAL_ST) {
+                if (ok) rout[idx] = v.x;
+            } else {
+                v.y *= w * sg_st;
+                if (ok) {
+                    cx<float>* p = out + idx;
+                    if (A.accumulate) {
+                        const cx<float> old = *p;
+                        v.x += old.x;
+                        v.y += old.y;
+                    }
+                    *p = v;
                 }
-                *p = v;
             }
         }
     });
@@ -402,7 +414,12 @@ __global__ __launch_bounds__(G::NT) void row_pass_split_kernel(const RowPassArgs
 // complex instance on the promoted row (up to the sign of a zero).  REAL = 2 (PAIR only): the pair geometry for a row whose
 // pitch is odd or whose base is only 4-byte aligned -- the lane's two adjacent reals through two 4-byte loads, everything
 // else as REAL = 1, so that the values do not depend on where the caller's rows lie in memory.
-template <class G, bool HAS_WIN, int ST, bool PAIR = false, int NSEG = 0, int CJ = -1, bool W4 = false, int REAL = 0>
+// REAL_ST (backward finish of real-valued facets, RowPassArgs::out_real; ST = 2 only): the output row is float32.  The
+// stored value is computed as in the complex instance -- same window fetch, same scale * window, same rotation phase
+// product -- and its real part goes out through a 4-byte store at out_pitch * 4 bytes per row; the products that only
+// feed the imaginary part are dead.  No accumulate (host-refused).
+template <class G, bool HAS_WIN, int ST, bool PAIR = false, int NSEG = 0, int CJ = -1, bool W4 = false, int REAL = 0,
+          bool REAL_ST = false>
 __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassArgs A, const cx<float>* __restrict__ gin,
                                                                  cx<float>* __restrict__ gout,
                                                                  const float* __restrict__ ld_win,
@@ -420,6 +437,7 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
     static_assert(NS <= NSEGTOT, "segment count");
     static_assert(!SEGSKIP || G::LOGN % G::LOGP == 0 || PAIR, "one output phase per lane needs a single block in the last phase");
     static_assert(!SEGSKIP || (T % P) == 0, "rotation phase must not depend on the last radix digit");
+    static_assert(!REAL_ST || (ST == 2 && REAL == 0), "real output: the mapped store of a finish_* primitive, complex input");
     const int t = threadIdx.x;
     const int b = blockIdx.x;
     const int h = (b >> 3) & 1;
@@ -452,7 +470,9 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
     // (REAL: in_pitch counts 4-byte elements)
     const char* __restrict__ inb = REAL ? reinterpret_cast<const char*>(reinterpret_cast<const float*>(gin) + (long long)in_row * A.in_pitch)
                                         : reinterpret_cast<const char*>(gin + (long long)in_row * A.in_pitch);
-    char* __restrict__ outb = reinterpret_cast<char*>(gout + (long long)__builtin_amdgcn_readfirstlane(row) * A.out_pitch);
+    // (REAL_ST: out_pitch counts 4-byte elements)
+    char* __restrict__ outb = REAL_ST ? reinterpret_cast<char*>(reinterpret_cast<float*>(gout) + (long long)__builtin_amdgcn_readfirstlane(row) * A.out_pitch)
+                                      : reinterpret_cast<char*>(gout + (long long)__builtin_amdgcn_readfirstlane(row) * A.out_pitch);
     const char* __restrict__ winb = reinterpret_cast<const char*>(ld_win);
     const float sg_ld = A.conj_ld ? -1.f : 1.f;
     const float sg_st = A.conj_st ? -1.f : 1.f;
@@ -740,14 +760,21 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
             const int ck = (2 * e + h) ^ (N >> 1);
             const int d = (ck + A.st_a) & (N - 1);
             const float w = scale * wv[s % CH];
-            if constexpr (SEGSKIP) v = cmul(v, rphi);
-            if (d < A.st_len) {
-                f32x2 val = {v.x * w, v.y * w * sg_st};
-                if (A.accumulate) {
-                    const f32x2 old = *reinterpret_cast<const f32x2*>(outb + ((unsigned)d << 3));
-                    val += old;
+            if constexpr (REAL_ST) {
+                // the real lane of cmul(v, rphi) -- a rounded product, then one fused multiply-add -- without the packed
+                // instructions that would compute the imaginary lane along with it
+                if constexpr (SEGSKIP) v.x = __builtin_fmaf(-v.y, rphi.y, v.x * rphi.x);
+                if (d < A.st_len) *reinterpret_cast<float*>(outb + ((unsigned)d << 2)) = v.x * w;
+            } else {
+                if constexpr (SEGSKIP) v = cmul(v, rphi);
+                if (d < A.st_len) {
+                    f32x2 val = {v.x * w, v.y * w * sg_st};
+                    if (A.accumulate) {
+                        const f32x2 old = *reinterpret_cast<const f32x2*>(outb + ((unsigned)d << 3));
+                        val += old;
+                    }
+                    *reinterpret_cast<f32x2*>(outb + ((unsigned)d << 3)) = val;
                 }
-                *reinterpret_cast<f32x2*>(outb + ((unsigned)d << 3)) = val;
             }
         });
         return;

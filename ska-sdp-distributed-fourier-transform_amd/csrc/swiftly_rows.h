@@ -83,6 +83,10 @@ struct RowsArgs {
     // REAL input (prepare_facet of a real-valued facet, plain band layout): `in` points to R, the input strides count real
     // elements; launch_fft_rows picks the REAL_IN instance, which sets the imaginary parts to zero in registers
     int real_in;
+    // REAL output (finish_facet of a real-valued facet, plain band layout): `out` points to R, the output strides count real
+    // elements; launch_fft_rows picks the REAL_OUT instance, which stores the real part of the mapped store (no st_rowmap, no
+    // raw_st, no accumulate: host-refused)
+    int real_out;
 };
 
 // Per-batch-item overrides of the map offsets (passed by value as a kernel
@@ -100,7 +104,7 @@ struct kOneTable {
 template <typename R>
 __device__ const R kOneTable<R>::value = (R)1;
 
-template <class G, typename R, bool REAL_IN = false>
+template <class G, typename R, bool REAL_IN = false, bool REAL_OUT = false>
 __global__ __launch_bounds__(G::NT) void fft_rows_kernel(const RowsArgs<R> A, const OffTab tab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int P = G::P, T = G::T, RB = G::RB;
@@ -155,7 +159,9 @@ __global__ __launch_bounds__(G::NT) void fft_rows_kernel(const RowsArgs<R> A, co
         else
             return in[e];
     };
-    cx<R>* __restrict__ out = A.out + row * A.out_rs + (long long)o * A.out_os + (long long)b * A.out_bs;
+    const long long out_base = row * A.out_rs + (long long)o * A.out_os + (long long)b * A.out_bs;
+    cx<R>* __restrict__ out = A.out + (REAL_OUT ? 0ll : out_base);
+    R* __restrict__ rout = reinterpret_cast<R*>(A.out) + (REAL_OUT ? out_base : 0ll);
     const int ld_a = (tab.use & 1) ? tab.ld_a[b] : A.ld.a;
     const int ld_c = (tab.use & 2) ? tab.ld_c[b] : A.ld.c;
     const int st_a = (tab.use & 4) ? tab.st_a[b] : A.st.a;
@@ -213,40 +219,55 @@ __global__ __launch_bounds__(G::NT) void fft_rows_kernel(const RowsArgs<R> A, co
             v = cmul(v, w);
         }
         v.x *= A.scale;
-        v.y *= A.scale * csign_st;
-        if (A.raw_st) {
-            cx<R>* p = out + (size_t)((unsigned)e * A.out_cs);
-            if (A.accumulate) {
-                cx<R> old = *p;
-                v.x += old.x;
-                v.y += old.y;
+        if constexpr (REAL_OUT) {  // the mapped store, real part only
+            const int pk = e * A.st_mul + st_add;
+            const int ck = wrapn(pk + (FN >> 1));
+            const int d = wrapn(ck + st_a);
+            if (d < A.st.len) {
+                int idx = d + st_c;
+                if (idx >= A.st.mod) idx -= A.st.mod;
+                R w = (R)1;
+                if (st_win) w = st_win[d];
+                if (A.st.win2) w *= A.st.win2[d];
+                if (A.row_win) w *= A.row_win[row];
+                rout[(size_t)((unsigned)idx * A.out_cs)] = v.x * w;
             }
-            *p = v;
-            return;
-        }
-        const int pk = e * A.st_mul + st_add;
-        const int ck = wrapn(pk + (FN >> 1));
-        const int d = wrapn(ck + st_a);
-        if (d < A.st.len) {
-            int idx = d + st_c;
-            if (idx >= A.st.mod) idx -= A.st.mod;
-            if (A.st_rowmap) {
-                idx = A.st_rowmap[idx];
-                if (idx < 0) return;
+        } else {
+            v.y *= A.scale * csign_st;
+            if (A.raw_st) {
+                cx<R>* p = out + (size_t)((unsigned)e * A.out_cs);
+                if (A.accumulate) {
+                    cx<R> old = *p;
+                    v.x += old.x;
+                    v.y += old.y;
+                }
+                *p = v;
+                return;
             }
-            R w = (R)1;
-            if (st_win) w = st_win[d];
-            if (A.st.win2) w *= A.st.win2[d];
-            if (A.row_win) w *= A.row_win[row];
-            v.x *= w;
-            v.y *= w;
-            cx<R>* p = out + (size_t)((unsigned)idx * A.out_cs);
-            if (A.accumulate) {
-                cx<R> old = *p;
-                v.x += old.x;
-                v.y += old.y;
+            const int pk = e * A.st_mul + st_add;
+            const int ck = wrapn(pk + (FN >> 1));
+            const int d = wrapn(ck + st_a);
+            if (d < A.st.len) {
+                int idx = d + st_c;
+                if (idx >= A.st.mod) idx -= A.st.mod;
+                if (A.st_rowmap) {
+                    idx = A.st_rowmap[idx];
+                    if (idx < 0) return;
+                }
+                R w = (R)1;
+                if (st_win) w = st_win[d];
+                if (A.st.win2) w *= A.st.win2[d];
+                if (A.row_win) w *= A.row_win[row];
+                v.x *= w;
+                v.y *= w;
+                cx<R>* p = out + (size_t)((unsigned)idx * A.out_cs);
+                if (A.accumulate) {
+                    cx<R> old = *p;
+                    v.x += old.x;
+                    v.y += old.y;
+                }
+                *p = v;
             }
-            *p = v;
         }
     });
 }

@@ -38,11 +38,19 @@ class SwiftlyBackward:
         dtype then raises ``ValueError`` on the band schedule.  ``wave_axis=1, dtype=torch.complex128`` is the
         explicit request that runs the band schedule in complex128 (power-of-two ``yN_size`` 64 .. 32768); nothing
         picks it on its own: with ``wave_axis=None`` complex128 stays on the reference's schedule.
+    :param facet_dtype: ``None`` (default) or the complex dtype of the data: :py:meth:`finish` returns complex facets.
+        ``torch.float32`` (complex64 data) / ``torch.float64`` (complex128 data): the facets are images and
+        :py:meth:`finish` returns their real parts, ``[size, size]`` in that dtype -- bit for bit the ``.real`` of the complex
+        result.  On the band schedule in complex64, where ``core.supports_real_facets_out()`` holds, the finishing row
+        kernels store float32 themselves and no complex facet is ever allocated (:py:attr:`real_finish_native`);
+        everywhere else each facet is finished complex, its real part copied out and the complex one released before
+        the next facet is finished.  A dtype that does not match the data's precision raises ``ValueError`` -- at
+        construction when ``dtype`` is given, else at the first data.
     """
 
     # pylint: disable=too-many-arguments,too-many-instance-attributes
     def __init__(self, swiftly_config, facets_config_list, lru_backward=1, queue_size=20, client=None,
-                 subgrid_configs=None, wave_axis=None, delayed=False, dtype=None):
+                 subgrid_configs=None, wave_axis=None, delayed=False, dtype=None, facet_dtype=None):
         self.delayed = bool(delayed)  # finish() hands out DeviceTask handles instead of bare device tensors
         # wave_axis=None: the reference's schedule, unless the caller hands over the plan of subgrids it will add and
         # the band kernels exist -- decided when the first subgrid shows the dtype (complex64 only)
@@ -81,6 +89,62 @@ class SwiftlyBackward:
             # an explicit request for the band schedule is answered at once (complex128: the explicit gate)
             if self.wave_axis == 1 and not self._auto_axis and not self.core.supports_backward_band(dtype, explicit=True):
                 raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={dtype}): {_lib.last_error()}")
+        self._facet_dtype = self._parse_facet_dtype(facet_dtype)
+        if self._fixed_dtype is not None:
+            self._check_facet_dtype(self._fixed_dtype)
+
+    @staticmethod
+    def _parse_facet_dtype(facet_dtype):
+        """``facet_dtype`` as a torch dtype: one of float32, float64, complex64, complex128, or None"""
+        if facet_dtype is None:
+            return None
+        torch = _torch()
+        if not isinstance(facet_dtype, torch.dtype):
+            try:
+                facet_dtype = {numpy.dtype(numpy.float32): torch.float32, numpy.dtype(numpy.float64): torch.float64,
+                               numpy.dtype(numpy.complex64): torch.complex64,
+                               numpy.dtype(numpy.complex128): torch.complex128}.get(numpy.dtype(facet_dtype))
+            except TypeError:
+                facet_dtype = None
+        if facet_dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+            raise ValueError("facet_dtype must be float32, float64, complex64, complex128 or None")
+        return facet_dtype
+
+    def _check_facet_dtype(self, data_dtype):
+        """``facet_dtype`` has the precision of the data (called wherever the data's dtype becomes known)"""
+        torch = _torch()
+        if self._facet_dtype is None:
+            return
+        single = data_dtype in (torch.complex64, torch.float32)
+        if (self._facet_dtype in (torch.float32, torch.complex64)) != single:
+            raise ValueError(f"SwiftlyBackward(facet_dtype={self._facet_dtype}) does not match {data_dtype} data: "
+                             "float32 / complex64 facets come from complex64 data, float64 / complex128 from complex128")
+
+    @property
+    def facet_dtype(self):
+        """dtype of the facets :py:meth:`finish` returns: the ``facet_dtype`` asked for, else the data's complex dtype
+        (``None`` while no data has shown it)"""
+        return self._facet_dtype if self._facet_dtype is not None else self.dtype
+
+    @property
+    def _real_facets(self):
+        return self._facet_dtype is not None and not self._facet_dtype.is_complex
+
+    @property
+    def real_finish_native(self):
+        """By which path :py:meth:`finish` produces real facets: True = the finishing row kernels store float32 (band
+        schedule, complex64, ``core.supports_real_facets_out()``), False = complex finish and a copy of the real part per
+        facet (also: the facets are complex).  ``None`` until the schedule is resolved."""
+        if self._auto_axis:
+            return None
+        if not self._real_facets:
+            return False
+        return bool(self.wave_axis == 1 and self._facet_dtype == _torch().float32 and self.core.supports_real_facets_out())
+
+    def _real_part(self, facet):
+        """the real part of a finished complex facet as a tensor of its own (the caller drops the complex one)"""
+        self._check_facet_dtype(facet.dtype)  # (contributions handed straight to accumulate_wave show their dtype only here)
+        return facet.real.contiguous()
 
     def add_new_subgrid_task(self, subgrid_config, new_subgrid_task):
         """Fold one subgrid into the facet sums (reference api.py:347-372)."""
@@ -220,6 +284,7 @@ class SwiftlyBackward:
             ten, _ = core._as_device(data)  # pylint: disable=protected-access
             if self.dtype is None:
                 self.dtype = ten.dtype
+                self._check_facet_dtype(ten.dtype)
             elif ten.dtype != self.dtype:
                 if self.wave_axis == 1 and self._fixed_dtype is not None:  # no silent conversion on the explicit band schedule
                     raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={self.dtype}) got {ten.dtype} data")
@@ -320,6 +385,7 @@ class SwiftlyBackward:
         for sgs, parts in chunks:
             if self.dtype is None:
                 self.dtype = parts.dtype
+                self._check_facet_dtype(parts.dtype)
             if col is None:
                 col = torch.zeros((F, m, yN), dtype=parts.dtype, device=core.device)
             for b, sg in enumerate(sgs):
@@ -393,6 +459,7 @@ class SwiftlyBackward:
                 )
         if self.dtype is None:
             self.dtype = chunks[0][1].dtype
+            self._check_facet_dtype(self.dtype)
         bands = self._band_state(chunks[0][1].dtype)
         for _sgs, parts in chunks:
             # on EVERY call, not only the one that creates the accumulators: the native side reads `parts` with the
@@ -432,11 +499,17 @@ class SwiftlyBackward:
         core = self.core
         out = []
         if self._bands is None:
-            dt = self.dtype or torch.complex64
+            dt = self.facet_dtype or torch.complex64
             return [torch.zeros((cfg.size, cfg.size), dtype=dt, device=core.device) for cfg in self.facets_config_list]
         core.band_zero_untouched(self._bands, self._touched)
+        native = self.real_finish_native and self._bands.dtype == torch.complex64
         for j, cfg in enumerate(self.facets_config_list):
-            out.append(core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1))
+            if native:  # float32 straight from the row kernels: no complex facet exists
+                out.append(core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1, real=True))
+                continue
+            facet = core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1)
+            out.append(self._real_part(facet) if self._real_facets else facet)
+            del facet  # (real facets: the complex one is gone before the next is finished)
         self._bands = None
         self._work = None
         return out
@@ -474,9 +547,11 @@ class SwiftlyBackward:
         out = []
         for cfg, acc in zip(self.facets_config_list, self.MNAF_BMNAFs_persist):
             if acc is None:
-                dt = self.dtype or torch.complex64
+                dt = self.facet_dtype or torch.complex64
                 out.append(torch.zeros((cfg.size, cfg.size), dtype=dt, device=core.device))
             else:
-                out.append(core.finish_facet(acc, cfg.off0, cfg.size, axis=0, mask=cfg.mask0))
+                facet = core.finish_facet(acc, cfg.off0, cfg.size, axis=0, mask=cfg.mask0)
+                out.append(self._real_part(facet) if self._real_facets else facet)
+                del facet  # (real facets: the complex one is gone before the next is finished)
         self.task_queue.wait_all_done()
         return [DeviceTask(t) for t in out] if self.delayed else out

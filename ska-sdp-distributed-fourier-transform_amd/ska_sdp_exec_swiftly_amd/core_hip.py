@@ -592,6 +592,12 @@ class SwiftlyCoreHip:
         and ``SwiftlyForward`` promote such facets as before."""
         return not (self.yN_size == 32768 and int(facet_size) > 23552)
 
+    def supports_real_facets_out(self):
+        """True when the backward finish stores real-valued (float32) facets as they are (``finish_facet_band(...,
+        real=True)``; ``swiftly_hip_finish_facet_band_real``): the complex64 backward band with a power-of-two ``yN_size``.
+        After a False ``_lib.last_error()`` says why."""
+        return self._supports(_lib.FEATURE_REAL_FACETS_OUT, _torch().complex64)
+
     def band_for_offsets(self, subgrid_offs):
         """Smallest cyclic range ``(start, length)`` of centred indices of the padded facet axis that contains
         the ``xM_yN_size`` window of every given subgrid offset (core.py:243-253); ``(0, yN_size)`` = all."""
@@ -1064,17 +1070,30 @@ class SwiftlyCoreHip:
             )
         )
 
-    def finish_facet_band(self, band_acc, band, facet_off, facet_size, mask=None, out=None):
+    def finish_facet_band(self, band_acc, band, facet_off, facet_size, mask=None, out=None, real=False):
         """``finish_facet`` (core.py:481-510) along the contiguous axis for a band accumulator ``[rows, band
-        length]`` (``swiftly_hip_finish_facet_band``)."""
+        length]`` (``swiftly_hip_finish_facet_band``).
+
+        ``real=True`` (complex64 accumulators, :py:meth:`supports_real_facets_out`): the facet is an image -- the result is
+        the float32 tensor ``[rows, facet_size]`` of the real parts, bit for bit those of the complex result, written
+        by the row kernels themselves (``swiftly_hip_finish_facet_band_real``; no complex facet exists at any time).
+        ``out``: float32 rows of any pitch ``>= facet_size`` with unit column stride."""
         torch = _torch()
         rows = band_acc.shape[0]
+        if real and not band_acc.is_complex():
+            raise ValueError(f"finish_facet_band(real=True) needs complex accumulators, got {band_acc.dtype}")
+        want = torch.float32 if real else band_acc.dtype
         if out is None:
-            out = torch.empty((rows, int(facet_size)), dtype=band_acc.dtype, device=self._device)
+            out = torch.empty((rows, int(facet_size)), dtype=want, device=self._device)
+        elif out.dtype != want:
+            raise ValueError(f"finish_facet_band(real={bool(real)}) on {band_acc.dtype} accumulators writes {want}, got an `out` of {out.dtype}")
+        if real and (out.dim() != 2 or tuple(out.shape) != (rows, int(facet_size)) or out.stride(1) != 1):
+            raise ValueError(f"finish_facet_band(real=True): `out` must be [{rows}, {int(facet_size)}] with unit column stride")
         mvec = self._real_vec(mask, band_acc.dtype, int(facet_size)) if mask is not None else None
         cvp = ctypes.c_void_p
+        entry = self._lib.swiftly_hip_finish_facet_band_real if real else self._lib.swiftly_hip_finish_facet_band
         _lib.check(
-            self._lib.swiftly_hip_finish_facet_band(
+            entry(
                 self._handle, self._code(band_acc), cvp(band_acc.data_ptr()), rows, band_acc.stride(0), int(band[0]),
                 int(band[1]), cvp(out.data_ptr()), out.stride(0), int(facet_off), int(facet_size),
                 cvp(mvec.data_ptr()) if mvec is not None else None, self._stream(),
