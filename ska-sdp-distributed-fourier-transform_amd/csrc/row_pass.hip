@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "swiftly_launch.h"
+#include "swiftly_rowinst.h"
 #include "swiftly_rowpass.h"
 
 namespace swf {
@@ -19,11 +20,11 @@ struct RGeoFor {
     using type = RGeo<LOGN, LOGN - 10, (LOGN >= 14)>;  // split from 16384: 64 KB LDS -> 2 workgroups per CU
 };
 
-template <int LOGN, int MODE>
+template <int LOGN, int MODE, bool REAL = false, bool REAL_ST = false>
 static int launch_mode(const RowPassArgs& a, hipStream_t s) {
     using G = typename RGeoFor<LOGN>::type;
-    return launch_lds<row_pass_kernel<G, MODE>, G::LDS_BYTES>(dim3((unsigned)a.nrows), dim3(G::NT), s, a, a.in, a.out, a.ld_win,
-                                                              a.st_win, a.st_win2, a.tw);
+    return launch_lds<row_pass_kernel<G, MODE, REAL, REAL_ST>, G::LDS_BYTES>(dim3((unsigned)a.nrows), dim3(G::NT), s, a, a.in, a.out,
+                                                                             a.ld_win, a.st_win, a.st_win2, a.tw);
 }
 template <int LOGN>
 static int launch_one(int mode, const RowPassArgs& a, hipStream_t s) {
@@ -34,31 +35,15 @@ static int launch_one(int mode, const RowPassArgs& a, hipStream_t s) {
 
 int launch_row_pass(int logn, int mode, const RowPassArgs& a, hipStream_t s) {
     if (a.nrows <= 0) return 0;
-    if (a.in_real) {  // real input: the 8192-point mapped load of the plain band layout (longer rows: launch_row_pass_band_n)
-        using G = typename RGeoFor<13>::type;
-        if (logn != 13 || mode != 0) return -1;
-        return launch_lds<row_pass_kernel<G, 0, true>, G::LDS_BYTES>(dim3((unsigned)a.nrows), dim3(G::NT), s, a, a.in, a.out, a.ld_win,
-                                                                    a.st_win, a.st_win2, a.tw);
-    }
-    if (a.out_real) {  // real output: the mapped store of 8192- and 16384-point rows (longer rows: launch_row_pass_band_n)
-        if (mode == 0 || a.accumulate) return -1;
-#define SWF_REAL_ST(LOGN, MODE)                                                                                              \
-    if (logn == LOGN && mode == MODE) {                                                                                      \
-        using G = typename RGeoFor<LOGN>::type;                                                                              \
-        return launch_lds<row_pass_kernel<G, MODE, false, true>, G::LDS_BYTES>(dim3((unsigned)a.nrows), dim3(G::NT), s, a, a.in, \
-                                                                               a.out, a.ld_win, a.st_win, a.st_win2, a.tw); \
-    }
-        SWF_REAL_ST(13, 1)
-        SWF_REAL_ST(13, 2)
-        SWF_REAL_ST(14, 1)
-        SWF_REAL_ST(14, 2)
-#undef SWF_REAL_ST
-        return -1;
-    }
-    switch (logn) {
-        case 13: return launch_one<13>(mode, a, s);
-        case 14: return launch_one<14>(mode, a, s);
-        case 15: return launch_one<15>(mode, a, s);
+    switch (choose_lean_form(logn, mode, a.in_real, a.out_real, a.accumulate)) {  // swiftly_rowinst.h: which forms exist
+        case kLeanRealLoad: return launch_mode<13, 0, true>(a, s);
+        case kLeanRealStore:
+            if (logn == 13) return mode == 1 ? launch_mode<13, 1, false, true>(a, s) : launch_mode<13, 2, false, true>(a, s);
+            return mode == 1 ? launch_mode<14, 1, false, true>(a, s) : launch_mode<14, 2, false, true>(a, s);
+        case kLeanComplex:
+            if (logn == 13) return launch_one<13>(mode, a, s);
+            if (logn == 14) return launch_one<14>(mode, a, s);
+            return launch_one<15>(mode, a, s);
         default: return -1;
     }
 }
@@ -79,51 +64,85 @@ int launch_row_pass_split(const RowPassArgs& a, const cx<float>* tw14, const cx<
     if (a.nrows <= 0) return 0;
     return launch_split<SplitGeo2, 1>(a, tw14, tw_full, s);
 }
-using BandGeo5 = RGeo<14, 5, true>;  // 2 x 16384 points, 512 threads x 32, 66 KB LDS: two workgroups per CU
-using BandGeo4 = RGeo<14, 4, true>;  // 2 x 16384 points, 1024 threads x 16, one workgroup per CU
-// Cyclic run of input segments (seglen consecutive points of the n-point transform input) that can hold data under
-// the load map of a prepare_* primitive: q = (j + n/2 + ld_a) mod n < ld_len.  Returns the length of the run and its
-// first segment (0, all segments: the row has no empty segment).
-static int data_segment_run(const RowPassArgs& a, int n, int seglen, int* first) {
-    const int nseg = n / seglen, base = (int)(((long long)a.ld_a + n / 2) % n);
-    int valid[64];
-    int count = 0;
-    for (int r = 0; r < nseg; r++) {
-        const int lo = (int)(((long long)seglen * r + base) % n);
-        valid[r] = a.ld_len > 0 && (lo < a.ld_len || lo + seglen > n);
-        count += valid[r];
-    }
-    *first = 0;
-    if (count == nseg || count == 0) return count == 0 ? 1 : nseg;
-    for (int r = 0; r < nseg; r++)
-        if (valid[r] && !valid[(r + nseg - 1) % nseg]) *first = r;
-    int run = 0;
-    while (run < nseg && valid[(*first + run) % nseg]) run++;
-    return run == count ? run : nseg;  // two runs cannot happen for one cyclic range; be safe
-}
+// -- the band row kernel: 2 x 2^(logn-1) points, two workgroups per row ---------------------------------------------
+// geometries (BandGeoId of swiftly_rowinst.h names them)
+using BandGeo16k = RGeo<13, 4, true>;       // yN = 16384: 2 x  8192 points,  512 threads x 16, 33 KB LDS
+using BandGeo4 = RGeo<14, 4, true>;         // yN = 32768: 2 x 16384 points, 1024 threads x 16, one workgroup per CU
+using BandGeo5 = RGeo<14, 5, true>;         // yN = 32768: 2 x 16384 points,  512 threads x 32, 66 KB LDS: two workgroups per CU
+using BandGeo5Pre = RGeoPre<14, 5, true>;   // ... with the twiddle preload (forward K1)
+using BandGeo5PreC = RGeoPreC<14, 5, true>; // ... from the compact twiddle sections (forward K1 with the window table)
+using BandGeo5C = RGeoC<14, 5, true>;       // ... compact sections without the preload (backward finish)
+using BandGeo64k = RGeo<15, 5, true>;       // yN = 65536: 2 x 32768 points, 1024 threads x 32, 132 KB LDS, one workgroup per CU
 
-template <class G, bool PAIR, bool WIN, int ST, int NSEG, int CJ = -1, bool W4 = false, int REAL = 0>
-static int launch_band_inst(const RowPassArgs& a, unsigned blocks, const cx<float>* tw14, const cx<float>* tw_full,
-                            hipStream_t s) {
-    return launch_lds<row_pass_band_kernel<G, WIN, ST, PAIR, NSEG, CJ, W4, REAL>, G::LDS_BYTES>(dim3(blocks), dim3(G::NT), s, a,
-                                                                                                a.in, a.out, a.ld_win, tw14, tw_full);
-}
-// Mapped store (ST = 2, no load window) of the instance <G, PAIR, NSEG, CJ>: the complex form, or for RowPassArgs::out_real
-// its real-store twin.  Every mapped-store launch goes through here, so the instance -- geometry, segment count, rotation --
-// is chosen before, and never from, the type of the destination.
-template <class G, bool PAIR, int NSEG, int CJ = -1>
-static int launch_band_finish(const RowPassArgs& a, unsigned blocks, const cx<float>* tw14, const cx<float>* tw_full,
-                              hipStream_t s) {
-    if (!a.out_real) return launch_band_inst<G, PAIR, false, 2, NSEG, CJ>(a, blocks, tw14, tw_full, s);
-    // real twins exist where a finish can arrive: the 512 x 32 geometry of the 32768-point rows and the 65536-point geometry
-    if constexpr (G::LOGP == 5) {
-        if (a.accumulate) return -1;
-        return launch_lds<row_pass_band_kernel<G, false, 2, PAIR, NSEG, CJ, false, 0, true>, G::LDS_BYTES>(
-            dim3(blocks), dim3(G::NT), s, a, a.in, a.out, a.ld_win, tw14, tw_full);
-    } else {
-        return -1;
-    }
-}
+// Every instance of row_pass_band_kernel that exists: X(geometry, WIN, ST, PAIR, NSEG, CJ, W4, REAL, REAL_ST).  Which one
+// a call runs: choose_band_instance (swiftly_rowinst.h); tests/test_band_instances_cpu.py holds this list against it.
+// ST: 0 plain store, 1 band store, 2 mapped store (no load window).  REAL 1: real rows; 2: through 4-byte loads (PAIR only).
+#define SWF_BAND_INSTANCES(X)                                                                                          \
+    /* 16384-point rows: one geometry for every form */                                                                \
+    X(BandGeo16k, 0, 0, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo16k, 0, 1, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo16k, 0, 2, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo16k, 1, 0, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo16k, 1, 1, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo16k, 1, 1, 0, 0, -1, 0, 1, 0)                                                                             \
+    /* 32768-point rows, plain store: 1024 x 16 -- the 512-thread form spills ~49 VGPRs here */                        \
+    X(BandGeo4, 0, 0, 0, 0, -1, 0, 0, 0)                                                                               \
+    X(BandGeo4, 1, 0, 0, 0, -1, 0, 0, 0)                                                                               \
+    /* 32768-point rows, band and mapped store: 512 x 32, two workgroups per CU (1024 x 16 for the band store: */      \
+    /* 1.95 against 1.73 ms per facet, r4); without and with adjacent-point loads */                                   \
+    X(BandGeo5, 0, 1, 0, 0, -1, 0, 0, 0)                                                                               \
+    X(BandGeo5, 1, 1, 0, 0, -1, 0, 0, 0)                                                                               \
+    X(BandGeo5, 1, 1, 0, 0, -1, 0, 1, 0)                                                                               \
+    X(BandGeo5, 0, 2, 0, 0, -1, 0, 0, 0)                                                                               \
+    X(BandGeo5, 0, 2, 0, 0, -1, 0, 0, 1)                                                                               \
+    X(BandGeo5, 0, 1, 1, 0, -1, 0, 0, 0)                                                                               \
+    X(BandGeo5, 1, 1, 1, 0, -1, 0, 0, 0)                                                                               \
+    X(BandGeo5, 1, 1, 1, 0, -1, 0, 1, 0)                                                                               \
+    X(BandGeo5, 1, 1, 1, 0, -1, 0, 2, 0)                                                                               \
+    X(BandGeo5, 0, 2, 1, 0, -1, 0, 0, 0)                                                                               \
+    X(BandGeo5, 0, 2, 1, 0, -1, 0, 0, 1)                                                                               \
+    /* backward finish with its empty segments compiled out: the band is 11488 of 32768 columns, 12 segments, 13 at */ \
+    /* an unaligned position; 16 for wider bands.  Plain geometry: at 128 VGPRs the preload does not gain */          \
+    X(BandGeo5, 0, 2, 1, 13, 0, 0, 0, 0)                                                                               \
+    X(BandGeo5, 0, 2, 1, 13, 0, 0, 0, 1)                                                                               \
+    X(BandGeo5, 0, 2, 1, 16, 0, 0, 0, 0)                                                                               \
+    X(BandGeo5, 0, 2, 1, 16, 0, 0, 0, 1)                                                                               \
+    X(BandGeo5C, 0, 2, 1, 13, 0, 0, 0, 0)                                                                              \
+    X(BandGeo5C, 0, 2, 1, 13, 0, 0, 0, 1)                                                                              \
+    X(BandGeo5C, 0, 2, 1, 16, 0, 0, 0, 0)                                                                              \
+    X(BandGeo5C, 0, 2, 1, 16, 0, 0, 0, 1)                                                                              \
+    /* forward K1 with its empty segments compiled out: 16 (a 16384-point facet), 22 (the 22528 points of the 64k */   \
+    /* workload at a segment boundary) and 24 (the same facet anywhere, and 24576 points) of 32 segments; with the */  \
+    /* plain window loads, and for complex rows with the window table alone (SWIFTLY_K1_WIN4=1) */                     \
+    X(BandGeo5Pre, 1, 1, 1, 16, 1, 0, 0, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 16, 1, 0, 1, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 16, 1, 0, 2, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 16, 1, 1, 0, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 22, 1, 0, 0, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 22, 1, 0, 1, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 22, 1, 0, 2, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 22, 1, 1, 0, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 24, 1, 0, 0, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 24, 1, 0, 1, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 24, 1, 0, 2, 0)                                                                            \
+    X(BandGeo5Pre, 1, 1, 1, 24, 1, 1, 0, 0)                                                                            \
+    /* ... and the tuned ones: window table, compact twiddles, load pipeline */                                        \
+    X(BandGeo5PreC, 1, 1, 1, 16, 1, 1, 0, 0)                                                                           \
+    X(BandGeo5PreC, 1, 1, 1, 16, 1, 1, 1, 0)                                                                           \
+    X(BandGeo5PreC, 1, 1, 1, 22, 1, 1, 0, 0)                                                                           \
+    X(BandGeo5PreC, 1, 1, 1, 22, 1, 1, 1, 0)                                                                           \
+    X(BandGeo5PreC, 1, 1, 1, 24, 1, 1, 0, 0)                                                                           \
+    X(BandGeo5PreC, 1, 1, 1, 24, 1, 1, 1, 0)                                                                           \
+    /* 65536-point rows; forward K1 with 44 of 64 segments: the 45056-point facet of the 128k workloads */            \
+    X(BandGeo64k, 0, 0, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo64k, 0, 1, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo64k, 0, 2, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo64k, 0, 2, 0, 0, -1, 0, 0, 1)                                                                             \
+    X(BandGeo64k, 1, 0, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo64k, 1, 1, 0, 0, -1, 0, 0, 0)                                                                             \
+    X(BandGeo64k, 1, 1, 0, 0, -1, 0, 1, 0)                                                                             \
+    X(BandGeo64k, 1, 1, 0, 44, 1, 0, 0, 0)                                                                             \
+    X(BandGeo64k, 1, 1, 0, 44, 1, 0, 1, 0)
 
 // -- re-laid-out load windows (Win4Cache, swiftly_rowpass.h) ------------------------------------------------------
 // entry (p * T + t), T = seglen / 2 lanes: the window pairs of the p-th segment pair of the K1 load loop -- segments
@@ -190,181 +209,59 @@ void Win4Cache::clear() {
     items.clear();
 }
 
-template <class G, bool PAIR = false>
-static int launch_band_geo(const RowPassArgs& a0, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s,
-                           Win4Cache* w4cache = nullptr) {
-    RowPassArgs a = a0;
-    a.seg_rot = 0;
-    const unsigned blocks = (unsigned)(((a.nrows + 7) / 8) * 16);
-    const bool band = a.band_len > 0;
-    // instances with empty segments compiled out (PAIR geometry of the 32768-point rows, 65536-point geometry): the
-    // forward K1 (window, band store) and the backward finish (no load window, mapped store)
-    constexpr bool SEGS = PAIR || (G::LOGN == 15 && G::LOGP == 5);
-    if constexpr (SEGS) {
-        constexpr int SEGLEN = PAIR ? 2 * G::T : G::T;
-        int first = 0;
-        const int run = data_segment_run(a, 2 * G::N, SEGLEN, &first);
-#define SWF_TRY_SEG(WIN, ST, NS, CJ)                                                    \
-    if (run <= NS) {                                                                    \
-        a.seg_rot = first;                                                              \
-        return launch_band_inst<G, PAIR, WIN, ST, NS, CJ>(a, blocks, tw14, tw_full, s); \
-    }
-        // these instances also have the conjugations compiled in (CJ): prepare_facet is an inverse transform (both
-        // set), finish_facet a forward one (neither)
-        const bool inv = a.conj_ld && a.conj_st, fwd = !a.conj_ld && !a.conj_st;
-        if constexpr (PAIR) {
-            if (a.band_len > 0 && a.ld_win && inv) {
-                // forward K1: geometry with the twiddle preload (RGeoPre)
-                using GP = RGeoPre<G::LOGN, G::LOGP, G::SPLIT>;
-                using GC = RGeoPreC<G::LOGN, G::LOGP, G::SPLIT>;
-                // ... and, when the caller owns a table cache, the window through 16-byte loads (W4)
-#define SWF_TRY_SEG_PRE(NS)                                                                    \
-    if (run <= NS) {                                                                           \
-        a.seg_rot = first;                                                                     \
-        constexpr int n_ = 2 * G::N;                                                           \
-        const int c_ = (int)(((long long)a.ld_a + n_ / 2 + (long long)first * SEGLEN) % n_);   \
-        a.ld_win4 = (w4cache && win4_enabled()) ? w4cache->get(a.ld_win, c_, a.ld_len, NS, n_, SEGLEN, s) : nullptr; \
-        a.twc = (a.ld_win4 && win4_enabled() >= 2) ? w4cache->twc : nullptr;               \
-        {   /* whole-row form: the window-rows store (win_full), or SWIFTLY_K1_WHOLE=1 for the band store */ \
-            const int ew_ = launch_row_pass_whole(a, NS, tw14, tw_full, s);                    \
-            if (ew_ != -2 || a.win_full) return ew_;                                           \
-        }                                                                                      \
-        if (a.twc) return launch_band_inst<GC, PAIR, true, 1, NS, 1, true>(a, blocks, tw14, tw_full, s); \
-        if (a.ld_win4) return launch_band_inst<GP, PAIR, true, 1, NS, 1, true>(a, blocks, tw14, tw_full, s); \
-        return launch_band_inst<GP, PAIR, true, 1, NS, 1>(a, blocks, tw14, tw_full, s);        \
-    }
-                SWF_TRY_SEG_PRE(16)
-                SWF_TRY_SEG_PRE(22)
-                SWF_TRY_SEG_PRE(24)
-#undef SWF_TRY_SEG_PRE
-                if (a.win_full) return -2;  // window-rows store: only the instances above
-            } else if (a.band_len < 0 && fwd) {
-                // backward finish: compact twiddle sections when the caller owns the tables
-                using GB = RGeoC<G::LOGN, G::LOGP, G::SPLIT>;
-                a.twc = (w4cache && win4_enabled() >= 2) ? w4cache->twc : nullptr;
-#define SWF_TRY_SEG_C(NS)                                                                \
-    if (a.twc && run <= NS) {                                                            \
-        a.seg_rot = first;                                                               \
-        return launch_band_finish<GB, PAIR, NS, 0>(a, blocks, tw14, tw_full, s);         \
-    }
-                SWF_TRY_SEG_C(13)
-                SWF_TRY_SEG_C(16)
-#undef SWF_TRY_SEG_C
-#define SWF_TRY_SEG_FIN(NS)                                                         \
-    if (run <= NS) {                                                                \
-        a.seg_rot = first;                                                          \
-        return launch_band_finish<G, PAIR, NS, 0>(a, blocks, tw14, tw_full, s);     \
-    }
-                SWF_TRY_SEG_FIN(13)
-                SWF_TRY_SEG_FIN(16)
-#undef SWF_TRY_SEG_FIN
-            }
-        } else {
-            if (a.band_len > 0 && a.ld_win && inv) {
-                SWF_TRY_SEG(true, 1, 44, 1)
-            }
-        }
-#undef SWF_TRY_SEG
-    }
-#define SWF_LAUNCH_BAND(WIN, ST) launch_band_inst<G, PAIR, WIN, ST, 0>(a, blocks, tw14, tw_full, s)
-    if (a.band_len < 0) return launch_band_finish<G, PAIR, 0>(a, blocks, tw14, tw_full, s);  // mapped (crop + window) store: finish_* primitives
-    if (a.out_real) return -1;  // real output: the mapped store only
-    if (a.ld_win) return band ? SWF_LAUNCH_BAND(true, 1) : SWF_LAUNCH_BAND(true, 0);
-    return band ? SWF_LAUNCH_BAND(false, 1) : SWF_LAUNCH_BAND(false, 0);
-#undef SWF_LAUNCH_BAND
-}
-using BandGeo64k = RGeo<15, 5, true>;  // yN = 65536: 2 x 32768 points, 1024 threads x 32, 132 KB LDS, one workgroup per CU
-using BandGeo16k = RGeo<13, 4, true>;  // yN = 16384: 2 x  8192 points,  512 threads x 16, 33 KB LDS
 int launch_row_pass_band(const RowPassArgs& a, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s, Win4Cache* w4) {
     return launch_row_pass_band_n(15, a, tw14, tw_full, s, w4);
 }
-// Forward K1 of a REAL row (RowPassArgs::in_real; window, band store, inverse transform).  The instance is chosen the way
-// launch_row_pass_band_n chooses it for the same row promoted to a contiguous complex64 copy -- same geometry, same segment
-// count and rotation -- so that the values are that call's: at 32768 points the pair geometry whenever the shift and the
-// length are even, whatever the pitch and the base of the caller's rows, which only decide how a lane fetches its two
-// adjacent reals (one 8-byte load, or two 4-byte loads: REAL = 2).  Tuned: 8-byte loads with 16 / 22 / 24 data segments
-// (W4 window table, compact twiddles, load pipeline -- the instances the complex K1 of the benchmark runs) and the
-// 44-segment form of the 65536-point rows.  Without the window table (SWIFTLY_K1_WIN4 < 2, cache full) and for 4-byte
-// loads: the same instances with the plain window loads, whose products and twiddles are the same numbers.
-static int launch_band_real(int logn, const RowPassArgs& a0, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s,
-                            Win4Cache* w4cache) {
-    RowPassArgs a = a0;
-    a.seg_rot = 0;
-    if (!a.ld_win || a.band_len <= 0 || a.win_full || a.ld_c != 0 || a.ld_mod != a.ld_len) return -1;
-    const unsigned blocks = (unsigned)(((a.nrows + 7) / 8) * 16);
-    const bool inv = a.conj_ld && a.conj_st;
-    if (logn == 15) {
-        using G = BandGeo5;
-        using GP = RGeoPre<G::LOGN, G::LOGP, G::SPLIT>;
-        using GC = RGeoPreC<G::LOGN, G::LOGP, G::SPLIT>;
-        constexpr int n = 2 * G::N, SEGLEN = 2 * G::T;
-        // odd shift or length: the 512 x 32 geometry without pair loads, as for the promoted row
-        if ((a.ld_a & 1) || (a.ld_len & 1)) return launch_band_inst<G, false, true, 1, 0, -1, false, 1>(a, blocks, tw_half, tw_full, s);
-        // adjacent reals through ONE 8-byte load: even pitch (in reals), 8-byte-aligned base
-        const bool load8 = !(a.in_pitch & 1) && (reinterpret_cast<uintptr_t>(a.in) & 7) == 0;
-        int first = 0;
-        const int run = data_segment_run(a, n, SEGLEN, &first);
-        const int ns = !inv ? 0 : run <= 16 ? 16 : run <= 22 ? 22 : run <= 24 ? 24 : 0;
-        if (!ns)
-            return load8 ? launch_band_inst<G, true, true, 1, 0, -1, false, 1>(a, blocks, tw_half, tw_full, s)
-                         : launch_band_inst<G, true, true, 1, 0, -1, false, 2>(a, blocks, tw_half, tw_full, s);
-        a.seg_rot = first;
-        if (load8 && w4cache && win4_enabled() >= 2 && w4cache->twc) {
-            const int c = (int)(((long long)a.ld_a + n / 2 + (long long)first * SEGLEN) % n);
-            a.ld_win4 = w4cache->get(a.ld_win, c, a.ld_len, ns, n, SEGLEN, s);
-            if (a.ld_win4) {
-                a.twc = w4cache->twc;
-                if (ns == 16) return launch_band_inst<GC, true, true, 1, 16, 1, true, 1>(a, blocks, tw_half, tw_full, s);
-                if (ns == 22) return launch_band_inst<GC, true, true, 1, 22, 1, true, 1>(a, blocks, tw_half, tw_full, s);
-                return launch_band_inst<GC, true, true, 1, 24, 1, true, 1>(a, blocks, tw_half, tw_full, s);
-            }
-        }
-#define SWF_REAL_PLAIN(NS)                                                                                   \
-    if (ns == NS)                                                                                            \
-        return load8 ? launch_band_inst<GP, true, true, 1, NS, 1, false, 1>(a, blocks, tw_half, tw_full, s)  \
-                     : launch_band_inst<GP, true, true, 1, NS, 1, false, 2>(a, blocks, tw_half, tw_full, s);
-        SWF_REAL_PLAIN(16)
-        SWF_REAL_PLAIN(22)
-        SWF_REAL_PLAIN(24)
-#undef SWF_REAL_PLAIN
-        return -1;
-    }
-    if (logn == 16) {
-        using G = BandGeo64k;
-        int first = 0;
-        if (inv && data_segment_run(a, 2 * G::N, G::T, &first) <= 44) {
-            a.seg_rot = first;
-            return launch_band_inst<G, false, true, 1, 44, 1, false, 1>(a, blocks, tw_half, tw_full, s);
-        }
-        return launch_band_inst<G, false, true, 1, 0, -1, false, 1>(a, blocks, tw_half, tw_full, s);
-    }
-    if (logn == 14) return launch_band_inst<BandGeo16k, false, true, 1, 0, -1, false, 1>(a, blocks, tw_half, tw_full, s);
-    return -1;
+// what choose_band_instance reads of a call; table_available: what Win4Cache::get is assumed to answer
+static BandCall band_call_of(int logn, const RowPassArgs& a, const Win4Cache* w4, bool table_available) {
+    BandCall c;
+    c.logn = logn;
+    c.ld_a = a.ld_a, c.ld_len = a.ld_len, c.ld_c = a.ld_c, c.ld_mod = a.ld_mod;
+    c.ld_win = a.ld_win != nullptr;
+    c.band_sign = a.band_len > 0 ? 1 : a.band_len < 0 ? -1 : 0;
+    c.band_half = a.band_half;
+    c.conj_ld = a.conj_ld, c.conj_st = a.conj_st, c.accumulate = a.accumulate;
+    c.in_real = a.in_real, c.out_real = a.out_real;
+    c.pitch_odd = a.in_pitch & 1;
+    c.base_align = (int)(reinterpret_cast<uintptr_t>(a.in) & 15);
+    c.win_full = a.win_full;
+    c.win_logm = a.win_logm, c.nwin = a.nwin;
+    c.win_d = a.win_d, c.win_fn = a.win_fn, c.win_tw_m = a.win_tw_m, c.win_twc_m = a.win_twc_m;
+    c.win4_level = win4_enabled();
+    c.whole_enabled = row_pass_whole_enabled();
+    c.has_cache = w4 != nullptr;
+    c.has_twc = w4 && w4->twc;
+    c.table_available = table_available;
+    c.stage_columns = row_pass_whole_stage_columns(), c.max_windows = kWholeMaxWindows;
+    return c;
 }
-// logn = log2 of the full row length (14, 15 or 16); tw_half = table of length 2^(logn-1), tw_full of length 2^logn
-int launch_row_pass_band_n(int logn, const RowPassArgs& a, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s,
+// logn = log2 of the full row length (14, 15 or 16); tw_half = table of length 2^(logn-1), tw_full of length 2^logn.
+// Returns -1 when no instance takes the call and -2 when the window-rows form (RowPassArgs::win_full) does not apply.
+int launch_row_pass_band_n(int logn, const RowPassArgs& a0, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s,
                            Win4Cache* w4) {
-    if (a.nrows <= 0) return 0;
-    if (a.in_real) return launch_band_real(logn, a, tw_half, tw_full, s, w4);
-    if (a.out_real && (a.band_len >= 0 || a.win_full)) return -1;  // real output: the mapped store (launch_band_finish) only
-    if (a.win_full) {
-        // window-rows store (whole-row kernel): 32768-point rows, 512-column windows, 16-byte loads
-        if (logn != 15 || a.win_logm != 9 || a.nwin <= 0 || !a.win_d || a.band_len <= 0) return -2;
-        const bool pair_ok_w = !(a.ld_a & 1) && !(a.ld_len & 1) && !(a.in_pitch & 1) && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0;
-        if (!pair_ok_w || !a.ld_win || !(a.conj_ld && a.conj_st)) return -2;
-        return launch_band_geo<BandGeo5, true>(a, tw_half, tw_full, s, w4);
+    if (a0.nrows <= 0) return 0;
+    RowPassArgs a = a0;
+    // the choice is pure: made with the window table assumed available, and again without it when the cache has none
+    BandInst inst = choose_band_instance(band_call_of(logn, a, w4, true));
+    const float* table = nullptr;
+    if (inst.key_ns) {
+        table = w4->get(a.ld_win, inst.key_c, a.ld_len, inst.key_ns, inst.key_n, inst.key_seglen, s);
+        if (!table) inst = choose_band_instance(band_call_of(logn, a, w4, false));
     }
-    if (logn == 16) return launch_band_geo<BandGeo64k>(a, tw_half, tw_full, s);
-    if (logn == 14) return launch_band_geo<BandGeo16k>(a, tw_half, tw_full, s);
-    if (logn != 15) return -1;
-    const cx<float>* tw14 = tw_half;
-    // 512 threads x 32 points (two workgroups per CU) for the band store and the mapped store; 1024 x 16 (one per CU) for
-    // the plain store, where the 512-thread form spills ~49 VGPRs (1024 x 16 for the band store: 1.95 vs 1.73 ms per facet, r4)
-    if (a.band_len == 0) return launch_band_geo<BandGeo4>(a, tw14, tw_full, s);
-    // adjacent-point (16-byte) loads need even shifts / lengths / pitches
-    const bool pair_ok = !(a.ld_a & 1) && !(a.ld_len & 1) && !(a.in_pitch & 1) && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0;
-    if (pair_ok) return launch_band_geo<BandGeo5, true>(a, tw14, tw_full, s, w4);
-    return launch_band_geo<BandGeo5>(a, tw14, tw_full, s);
+    if (inst.status != kBandChosen) return inst.status;
+    a.seg_rot = inst.seg_rot;
+    a.ld_win4 = inst.ld_win4 ? table : nullptr;
+    a.twc = inst.twc ? w4->twc : nullptr;
+    if (inst.family == kBandWholeRow) return launch_row_pass_whole(a, inst.nseg, tw_half, tw_full, s);
+    const unsigned blocks = (unsigned)(((a.nrows + 7) / 8) * 16);
+#define SWF_BAND_LAUNCH(G, WIN, ST, PAIR, NSEG, CJ, W4, REAL, REAL_ST)                                                       \
+    if (inst.geo == k##G && inst.win == WIN && inst.st == ST && inst.pair == PAIR && inst.nseg == NSEG && inst.cj == CJ &&   \
+        inst.w4 == W4 && inst.real == REAL && inst.real_st == REAL_ST)                                                       \
+        return launch_lds<row_pass_band_kernel<G, WIN, ST, PAIR, NSEG, CJ, W4, REAL, REAL_ST>, G::LDS_BYTES>(                \
+            dim3(blocks), dim3(G::NT), s, a, a.in, a.out, a.ld_win, tw_half, tw_full);
+    SWF_BAND_INSTANCES(SWF_BAND_LAUNCH)
+#undef SWF_BAND_LAUNCH
+    return -1;  // the choice names an instance the list lacks: a bug (tests/test_band_instances_cpu.py)
 }
 int row_pass_band_occupancy() {
     int n = -1;

@@ -20,7 +20,7 @@ extern "C" int swiftly_hip_wtrace_fetch(void* host, size_t bytes) {
 // SWIFTLY_K1_WHOLE: 1 = the plain band store too runs as one persistent workgroup per CU that owns whole rows (A/B runs of
 // the r6 experiment: no faster than the two-workgroup form, tools/experiments/README.md); default 0 -- the whole-row form is
 // the K1 of the axis-1-first pipeline only (RowPassArgs::win_full).  Read once per process.
-static int whole_enabled() {
+int row_pass_whole_enabled() {
     static const int v = getenv("SWIFTLY_K1_WHOLE") ? atoi(getenv("SWIFTLY_K1_WHOLE")) : 0;
     return v;
 }
@@ -42,26 +42,14 @@ static int launch_whole_inst(const RowPassArgs& a, const cx<float>* tw14, const 
 }
 
 // forward K1 with the re-laid-out window (a.ld_win4) and the compact twiddle sections (a.twc) set, a.seg_rot chosen for
-// `nseg` data segments; returns -2 when this form does not apply (the caller launches the two-workgroup kernel)
+// `nseg` data segments; a.win_full: the window-rows store.  Whether a call runs this form is choose_band_instance's
+// decision (swiftly_rowinst.h); -1: no instance for `nseg`
 int launch_row_pass_whole(const RowPassArgs& a, int nseg, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s) {
-    if (!a.ld_win4 || !a.twc || a.band_len <= 0 || !(a.conj_ld && a.conj_st)) return -2;
-    if (a.win_full) {
-        if (a.win_logm != 9 || !a.win_d || a.nwin <= 0 || a.nwin > kWholeMaxWindows || !a.win_fn || !a.win_tw_m || !a.win_twc_m ||
-            2 * a.band_half > row_pass_whole_stage_columns())
-            return -2;
-        switch (nseg) {
-            case 16: return launch_whole_inst<16, true>(a, tw14, tw_full, s);
-            case 22: return launch_whole_inst<22, true>(a, tw14, tw_full, s);
-            case 24: return launch_whole_inst<24, true>(a, tw14, tw_full, s);
-            default: return -2;
-        }
-    }
-    if (!whole_enabled()) return -2;
     switch (nseg) {
-        case 16: return launch_whole_inst<16>(a, tw14, tw_full, s);
-        case 22: return launch_whole_inst<22>(a, tw14, tw_full, s);
-        case 24: return launch_whole_inst<24>(a, tw14, tw_full, s);
-        default: return -2;
+        case 16: return a.win_full ? launch_whole_inst<16, true>(a, tw14, tw_full, s) : launch_whole_inst<16>(a, tw14, tw_full, s);
+        case 22: return a.win_full ? launch_whole_inst<22, true>(a, tw14, tw_full, s) : launch_whole_inst<22>(a, tw14, tw_full, s);
+        case 24: return a.win_full ? launch_whole_inst<24, true>(a, tw14, tw_full, s) : launch_whole_inst<24>(a, tw14, tw_full, s);
+        default: return -1;
     }
 }
 
