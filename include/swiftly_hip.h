@@ -682,6 +682,16 @@ int swiftly_hip_cu_census(int32_t* out, int nblocks, void* stream);
  *    per-device attribute is set by swiftly_hip_create) and the largest LDS size in bytes among them.  No device needed. */
 int swiftly_hip_kernel_table(int64_t* count, int64_t* max_lds_bytes);
 
+/* -- which instance of the band row kernel (the contiguous-axis kernel of prepare_facet_band / finish_facet_band and of
+ *    prepare_facet / finish_facet on 32768 and 65536 points) the calling thread's last launch ran.  Writes the first
+ *    min(n, 18) of: status (0 launched, -1 / -2 refused), family (0 two workgroups per row, 1 whole row), geometry, WIN,
+ *    ST, PAIR, NSEG, CJ, W4, REAL, REAL_ST (the template arguments), seg_rot, ld_win4, twc (window table / compact twiddles
+ *    in use), and the key of the window table (c, segments, n, segment length; segments = 0: none).  The record is taken
+ *    after the fallback of a full window-table cache.  Returns the number of band row launches the calling thread has made
+ *    so far (refused ones included, calls without rows not).  No device needed: before the first launch 0 and the default
+ *    record. */
+int64_t swiftly_hip_last_band_instance(int32_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,13 @@ static BandCall band_call_of(int logn, const RowPassArgs& a, const Win4Cache* w4
     c.stage_columns = row_pass_whole_stage_columns(), c.max_windows = kWholeMaxWindows;
     return c;
 }
+// per thread: the instance the last call with rows settled on, and the number of such calls (last_band_instance)
+static thread_local BandInst t_last_band;
+static thread_local long long t_band_calls = 0;
+long long last_band_instance(BandInst* out) {
+    if (out) *out = t_last_band;
+    return t_band_calls;
+}
 // logn = log2 of the full row length (14, 15 or 16); tw_half = table of length 2^(logn-1), tw_full of length 2^logn.
 // Returns -1 when no instance takes the call and -2 when the window-rows form (RowPassArgs::win_full) does not apply.
 int launch_row_pass_band_n(int logn, const RowPassArgs& a0, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s,
@@ -248,6 +255,7 @@ int launch_row_pass_band_n(int logn, const RowPassArgs& a0, const cx<float>* tw_
         table = w4->get(a.ld_win, inst.key_c, a.ld_len, inst.key_ns, inst.key_n, inst.key_seglen, s);
         if (!table) inst = choose_band_instance(band_call_of(logn, a, w4, false));
     }
+    t_last_band = inst, t_band_calls++;  // (what last_band_instance answers: the choice after the fallback, refusals too)
     if (inst.status != kBandChosen) return inst.status;
     a.seg_rot = inst.seg_rot;
     a.ld_win4 = inst.ld_win4 ? table : nullptr;

@@ -1,6 +1,7 @@
 // C ABI of libswiftly_hip.so, part 3: device memory / stream helpers for callers without their own allocator,
 // CU-partitioned streams and diagnostics (include/swiftly_hip.h, last section).
 #include "swiftly_abi_internal.h"
+#include "swiftly_rowinst.h"
 #include "build/build_id.h"
 
 // where does this workgroup run?  xcc_id << 16 | se_id << 8 | cu_id  (HW_REG_XCC_ID, HW_REG_HW_ID of gfx9);
@@ -151,6 +152,14 @@ int swiftly_hip_kernel_table(int64_t* count, int64_t* max_lds_bytes) {
         *max_lds_bytes = std::max<int64_t>(*max_lds_bytes, e.lds_bytes);
     }
     return 0;
+}
+int64_t swiftly_hip_last_band_instance(int32_t* out, int n) {
+    BandInst b;
+    const int64_t calls = last_band_instance(&b);
+    const int32_t fields[18] = {b.status, b.family, b.geo, b.win, b.st, b.pair, b.nseg, b.cj, b.w4, b.real, b.real_st,
+                                b.seg_rot, b.ld_win4, b.twc, b.key_c, b.key_ns, b.key_n, b.key_seglen};
+    for (int i = 0; out && i < n && i < 18; i++) out[i] = fields[i];
+    return calls;
 }
 
 }  // extern "C"

@@ -892,6 +892,11 @@ struct Win4Cache {
 int launch_row_pass_band(const RowPassArgs& a, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s, Win4Cache* w4 = nullptr);
 int launch_row_pass_band_n(int logn, const RowPassArgs& a, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s,
                            Win4Cache* w4 = nullptr);
+// diagnostic (swiftly_hip_last_band_instance): the BandInst (swiftly_rowinst.h) the calling thread's last
+// launch_row_pass_band_n settled on -- after the window-table fallback; a refused call with its status -- and how many such
+// calls with rows the thread has made.  No device needed; before the first call: a default BandInst and 0.
+struct BandInst;
+long long last_band_instance(BandInst* out);
 int row_pass_band_occupancy();
 int launch_row_pass_whole(const RowPassArgs& a, int nseg, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s);
 int row_pass_whole_grid();  // workgroups of a whole-row launch (one per CU)

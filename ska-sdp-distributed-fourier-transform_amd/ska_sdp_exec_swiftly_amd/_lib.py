@@ -203,6 +203,8 @@ def _declare(lib):
     lib.swiftly_hip_cu_census.argtypes = [vp, c_int, vp]
     lib.swiftly_hip_kernel_table.restype = c_int
     lib.swiftly_hip_kernel_table.argtypes = [POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]
+    lib.swiftly_hip_last_band_instance.restype = ctypes.c_int64
+    lib.swiftly_hip_last_band_instance.argtypes = [POINTER(ctypes.c_int32), c_int]
 
 
 def load():

@@ -145,6 +145,95 @@ def test_the_instance_list_is_what_the_chooser_names(golden):
     assert not [i for i in instance_list() if GEOS[i[0]] == "BandGeo5" and i[2] == 0]
 
 
+def test_every_instance_has_an_oracle_case_or_a_reason():
+    """tests/band_instance_cases.py (what tests/test_hip_band_instance_sweep_gpu.py runs against the oracle) leaves out no
+    instance of the list and of the whole-row family, except those it names as unreachable through the C ABI"""
+    import band_instance_cases as bic
+
+    assert bic.GEOS == GEOS
+    run = {bic.instance_key(c["want"]) for c in bic.CASES}
+    unreachable = {bic.instance_key(k) for k in bic.NOT_REACHABLE_THROUGH_THE_ABI}
+    assert all(len(why.split()) > 5 for why in bic.NOT_REACHABLE_THROUGH_THE_ABI.values())
+    everything = set(instance_list()) | {(ns, st) for ns in (16, 22, 24) for st in (1, 3)}
+    assert run | unreachable == everything, (sorted(everything - run - unreachable), sorted((run | unreachable) - everything))
+    assert not run & unreachable
+    print(f"band row kernel instances: {len(run)} with an oracle case, {len(unreachable)} unreachable, {len(everything)} in all")
+    assert (len(run), len(unreachable), len(everything)) == (53, 7, 60)
+    # every instance with compiled-out segments at a rotation of 0 and at another one (the data wrap the end of the row)
+    for key in run:
+        rots = {c["seg_rot"] for c in bic.CASES if bic.instance_key(c["want"]) == key}
+        if key[4 if len(key) > 2 else 0] != 0:
+            assert 0 in rots and rots - {0}, (key, rots)
+        else:
+            assert rots == {None}, key
+    # 7 rows (not a multiple of the 8 rows of a workgroup group) everywhere, 17 rows (three groups) once per geometry
+    assert {c["rows"] for c in bic.CASES} == {7, 17}
+    assert {c["want"][0] for c in bic.CASES if c["rows"] == 17} == set(GEOS[:-1]) | {"whole"}
+    assert {tuple(sorted(c["knob"].items())) for c in bic.CASES} == {(), (("SWIFTLY_K1_WIN4", "0"),), (("SWIFTLY_K1_WIN4", "1"),),
+                                                                     (("SWIFTLY_K1_WHOLE", "1"),)}
+
+
+def test_every_case_runs_the_instance_the_chooser_names(dump):
+    """the expectation of every case against ``choose_band_instance`` for the BandCall the case spells out; and the maps of
+    that BandCall against the closed forms of the entry point's arguments"""
+    import band_instance_cases as bic
+
+    got = choose(dump, [c["call"] for c in bic.CASES])
+    for case, have in zip(bic.CASES, got):
+        call, want = case["call"], case["want"]
+        assert have["status"] == 0, case["id"]
+        if want[0] == "whole":
+            assert (have["family"], GEOS[have["geo"]], have["nseg"], have["st"]) == (1, "BandGeoWhole") + tuple(want[1:]), case["id"]
+        else:
+            assert have["family"] == 0 and (GEOS[have["geo"]],) + tuple(have[k] for k in TEMPLATE[1:]) == tuple(want), (case["id"], have)
+        if case["seg_rot"] is not None:
+            assert have["seg_rot"] == case["seg_rot"], (case["id"], have["seg_rot"])
+            # the first data segment, counted on the padded row: transform input j holds element (j + n/2 + ld_a) mod n
+            n = 1 << call["logn"]
+            q = (numpy.arange(n) + n // 2 + call["ld_a"]) % n
+            has = (q < call["ld_len"]).reshape(-1, 1024).any(axis=1)
+            assert has[case["seg_rot"]] and not has[case["seg_rot"] - 1] and has.sum() <= have["nseg"], case["id"]
+        # the knob level decides the window path
+        level = int(case["knob"].get("SWIFTLY_K1_WIN4", 2))
+        assert call["win4_level"] == level and call["whole_enabled"] == int(case["knob"].get("SWIFTLY_K1_WHOLE", 0))
+        assert call["table_available"] == call["has_cache"] and call["has_twc"] == (call["has_cache"] and call["logn"] == 15)
+        assert have["ld_win4"] <= (level > 0) and have["twc"] <= (level > 1)
+        # the load map from the arguments: where pixel 0 of the facet / subgrid / band lies on the padded axis
+        W, N, xM, yN = bic.CORES[case["core"]]
+        n = xM if case["kind"] == "prepare_subgrid" else yN
+        assert n == 1 << call["logn"]
+        first = case["band"][0] if case["kind"] == "finish" else (n // 2 - case["size"] // 2 + case["off"]) % n
+        assert (first + call["ld_a"]) % n == 0, case["id"]
+        assert call["ld_len"] == (case["band"][1] if case["kind"] == "finish" else case["size"]) == call["ld_mod"]
+
+
+def test_last_band_instance_without_a_launch():
+    """``swiftly_hip_last_band_instance`` needs no device; the record and the counter belong to the calling thread: a
+    thread that never launched reads 0 and a default BandInst"""
+    import ctypes
+    import threading
+
+    from ska_sdp_exec_swiftly_amd import _lib
+
+    lib = _lib.load()
+    seen = {}
+
+    def ask():
+        for n in (18, 5, 40, 0):
+            buf = (ctypes.c_int32 * 20)(*([77] * 20))
+            seen[n] = (lib.swiftly_hip_last_band_instance(buf, n), list(buf))
+        seen["null"] = lib.swiftly_hip_last_band_instance(None, 18)
+
+    thread = threading.Thread(target=ask)
+    thread.start()
+    thread.join()
+    default = dict(zip(INST, [0] * 18), cj=-1)
+    assert seen["null"] == 0
+    for n, (count, buf) in ((k, v) for k, v in seen.items() if k != "null"):
+        assert count == 0
+        assert buf[: min(n, 18)] == [default[k] for k in INST][: min(n, 18)] and set(buf[min(n, 18) :]) == {77}, (n, buf)
+
+
 def test_real_rows_get_the_instance_of_the_promoted_row(dump, golden):
     """A real call -- whatever its pitch and base -- against the complex call for the same row promoted to a contiguous,
     aligned complex64 copy: same geometry, pair loads, segment count, conjugations and rotation.  The window path may
