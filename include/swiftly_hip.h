@@ -113,9 +113,12 @@ enum {
     SWIFTLY_FEATURE_REAL_FACETS = 8,            /* prepare_facet_band_real / prepare_facet_band_rows_real (dtype = the OUTPUT
                                                    type): the sizes of BAND_PIPELINE in complex64 with a power-of-two yN_size;
                                                    no complex128, no Q * 2^k.  The gate both entry points refuse through */
-    SWIFTLY_FEATURE_REAL_FACETS_OUT = 9         /* finish_facet_band_real (dtype = the INPUT type): the sizes of BACKWARD_BAND
+    SWIFTLY_FEATURE_REAL_FACETS_OUT = 9,        /* finish_facet_band_real (dtype = the INPUT type): the sizes of BACKWARD_BAND
                                                    in complex64 with a power-of-two yN_size; no complex128, no Q * 2^k.  The
                                                    gate the entry point refuses through */
+    SWIFTLY_FEATURE_GROUP_FINISH = 10           /* wave_group_finish_pieces (dtype, n_facets): FUSED_SUBGRID in complex64 with
+                                                   (m, xM) = (128, 256) or (512, 1024) and n_facets * xM / m <= 64.  The gate
+                                                   the entry point refuses through */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -499,6 +502,34 @@ int swiftly_hip_wave_subgrid_side(swiftly_hip_t* h, int dtype, const void* g, in
                                   int64_t nsub, const int64_t* sub_off0s, const int64_t* sub_off1s, int64_t subgrid_size,
                                   const void* mask0, int64_t mask0_bs, const void* mask1, int64_t mask1_bs,
                                   void* tmp_work, void* out, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* The subgrid side of one forward wave with the STRIDED axis finished first, straight from the wave's K2 buffers (the
+ * pieces of transform_contributions_pieces: same arguments, same checks), in two kernels instead of K3 + sum_finish_facets
+ * + finish_subgrid(axis 0):
+ *   stage 1 (group_finish): per facet off1 group g, subgrid b and column j of the m-wide window
+ *       T[g][b][a, j] = mask0_b[a] * finish_subgrid_axis0( sum_{f in g} add_to_subgrid_axis0( C_f[:, j], facet_off0s[f] ) )[a]
+ *     with C_f the window rows of facet f (extract_from_facet along axis 0 from Q), a < subgrid_size;
+ *   stage 2 (sum_finish_facets over the rows of T): out[b][a, :] = mask1_b * finish_subgrid_axis1( sum_g
+ *       add_to_subgrid_axis1( T[g][b][a, :], off1 of group g ) ).
+ * The facet sums of api_helper.sum_and_finish_subgrid (api_helper.py:81-99) re-associated once more: the same subgrids as
+ * transform_contributions_pieces + wave_subgrid_side up to float32 rounding, not the same bits, for 48.6 instead of 78.8 MB
+ * of HBM traffic per subgrid on the N = 65536 workload.  Groups are numbered by ascending facet off1; within a group the
+ * facets are summed in list order.  t_work: device scratch T[ngroups][nsub][xM][m] complex elements (t_work_elems >=
+ * ngroups * nsub * xM * m; only subgrid_size of every xM rows are touched).  stages: 1 | 2 | 3 (both; a test may run
+ * either kernel alone on a T of its own).  out[nsub][subgrid_size][subgrid_size].  complex64,
+ * swiftly_hip_supports(SWIFTLY_FEATURE_GROUP_FINISH). */
+int swiftly_hip_wave_group_finish_pieces(swiftly_hip_t* h, int dtype, int64_t npieces, const void* const* q,
+                                         const int64_t* q_facet_strides, const int32_t* const* rowmaps,
+                                         const int64_t* n_rows, const int64_t* first, const int64_t* count,
+                                         int64_t nfacets, const int64_t* facet_off0s, const int64_t* facet_off1s,
+                                         int64_t nsub, const int64_t* sub_off0s, const int64_t* sub_off1s,
+                                         int64_t subgrid_size, const void* mask0, int64_t mask0_bs, const void* mask1,
+                                         int64_t mask1_bs, void* t_work, int64_t t_work_elems, void* out, int stages,
+                                         void* stream);
+/* Process-wide switch between that form and K3 + wave_subgrid_side for the callers that own both halves (A/B runs and
+ * tests): sets it to on != 0 and returns the previous value; on < 0 only queries.  Initial value 1, or 0 with the
+ * environment variable SWIFTLY_GROUP_FINISH=0.  (No reference counterpart: scheduling of this implementation.) */
+int swiftly_hip_group_finish(int on);
 
 /* AXIS-1-FIRST forward pipeline (r6; opt-in: the accuracy mode that replaces float64 column passes).  The transforms of
  * the two axes commute (api_helper.py:81-99, 200-210), so the contiguous-axis half of add_to_subgrid (core.py:255-285:

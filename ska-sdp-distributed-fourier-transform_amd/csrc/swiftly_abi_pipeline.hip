@@ -3,6 +3,7 @@
 // band accumulators").  Each one is a short launch sequence over the column-tile passes (swiftly_colpass.h) and the
 // row-wise fused kernels (swiftly_sumfinish.h).
 #include "swiftly_abi_internal.h"
+#include "swiftly_groupfinish.h"
 
 // touched[d] = 1 for the band columns d of one wave's window (see accumulate_facet_columns)
 __global__ void mark_columns_kernel(unsigned char* __restrict__ touched, int m, int rot, int base, int yN, int band_start,
@@ -447,8 +448,32 @@ static int transform_contributions_impl(swiftly_hip_t* h, int dtype, const void*
     return 0;
 }
 
+// The pieces of a wave's window (transform_contributions_pieces, wave_group_finish_pieces): up to two, multiples of 16,
+// disjoint, together exactly [0, m), each with rows enough behind its facet stride
+static int check_window_pieces(const swiftly_hip_t* h, const char* who, int64_t npieces, const void* const* q,
+                               const int64_t* q_facet_strides, const int64_t* n_rows, const int64_t* first,
+                               const int64_t* count) {
+    if (npieces < 0 || npieces > 2) return fail(SWIFTLY_ERR_PARAM, "%s: 0..2 pieces, got %lld", who, (long long)npieces);
+    const int64_t m = h->m;
+    int64_t covered = 0;
+    for (int64_t i = 0; i < npieces; i++) {
+        if (count[i] < 0 || first[i] < 0 || first[i] + count[i] > m || first[i] % 16 || count[i] % 16)
+            return fail(SWIFTLY_ERR_PARAM, "%s: piece %lld = [%lld, +%lld) must be multiples of 16 "
+                        "inside [0, %lld)", who, (long long)i, (long long)first[i], (long long)count[i], (long long)m);
+        if (count[i] && (!q[i] || n_rows[i] <= 0 || n_rows[i] > h->yN || q_facet_strides[i] < n_rows[i] * m))
+            return fail(SWIFTLY_ERR_PARAM, "bad row count %lld / facet stride %lld", (long long)n_rows[i], (long long)q_facet_strides[i]);
+        covered += count[i];
+    }
+    if (npieces == 2 && count[0] && count[1] && first[0] < first[1] + count[1] && first[1] < first[0] + count[0])
+        return fail(SWIFTLY_ERR_PARAM, "%s: the pieces overlap", who);
+    if (covered != m) return fail(SWIFTLY_ERR_PARAM, "%s: the pieces hold %lld of %lld positions", who, (long long)covered, (long long)m);
+    return 0;
+}
+
 // SWIFTLY_K3_ONE_LAUNCH=0: K3 of a window in two pieces as one launch sequence per piece (A/B runs; swiftly_hip_k3_one_launch)
 static std::atomic<int> g_k3_one_launch{getenv("SWIFTLY_K3_ONE_LAUNCH") ? atoi(getenv("SWIFTLY_K3_ONE_LAUNCH")) != 0 : 1};
+// SWIFTLY_GROUP_FINISH=0: the callers that own K3 and the finish keep K3 + wave_subgrid_side (A/B runs; swiftly_hip_group_finish)
+static std::atomic<int> g_group_finish{getenv("SWIFTLY_GROUP_FINISH") ? atoi(getenv("SWIFTLY_GROUP_FINISH")) != 0 : 1};
 
 extern "C" {
 int swiftly_hip_k3_one_launch(int on) {
@@ -483,22 +508,10 @@ int swiftly_hip_transform_contributions_pieces(swiftly_hip_t* h, int dtype, int6
                                                const int64_t* g_facet_strides, void* stream) {
     if (!h || !q || !q_facet_strides || !rowmaps || !n_rows || !first || !count || !g_out || !facet_off0s || !sub_off0s)
         return fail(SWIFTLY_ERR_PARAM, "null argument");
-    if (npieces < 0 || npieces > 2) return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: 0..2 pieces, got %lld", (long long)npieces);
     if (!g_offsets != !g_facet_strides) return fail(SWIFTLY_ERR_PARAM, "g_offsets and g_facet_strides go together");
+    if (int rc = check_window_pieces(h, "transform_contributions_pieces", npieces, q, q_facet_strides, n_rows, first, count)) return rc;
     DeviceGuard device_guard_(h->device);
     const int64_t m = h->m;
-    int64_t covered = 0;
-    for (int64_t i = 0; i < npieces; i++) {
-        if (count[i] < 0 || first[i] < 0 || first[i] + count[i] > m || first[i] % 16 || count[i] % 16)
-            return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: piece %lld = [%lld, +%lld) must be multiples of 16 "
-                        "inside [0, %lld)", (long long)i, (long long)first[i], (long long)count[i], (long long)m);
-        if (count[i] && (!q[i] || n_rows[i] <= 0 || n_rows[i] > h->yN || q_facet_strides[i] < n_rows[i] * m))
-            return fail(SWIFTLY_ERR_PARAM, "bad row count %lld / facet stride %lld", (long long)n_rows[i], (long long)q_facet_strides[i]);
-        covered += count[i];
-    }
-    if (npieces == 2 && count[0] && count[1] && first[0] < first[1] + count[1] && first[1] < first[0] + count[0])
-        return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: the pieces overlap");
-    if (covered != m) return fail(SWIFTLY_ERR_PARAM, "transform_contributions_pieces: the pieces hold %lld of %lld positions", (long long)covered, (long long)m);
     if (npieces == 2 && count[0] && count[1] && g_k3_one_launch.load()) {
         const int b = first[0] == 0 ? 0 : 1, a = 1 - b;  // piece b holds [0, split), piece a [split, m)
         const SecondSource second = {q[b], q_facet_strides[b], rowmaps[b], count[b]};
@@ -798,6 +811,118 @@ int swiftly_hip_wave_subgrid_side_placed(swiftly_hip_t* h, int dtype, const void
                                   1, stream);
 }
 
+
+/* The subgrid side of a wave with the strided axis finished first (swiftly_groupfinish.h): group_finish from the K2 pieces
+ * into T[g][b][xM rows, subgrid_size used][m], then sum_finish_facets over the rows of T.  The row kernel is the one
+ * wave_subgrid_side runs, unchanged: a group's T[g][b] enters it as xM / m "facets" of m rows each (entry c = rows
+ * [c m, (c + 1) m), band start c m), so every row is covered by exactly one entry per group and is read as it lies. */
+int swiftly_hip_group_finish(int on) {
+    return on < 0 ? g_group_finish.load() : g_group_finish.exchange(on ? 1 : 0);
+}
+
+int swiftly_hip_wave_group_finish_pieces(swiftly_hip_t* h, int dtype, int64_t npieces, const void* const* q,
+                                         const int64_t* q_facet_strides, const int32_t* const* rowmaps,
+                                         const int64_t* n_rows, const int64_t* first, const int64_t* count,
+                                         int64_t nfacets, const int64_t* facet_off0s, const int64_t* facet_off1s,
+                                         int64_t nsub, const int64_t* sub_off0s, const int64_t* sub_off1s,
+                                         int64_t subgrid_size, const void* mask0, int64_t mask0_bs, const void* mask1,
+                                         int64_t mask1_bs, void* t_work, int64_t t_work_elems, void* out, int stages,
+                                         void* stream) {
+    if (!h || !q || !q_facet_strides || !rowmaps || !n_rows || !first || !count || !t_work || !facet_off0s || !facet_off1s ||
+        !sub_off0s || !sub_off1s || (!out && (stages & 2)))
+        return fail(SWIFTLY_ERR_PARAM, "null argument");
+    if (stages < 1 || stages > 3) return fail(SWIFTLY_ERR_PARAM, "wave_group_finish_pieces: stages must be 1, 2 or 3");
+    CHECK_SUBGRID_SIZE();
+    if (nfacets <= 0) return fail(SWIFTLY_ERR_UNSUPPORTED, "wave_group_finish_pieces: 1..%d facets supported", kGroupFinishMaxFacets);
+    // (the gate of swiftly_hip_supports(GROUP_FINISH): a caller that asked it is never refused here)
+    if (const std::string why = why_not_group_finish(*h, dtype, nfacets); !why.empty())
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "wave_group_finish_pieces: %s", why.c_str());
+    if (h->col_f64)
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "wave_group_finish_pieces: float32 column arithmetic only (column precision is 64)");
+    if (int rc = check_window_pieces(h, "wave_group_finish_pieces", npieces, q, q_facet_strides, n_rows, first, count)) return rc;
+    if (nsub <= 0) return 0;
+    DeviceGuard device_guard_(h->device);
+    const int m = (int)h->m, xM = (int)h->xM, xA = (int)subgrid_size, yN = (int)h->yN, ratio = xM / m;
+    CHECK_OFFSETS_32(offsets_fit_32(yN, m, yN));
+
+    SumFinishFacetArgs r;  // stage 2; its facet tables first serve as the grouping of the real facets
+    std::memset(&r, 0, sizeof r);
+    fill_facet_groups(r, h, nfacets, facet_off0s, facet_off1s);
+    const int ngroups = r.ngroups;
+    if (t_work_elems < (int64_t)ngroups * nsub * xM * m)
+        return fail(SWIFTLY_ERR_PARAM, "t_work holds %lld elements, %lld needed", (long long)t_work_elems,
+                    (long long)((int64_t)ngroups * nsub * xM * m));
+    GroupFinishArgs a;
+    std::memset(&a, 0, sizeof a);
+    for (int n = 0; n < nfacets; n++) {
+        a.fidx[n] = r.fidx[n];
+        a.sp0[n] = (int)facet_shift(*h, facet_off0s[r.fidx[n]]);
+    }
+    for (int g = 0; g <= ngroups; g++) a.gstart[g] = r.gstart[g];
+    // piece B holds the window positions [0, split), piece A the others; one piece: A
+    int pa = -1, pb = -1;
+    for (int64_t i = 0; i < npieces; i++) {
+        if (!count[i]) continue;
+        if (first[i] == 0 && count[i] < m) pb = (int)i; else pa = (int)i;
+    }
+    a.in_a = (const cx<float>*)q[pa]; a.in_fs_a = q_facet_strides[pa]; a.rowmap_a = rowmaps[pa];
+    if (pb >= 0) {
+        a.in_b = (const cx<float>*)q[pb]; a.in_fs_b = q_facet_strides[pb]; a.rowmap_b = rowmaps[pb];
+        a.split = (int)count[pb];
+    }
+    a.in_pitch = (unsigned)m;
+    a.out_gs = (long long)nsub * xM * m; a.out_bs = (long long)xM * m;
+    a.yN = yN; a.xA = xA; a.ncols = m;
+    a.fn = h->fn_f;
+    a.tw_m = twiddles<float>(h, h->log_m);
+    a.tw_x = twiddles<float>(h, h->log_xM);
+    if (!a.fn || !a.tw_m || !a.tw_x) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
+    a.mask_bs = mask0 ? mask0_bs : 0;
+
+    // the row kernel's view of T: xM / m entries of m rows per group
+    for (int g = 0; g < ngroups; g++) {
+        r.gstart[g] = g * ratio;
+        for (int c = 0; c < ratio; c++) {
+            r.fidx[g * ratio + c] = (int)((int64_t)g * nsub * ratio + c);
+            r.base0[g * ratio + c] = c * m;
+        }
+    }
+    r.gstart[ngroups] = ngroups * ratio;
+    r.nfacets = ngroups * ratio;
+    r.in_fs = (long long)m * m; r.in_bs = (long long)xM * m; r.in_rs = m;
+    r.out_bs = (long long)xA * xA; r.out_rs = xA;
+    r.nrows = xA;  // the rows group_finish kept
+    r.xA = xA;
+    fill_group_rounds(r, h);
+    r.mask_bs = mask1 ? mask1_bs : 0;
+    if (int rc = fill_sum_finish_tables(h, false, &r.fn, &r.tw_m, &r.tw_x, &r.twc_m, &r.twc_x)) return rc;
+
+    static_assert(kGroupFinishMaxBatch == kSumFinishMaxBatch, "one batch loop");
+    for (int64_t b0 = 0; b0 < nsub; b0 += kGroupFinishMaxBatch) {
+        const int nb = (int)std::min<int64_t>(kGroupFinishMaxBatch, nsub - b0);
+        if (stages & 1) {
+            a.out = (cx<float>*)t_work + b0 * a.out_bs;
+            a.mask = mask0 ? (const float*)mask0 + b0 * mask0_bs : nullptr;
+            for (int b = 0; b < nb; b++) {
+                const Window w = window_of(*h, sub_off0s[b0 + b]);
+                a.lda[b] = w.rot;
+                a.ldc[b] = w.base;
+                a.st_a[b] = subgrid_in_padded_subgrid(*h, xA, sub_off0s[b0 + b]).a;
+            }
+            if (int rc = launch_status(launch_group_finish(h->log_m, h->log_xM, a, nb, ngroups, (hipStream_t)stream), "group_finish",
+                                       "no instance"))
+                return rc;
+        }
+        if (stages & 2) {
+            r.in = (const cx<float>*)t_work + b0 * r.in_bs;
+            r.out = (cx<float>*)out + b0 * r.out_bs;
+            r.mask = mask1 ? (const float*)mask1 + b0 * mask1_bs : nullptr;
+            for (int b = 0; b < nb; b++) r.st_a[b] = subgrid_in_padded_subgrid(*h, xA, sub_off1s[b0 + b]).a;
+            if (int rc = launch_status(launch_sum_finish_facets(h->log_m, h->log_xM, r, nb, (hipStream_t)stream))) return rc;
+        }
+    }
+    return 0;
+}
 
 int swiftly_hip_accumulate_facet_columns(swiftly_hip_t* h, int dtype, const void* parts, int64_t part_row_stride,
                                          int64_t nchunks, const int64_t* chunk_offsets,

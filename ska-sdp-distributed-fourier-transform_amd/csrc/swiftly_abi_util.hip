@@ -73,6 +73,7 @@ int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int
             case SWIFTLY_FEATURE_SPLIT_PREPARE: why = why_not_split_prepare(s, dtype, n_facets); break;
             case SWIFTLY_FEATURE_REAL_FACETS: why = why_not_real_facets(s, dtype); break;
             case SWIFTLY_FEATURE_REAL_FACETS_OUT: why = why_not_real_facets_out(s, dtype); break;
+            case SWIFTLY_FEATURE_GROUP_FINISH: why = why_not_group_finish(s, dtype, n_facets); break;
             default: why = reason("unknown feature %d", feature);
         }
     }

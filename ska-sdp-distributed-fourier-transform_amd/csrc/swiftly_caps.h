@@ -40,8 +40,17 @@ int row_pass_whole_stage_columns();     // physical band columns (both parities)
 // complex128 m-point column pass: m <= 512): the same five pairs, none spills
 #define SPLIT_PAIRS_C128(X) X(7, 8) X(7, 10) X(8, 9) X(8, 10) X(9, 10)
 
+// (m, xM) instances of the column kernel that finishes the strided subgrid axis per facet off1 group (group_finish.hip):
+// the benchmarked pair and the smallest pair of SF_PAIRS
+#define GF_PAIRS(X) X(7, 8) X(9, 10)
+constexpr int kGroupFinishMaxFacets = kSumFinishMaxFacets;  // facet table of swiftly_groupfinish.h
+
 #define SF_HAS(M, XX) \
     if (logm == M && logx == XX) return true;
+inline bool group_finish_supported(int logm, int logx) {
+    GF_PAIRS(SF_HAS)
+    return false;
+}
 inline bool sum_finish_supported(int logm, int logx) {
     SF_PAIRS(SF_HAS)
     return false;
@@ -169,6 +178,17 @@ inline std::string why_not_fused_subgrid(const Sizes& s, int dtype, int64_t n_fa
     if (std::string why = too_many_facets(n_facets); !why.empty()) return why;
     if (s.log_m > kFusedMaxLogM || !sum_finish_supported(s.log_m, s.log_xM))
         return reason("fused subgrid side: no sum_finish instance for m %lld, xM %lld", (long long)s.m, (long long)s.xM);
+    return {};
+}
+// group_finish + sum_finish_facets over the rows of its output (swiftly_hip_wave_group_finish_pieces): the forward subgrid
+// side with the strided axis finished first.  The row kernel takes xM / m entries per off1 group, at most one group per facet
+inline std::string why_not_group_finish(const Sizes& s, int dtype, int64_t n_facets) {
+    if (std::string why = why_not_fused_subgrid(s, dtype, n_facets); !why.empty()) return why;
+    if (!group_finish_supported(s.log_m, s.log_xM))
+        return reason("group finish: no group_finish instance for m %lld, xM %lld", (long long)s.m, (long long)s.xM);
+    if (n_facets * (s.xM / s.m) > kSumFinishMaxFacets)
+        return reason("group finish: %lld facets x %lld row-kernel entries per group exceed %d", (long long)n_facets,
+                      (long long)(s.xM / s.m), kSumFinishMaxFacets);
     return {};
 }
 // split_prepare_facets + wave_split_subgrids

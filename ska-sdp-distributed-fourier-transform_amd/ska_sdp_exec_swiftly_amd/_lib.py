@@ -18,7 +18,7 @@ ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
 # swiftly_hip_supports / swiftly_hip_limit (include/swiftly_hip.h)
 (FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
  FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE, FEATURE_REAL_FACETS,
- FEATURE_REAL_FACETS_OUT) = range(10)
+ FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH) = range(11)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None
@@ -143,6 +143,13 @@ def _declare(lib):
     lib.swiftly_hip_transform_contributions_pieces.argtypes = [
         vp, c_int, i64, POINTER(vp), pi64, POINTER(vp), pi64, pi64, pi64, i64, pi64, i64, pi64, vp, i64, i64, pi64, pi64, vp,
     ]
+    lib.swiftly_hip_wave_group_finish_pieces.restype = c_int
+    lib.swiftly_hip_wave_group_finish_pieces.argtypes = [
+        vp, c_int, i64, POINTER(vp), pi64, POINTER(vp), pi64, pi64, pi64, i64, pi64, pi64, i64, pi64, pi64, i64, vp, i64, vp,
+        i64, vp, i64, vp, c_int, vp,
+    ]
+    lib.swiftly_hip_group_finish.restype = c_int
+    lib.swiftly_hip_group_finish.argtypes = [c_int]
     lib.swiftly_hip_wave_subgrid_side.restype = c_int
     lib.swiftly_hip_wave_subgrid_side.argtypes = [
         vp, c_int, vp, i64, i64, i64, pi64, pi64, i64, pi64, pi64, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp,

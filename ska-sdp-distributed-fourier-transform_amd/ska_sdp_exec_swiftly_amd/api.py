@@ -35,7 +35,8 @@ from .backward import SwiftlyBackward
 from .config import (FacetConfig, SubgridConfig, SwiftlyConfig, _ChunkConfig, make_full_cover_config,
                      make_full_facet_cover, make_full_subgrid_cover, make_mask_from_slice)
 from .forward import (K1_DESCRIPTION, SwiftlyForward, _colacc_from_columns, _facet_grid, _finish_from_colacc,
-                      _finish_from_columns, _finish_from_G, finish_from_blocks, preferred_wave_axis, sum_and_finish_wave)
+                      _finish_from_columns, _finish_from_G, _finish_from_pieces, finish_from_blocks, group_finish_active,
+                      preferred_wave_axis, sum_and_finish_wave)
 from .ingest import _FacetIngest, _mask_table
 from .tasks import DeviceTask, LRUCache, TaskQueue, _torch, _unwrap
 

@@ -577,6 +577,11 @@ class SwiftlyCoreHip:
         given, for ``n_facets`` facets); complex64: the answer of :py:meth:`supports_fused_subgrid`."""
         return self._supports(_lib.FEATURE_SPLIT_PREPARE, dtype, n_facets)
 
+    def supports_group_finish(self, dtype=None, n_facets=None):
+        """True when the subgrid side with the strided axis finished first (:py:meth:`wave_group_finish_pieces`) exists for
+        these sizes and ``n_facets`` facets, in the float32 column arithmetic it computes in."""
+        return self._supports(_lib.FEATURE_GROUP_FINISH, dtype, n_facets) and self.column_precision == 32
+
     def supports_real_facets(self):
         """True when the forward K1 takes real-valued (float32) facets as they are (``prepare_facet_band`` with a float32
         tensor; ``swiftly_hip_prepare_facet_band_real``): the complex64 band pipeline with a power-of-two ``yN_size``.  After a
@@ -783,6 +788,36 @@ class SwiftlyCoreHip:
             )
         )
         return g_out
+
+    def wave_group_finish_pieces(self, pieces, facet_off0s, facet_off1s, sub_off0s, sub_off1s, subgrid_size, mask0, mask1,
+                                 out, t_work=None, stages=3):
+        """The subgrid side of a wave with the strided axis finished first (``swiftly_hip_wave_group_finish_pieces``):
+        ``pieces`` as in :py:meth:`transform_contributions_pieces` -> per facet off1 group ``T[G, S, xM, m]`` (rows below
+        ``subgrid_size`` used; returned when ``stages == 1``) -> ``out[S, xA, xA]``.  ``stages``: 1 = the column kernel
+        only, 2 = the row kernel only (on the caller's ``t_work``), 3 = both."""
+        torch = _torch()
+        n = len(pieces)
+        F, S = pieces[0][0].shape[0], len(sub_off0s)
+        m, xM = self.xM_yN_size, self.xM_size
+        groups = len({int(o) for o in facet_off1s})
+        if t_work is None:
+            t_work = self.scratch("group_finish", groups * S * xM * m * 8).view(torch.complex64)
+        cvp = ctypes.c_void_p
+        qs = (cvp * n)(*[pc[0].data_ptr() for pc in pieces])
+        maps = (cvp * n)(*[pc[1].data_ptr() if pc[1] is not None else None for pc in pieces])
+        _lib.check(
+            self._lib.swiftly_hip_wave_group_finish_pieces(
+                self._handle, self._code(pieces[0][0]), n, qs, self._i64([pc[0].stride(0) for pc in pieces]), maps,
+                self._i64([pc[2] for pc in pieces]), self._i64([pc[3] for pc in pieces]),
+                self._i64([pc[4] for pc in pieces]), F, self._i64(facet_off0s), self._i64(facet_off1s), S,
+                self._i64(sub_off0s), self._i64(sub_off1s), int(subgrid_size),
+                cvp(mask0.data_ptr()) if mask0 is not None else None, mask0.stride(0) if mask0 is not None else 0,
+                cvp(mask1.data_ptr()) if mask1 is not None else None, mask1.stride(0) if mask1 is not None else 0,
+                cvp(t_work.data_ptr()), t_work.numel(), cvp(out.data_ptr()) if out is not None else None, int(stages),
+                self._stream(),
+            )
+        )
+        return t_work[: groups * S * xM * m].view(groups, S, xM, m) if stages == 1 else out
 
     def transform_contributions(self, src, layout, facet_off0s, subgrid_offs, out=None, rowmap=None, band=None, nsub=None):
         """K3 + K4a: ``out[f, b] = Fn * cfft_m(contribution_{f,b}, axis 0)`` rotated by the facet's ``off0``

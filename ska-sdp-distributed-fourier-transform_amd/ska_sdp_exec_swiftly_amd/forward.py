@@ -667,10 +667,10 @@ class SwiftlyForward(WavePrefetch):
             self.core.prepare_facet_columns_range(self.BF_Fs_persist, off0s, self._band, plan.off1(j), first, count, Q, rowmap)
         return len(plan.ranges[j])
 
-    def _facet_side_slabs(self, sgs, g_out, g_layout):
-        """:py:meth:`_facet_side` with K2 per slab: the wave's one or two slabs are taken from the cache or the prefetch
-        (a missing one is computed on the current stream), the slabs of the next predicted waves go to the side stream,
-        and K3 + K4a read the window from the two pieces."""
+    def _slab_pieces(self, sgs):
+        """K2 per slab: the window of the wave as the pieces of ``core.transform_contributions_pieces``.  The wave's one or
+        two slabs are taken from the cache or the prefetch (a missing one is computed on the current stream), the slabs of
+        the next predicted waves go to the side stream."""
         core, off1 = self.core, sgs[0].off1
         if int(off1) not in self._planned_keys:
             raise ValueError(f"subgrid wave off1={off1} was not in the subgrid_configs plan")
@@ -690,6 +690,13 @@ class SwiftlyForward(WavePrefetch):
             self._slab_served.setdefault(j, set()).add(int(off1))
             pieces.append((*hit, first, count))
         self._prefetch_slabs_of(nxt)  # (behind this wave's own K2, if it had to run, and before its K3)
+        return pieces
+
+    def _facet_side_slabs(self, sgs, g_out, g_layout):
+        """:py:meth:`_facet_side` with K2 per slab (:py:meth:`_slab_pieces`): K3 + K4a read the window from the two pieces."""
+        core = self.core
+        pieces = self._slab_pieces(sgs)
+        torch = _torch()
         if g_out is None:
             m = core.xM_yN_size
             g_out = torch.empty((len(self.facet_configs), len(sgs), m, m), dtype=self.dtype, device=core.device)
@@ -727,11 +734,25 @@ class SwiftlyForward(WavePrefetch):
             self._prefetch_waves(nxt)
         return g_out
 
+    def _wave_pieces(self, sgs):
+        """K2 of one wave, and of the next predicted ones on the side stream, without K3: the wave's window as the pieces of
+        ``core.wave_group_finish_pieces`` (the two slabs, or the wave's own ``Q``)."""
+        off1 = sgs[0].off1
+        self.prepare_all_facets()
+        if self._slabs_on():
+            return self._slab_pieces(sgs)
+        Q, rowmap = self._get_wave_columns(off1)
+        self._prefetch_waves(self._predict_next_waves(off1, _knobs()._PREFETCH_DEPTH))
+        return [(Q, rowmap, Q.shape[1], 0, self.core.xM_yN_size)]
+
     def _wave_b(self, sgs):
-        """One wave = two native calls: facet side (K2 + K3 + K4a, _facet_side) and subgrid side (K4b + K5).  (r3's grouped
-        subgrid side -- axis 0 finished first per off1 group, 79 -> 49 MB per subgrid at the same speed -- lives in
-        tools/experiments/ since r4.)"""
+        """One wave = two native calls.  Where the grouped subgrid side exists (:py:func:`group_finish_active`): K2
+        (:py:meth:`_wave_pieces`), then group_finish + sum_finish_facets from its pieces -- the strided axis finished first
+        per facet off1 group, 49 instead of 79 MB per subgrid.  Else facet side (K2 + K3 + K4a, _facet_side) and subgrid
+        side (K4b + K5)."""
         self._check_planned(sgs)
+        if group_finish_active(self.core, self.dtype, len(self.facet_configs), self._placed()):
+            return _finish_from_pieces(self.core, self._wave_pieces(sgs), self.facet_configs, sgs)
         return _finish_from_G(self.core, self._facet_side(sgs), self.facet_configs, sgs, placed=self._placed())
 
 
@@ -760,8 +781,35 @@ def _finish_from_columns(core, src, layout, facet_configs, sgs, window_offs, row
         raise NotImplementedError("fused subgrid path is complex64 only")
     off0s = [cfg.off0 for cfg in facet_configs]
     off1s = [cfg.off1 for cfg in facet_configs]
+    # (the row-window layout owns K3 and the finish: the same kernels, hence the same bits, as SwiftlyForward._wave_b)
+    if layout == 1 and group_finish_active(core, dt, len(facet_configs), placed):
+        return _finish_from_pieces(core, [(src, rowmap, src.shape[1], 0, core.xM_yN_size)], facet_configs, sgs)
     G = core.transform_contributions(src, layout, off0s, window_offs, rowmap=rowmap, band=band)
     return _finish_from_G(core, G, facet_configs, sgs, placed=placed)
+
+
+def group_finish_active(core, dtype, n_facets, placed=False):
+    """Does a path that owns both K3 and the finish of a wave (``SwiftlyForward._wave_b``, its staged twin,
+    ``_finish_from_columns`` on the row-window layout) run the grouped subgrid side?  One rule for all of them, so that their
+    results stay bit-identical to each other: complex64 blocks of the default order, an instance for the sizes
+    (``core.supports_group_finish``), and the process-wide switch (``swiftly_hip_group_finish``, SWIFTLY_GROUP_FINISH=0)
+    on.  Paths that hand ``G[F, S, m, m]`` to someone else (wave_blocks, finish_from_blocks, the multi-GPU classes) keep K3 +
+    wave_subgrid_side."""
+    if placed or dtype != _torch().complex64 or not _lib.load().swiftly_hip_group_finish(-1):
+        return False
+    return core.supports_group_finish(dtype, n_facets)
+
+
+def _finish_from_pieces(core, pieces, facet_configs, sgs):
+    """group_finish + sum_finish_facets of one wave from the pieces of its K2 window (``core.wave_group_finish_pieces``)"""
+    torch = _torch()
+    xA, S = sgs[0].size, len(sgs)
+    dt = pieces[0][0].dtype
+    mask1 = _mask_table(core, sgs, "mask1", xA, dt)
+    mask0 = _mask_table(core, sgs, "mask0", xA, dt)
+    res = torch.empty((S, xA, xA), dtype=dt, device=core.device)
+    return core.wave_group_finish_pieces(pieces, [cfg.off0 for cfg in facet_configs], [cfg.off1 for cfg in facet_configs],
+                                         [sg.off0 for sg in sgs], [sg.off1 for sg in sgs], xA, mask0, mask1, res)
 
 
 def _finish_from_G(core, G, facet_configs, sgs, placed=False):

@@ -27,6 +27,9 @@ STAGES = [
     (r"col_pass_kernel.*CGeoILi[5-9]E.*EELi1ELb", "K2b"),   # four-step pass B
     (r"col_pass_kernel.*CGeoILi9E.*EELi2ELb", "K3"),        # transform_contributions (512-point single pass)
     (r"col_pass2_kernel.*CGeoILi9E", "K3"),                 # ... of a window in two column slabs (two-source load)
+    # the grouped subgrid side (swiftly_groupfinish.h) takes the place of K3 -- and of K5b, which then has no launches; the
+    # K4b5a line is then sum_finish_facets over the rows of its output
+    (r"group_finish_kernel", "K3"),
     (r"sum_finish_facets_kernel", "K4b5a"),
     (r"col_pass_kernel.*CGeoILi10E.*EELi2ELb", "K5b"),      # axis-0 finish (1024-point single pass)
 ]
