@@ -474,7 +474,9 @@ int swiftly_hip_sum_finish_facets(swiftly_hip_t* h, int dtype, const void* in, i
                                   const int64_t* subgrid_off1s, int64_t subgrid_size, const void* mask,
                                   int64_t mask_batch_stride, int64_t nsub, void* stream);
 
-/* One forward wave as TWO native calls (per-wave host work = two ABI calls; what the streaming classes use):
+/* One forward wave as TWO native calls (per-wave host work = two ABI calls), for native callers.  The streaming classes
+ * call K2 (prepare_facet_columns_waves / _range) and transform_contributions_pieces / wave_group_finish_pieces separately;
+ * wave_facet_side is the same launch sequence as K2 followed by transform_contributions_pieces on one whole-window piece.
  *
  * wave_facet_side: K2 (prepare_facet_columns into the workspace q_work[nfacets][n_rows][m], facet stride
  *   q_facet_stride elements; skipped when compute_q == 0 and q_work still holds the wave's result -- e.g. a slice

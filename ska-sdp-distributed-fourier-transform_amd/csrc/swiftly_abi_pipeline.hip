@@ -470,6 +470,14 @@ static int check_window_pieces(const swiftly_hip_t* h, const char* who, int64_t 
     return 0;
 }
 
+// Who holds what of a checked window: piece *a the positions [split, m) -- or the whole window --, piece *b the positions
+// [0, split), -1 where the window lies in one piece
+static void window_piece_roles(int64_t m, int64_t npieces, const int64_t* first, const int64_t* count, int* a, int* b) {
+    *a = *b = -1;
+    for (int64_t i = 0; i < npieces; i++)
+        if (count[i]) *(first[i] == 0 && count[i] < m ? b : a) = (int)i;
+}
+
 // SWIFTLY_K3_ONE_LAUNCH=0: K3 of a window in two pieces as one launch sequence per piece (A/B runs; swiftly_hip_k3_one_launch)
 static std::atomic<int> g_k3_one_launch{getenv("SWIFTLY_K3_ONE_LAUNCH") ? atoi(getenv("SWIFTLY_K3_ONE_LAUNCH")) != 0 : 1};
 // SWIFTLY_GROUP_FINISH=0: the callers that own K3 and the finish keep K3 + wave_subgrid_side (A/B runs; swiftly_hip_group_finish)
@@ -512,8 +520,9 @@ int swiftly_hip_transform_contributions_pieces(swiftly_hip_t* h, int dtype, int6
     if (int rc = check_window_pieces(h, "transform_contributions_pieces", npieces, q, q_facet_strides, n_rows, first, count)) return rc;
     DeviceGuard device_guard_(h->device);
     const int64_t m = h->m;
-    if (npieces == 2 && count[0] && count[1] && g_k3_one_launch.load()) {
-        const int b = first[0] == 0 ? 0 : 1, a = 1 - b;  // piece b holds [0, split), piece a [split, m)
+    int a, b;
+    window_piece_roles(m, npieces, first, count, &a, &b);
+    if (b >= 0 && g_k3_one_launch.load()) {
         const SecondSource second = {q[b], q_facet_strides[b], rowmaps[b], count[b]};
         const int rc = transform_contributions_impl(h, dtype, q[a], 1, m, q_facet_strides[a], 0, rowmaps[a], 0, 0, nfacets,
                                                     facet_off0s, nsub, sub_off0s, g_out, g_facet_stride, g_sub_stride,
@@ -859,12 +868,8 @@ int swiftly_hip_wave_group_finish_pieces(swiftly_hip_t* h, int dtype, int64_t np
         a.sp0[n] = (int)facet_shift(*h, facet_off0s[r.fidx[n]]);
     }
     for (int g = 0; g <= ngroups; g++) a.gstart[g] = r.gstart[g];
-    // piece B holds the window positions [0, split), piece A the others; one piece: A
-    int pa = -1, pb = -1;
-    for (int64_t i = 0; i < npieces; i++) {
-        if (!count[i]) continue;
-        if (first[i] == 0 && count[i] < m) pb = (int)i; else pa = (int)i;
-    }
+    int pa, pb;
+    window_piece_roles(m, npieces, first, count, &pa, &pb);
     a.in_a = (const cx<float>*)q[pa]; a.in_fs_a = q_facet_strides[pa]; a.rowmap_a = rowmaps[pa];
     if (pb >= 0) {
         a.in_b = (const cx<float>*)q[pb]; a.in_fs_b = q_facet_strides[pb]; a.rowmap_b = rowmaps[pb];

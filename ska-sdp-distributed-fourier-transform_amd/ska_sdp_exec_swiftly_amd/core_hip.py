@@ -766,25 +766,33 @@ class SwiftlyCoreHip:
         self.k2_columns_issued += int(ncols)
         return out
 
+    def _pieces_args(self, pieces):
+        """the leading arguments the ``*_pieces`` entry points share: dtype code, number of pieces, then per piece the ``Q``
+        pointer, its facet stride, the row map pointer, the kept rows, the first window position and the number of positions"""
+        n = len(pieces)
+        cvp = ctypes.c_void_p
+        return (
+            self._code(pieces[0][0]), n, (cvp * n)(*[pc[0].data_ptr() for pc in pieces]),
+            self._i64([pc[0].stride(0) for pc in pieces]),
+            (cvp * n)(*[pc[1].data_ptr() if pc[1] is not None else None for pc in pieces]),
+            self._i64([pc[2] for pc in pieces]), self._i64([pc[3] for pc in pieces]), self._i64([pc[4] for pc in pieces]),
+        )
+
+    def _g_placement(self, g_out, g_layout):
+        """``(facet stride, subgrid stride, offsets, facet strides)`` of the blocks of a wave in ``g_out``: a ``[F, S, m, m]``
+        tensor, or a flat buffer with ``g_layout = (offsets[S], facet_strides[S])``"""
+        if g_layout is None:
+            return g_out.stride(0), g_out.stride(1), None, None
+        return 0, 0, self._i64(g_layout[0]), self._i64(g_layout[1])
+
     def transform_contributions_pieces(self, pieces, facet_off0s, sub_off0s, g_out, g_layout=None):
         """K3 + K4a of a wave whose window lies in up to two ``Q`` buffers (``swiftly_hip_transform_contributions_pieces``):
         ``pieces = [(Q[F, n_rows, m], rowmap, n_rows, first position, number of positions)]``, together the whole window;
-        output as :py:meth:`wave_facet_side` -- ``g_out[F, S, m, m]``, or a flat buffer with ``g_layout``."""
-        n = len(pieces)
-        F, S = pieces[0][0].shape[0], len(sub_off0s)
-        cvp = ctypes.c_void_p
-        qs = (cvp * n)(*[pc[0].data_ptr() for pc in pieces])
-        maps = (cvp * n)(*[pc[1].data_ptr() if pc[1] is not None else None for pc in pieces])
-        if g_layout is None:
-            fs, ss, offs, fstr = g_out.stride(0), g_out.stride(1), None, None
-        else:
-            fs, ss, offs, fstr = 0, 0, self._i64(g_layout[0]), self._i64(g_layout[1])
+        the blocks are written into ``g_out`` as :py:meth:`_g_placement` says."""
         _lib.check(
             self._lib.swiftly_hip_transform_contributions_pieces(
-                self._handle, self._code(pieces[0][0]), n, qs, self._i64([pc[0].stride(0) for pc in pieces]), maps,
-                self._i64([pc[2] for pc in pieces]), self._i64([pc[3] for pc in pieces]),
-                self._i64([pc[4] for pc in pieces]), F, self._i64(facet_off0s), S, self._i64(sub_off0s),
-                cvp(g_out.data_ptr()), fs, ss, offs, fstr, self._stream(),
+                self._handle, *self._pieces_args(pieces), pieces[0][0].shape[0], self._i64(facet_off0s), len(sub_off0s),
+                self._i64(sub_off0s), ctypes.c_void_p(g_out.data_ptr()), *self._g_placement(g_out, g_layout), self._stream(),
             )
         )
         return g_out
@@ -796,20 +804,15 @@ class SwiftlyCoreHip:
         ``subgrid_size`` used; returned when ``stages == 1``) -> ``out[S, xA, xA]``.  ``stages``: 1 = the column kernel
         only, 2 = the row kernel only (on the caller's ``t_work``), 3 = both."""
         torch = _torch()
-        n = len(pieces)
         F, S = pieces[0][0].shape[0], len(sub_off0s)
         m, xM = self.xM_yN_size, self.xM_size
         groups = len({int(o) for o in facet_off1s})
         if t_work is None:
             t_work = self.scratch("group_finish", groups * S * xM * m * 8).view(torch.complex64)
         cvp = ctypes.c_void_p
-        qs = (cvp * n)(*[pc[0].data_ptr() for pc in pieces])
-        maps = (cvp * n)(*[pc[1].data_ptr() if pc[1] is not None else None for pc in pieces])
         _lib.check(
             self._lib.swiftly_hip_wave_group_finish_pieces(
-                self._handle, self._code(pieces[0][0]), n, qs, self._i64([pc[0].stride(0) for pc in pieces]), maps,
-                self._i64([pc[2] for pc in pieces]), self._i64([pc[3] for pc in pieces]),
-                self._i64([pc[4] for pc in pieces]), F, self._i64(facet_off0s), self._i64(facet_off1s), S,
+                self._handle, *self._pieces_args(pieces), F, self._i64(facet_off0s), self._i64(facet_off1s), S,
                 self._i64(sub_off0s), self._i64(sub_off1s), int(subgrid_size),
                 cvp(mask0.data_ptr()) if mask0 is not None else None, mask0.stride(0) if mask0 is not None else 0,
                 cvp(mask1.data_ptr()) if mask1 is not None else None, mask1.stride(0) if mask1 is not None else 0,
@@ -885,32 +888,6 @@ class SwiftlyCoreHip:
             buf = pool[key] = torch.empty((nbytes,), dtype=torch.uint8, device=self._device)
         return buf
 
-    def wave_facet_side(self, bands, facet_off0s, band, wave_off1, rowmap, n_rows, Q, compute_q, sub_off0s, g_out,
-                        g_layout=None):
-        """K2 + K3 + K4a of one wave natively (``swiftly_hip_wave_facet_side``): ``bands[F, yB, band columns]`` ->
-        workspace ``Q[F, n_rows, m]`` (computed when ``compute_q``) -> blocks written into ``g_out``: a
-        ``[F, S, m, m]`` tensor, or a flat send buffer with ``g_layout = (offsets[S], facet_strides[S])``."""
-        F, S = Q.shape[0], len(sub_off0s)
-        cvp = ctypes.c_void_p
-        scr = self.scratch("k2", self._k2_scratch_bytes(F, Q.element_size())) if compute_q else None
-        if g_layout is None:
-            fs, ss, offs, fstr = g_out.stride(0), g_out.stride(1), None, None
-        else:
-            fs, ss, offs, fstr = 0, 0, self._i64(g_layout[0]), self._i64(g_layout[1])
-        _lib.check(
-            self._lib.swiftly_hip_wave_facet_side(
-                self._handle, self._code(Q), cvp(bands.data_ptr()) if bands is not None else None,
-                int(bands.shape[1]) if bands is not None else 0, bands.stride(1) if bands is not None else 0,
-                bands.stride(0) if bands is not None else 0, F, self._i64(facet_off0s), int(band[0]), int(band[1]),
-                int(wave_off1), cvp(rowmap.data_ptr()) if rowmap is not None else None, int(n_rows),
-                cvp(Q.data_ptr()), Q.stride(0), int(bool(compute_q)), S, self._i64(sub_off0s), cvp(g_out.data_ptr()), fs,
-                ss, offs, fstr, cvp(scr.data_ptr()) if scr is not None else None, scr.numel() if scr is not None else 0,
-                self._stream(),
-            )
-        )
-        if compute_q:
-            self.k2_columns_issued += self.xM_yN_size
-
     def chain_chunk_streams(self, chain):
         """``swiftly_hip_chain_chunk_streams`` for the calling thread: the next chunked strided-axis transforms skip the
         fork of their two internal streams (the caller vouches that their inputs were complete before an earlier,
@@ -979,7 +956,7 @@ class SwiftlyCoreHip:
         """Step R of the axis-1-first pipeline (``swiftly_hip_finish_axis1_rows``): the contiguous-axis half of
         ``add_to_subgrid`` (reference core.py:255-285) on every row of the K1 band buffers ``bands[F, yB, band columns]``
         for the wave ``wave_off1``, BEFORE the strided-axis transforms.  Returns ``(W[F, yB, m], window band)``: hand both
-        to ``prepare_facet_columns`` / ``wave_facet_side`` in place of the band buffers and their band."""
+        to ``prepare_facet_columns`` in place of the band buffers and their band."""
         torch = _torch()
         F, rows = bands.shape[0], bands.shape[1]
         m, yN = self.xM_yN_size, self.yN_size

@@ -355,7 +355,7 @@ class SwiftlyForward(WavePrefetch):
         if self.wave_axis != 0:
             raise ValueError(
                 "wave_contributions belongs to the reference schedule (wave_axis=0); with wave_axis=1 use "
-                "distributed.DistributedForward.pack_wave / core.wave_facet_side"
+                "distributed.DistributedForward.pack_wave / wave_blocks_into"
             )
         torch = _torch()
         core = self.core
@@ -564,22 +564,17 @@ class SwiftlyForward(WavePrefetch):
             return bands[:, w], (start, m)
         return self.core.finish_axis1_rows(bands, [cfg.off1 for cfg in self.facet_configs], self._band, off1)
 
-    def _lookup_Q(self, off1):
-        """What the two forms of K2 share: a prefetched ``Q`` of wave ``off1`` is taken over, a cached one answers ``((Q,
-        rowmap), rowmap, n_rows)``; otherwise the wave is checked against the plan: ``(None, rowmap, n_rows)`` of its rows."""
+    def _get_wave_columns(self, off1):
+        """K2: ``(Q[F, rows, m], rowmap)`` for the subgrid wave ``off1`` (LRU cached like the reference's per-off0 columns).  A
+        prefetched ``Q`` is taken over; one that has to be computed is checked against the plan first and enters the cache
+        after its K2 has been enqueued."""
         self._take_prefetched(off1)
         hit = self.lru.get(("b", off1))
-        if hit is not None:
-            return hit, hit[1], hit[0].shape[1]
-        if self._plan is not None and int(off1) not in self._planned_keys:
-            raise ValueError(f"subgrid wave off1={off1} was not in the subgrid_configs plan")
-        self.prepare_all_facets()
-        return (None, *self._wave_rows(off1))
-
-    def _get_wave_columns(self, off1):
-        """K2: ``Q[F, rows, m]`` for the subgrid wave ``off1`` (LRU cached like the reference's per-off0 columns)."""
-        hit, rowmap, n_rows = self._lookup_Q(off1)
         if hit is None:
+            if self._plan is not None and int(off1) not in self._planned_keys:
+                raise ValueError(f"subgrid wave off1={off1} was not in the subgrid_configs plan")
+            self.prepare_all_facets()
+            rowmap, n_rows = self._wave_rows(off1)
             bands, band = self._k2_source(off1)
             Q = self.core.prepare_facet_columns(
                 bands, [cfg.off0 for cfg in self.facet_configs], band, off1, rowmap, n_rows
@@ -593,21 +588,12 @@ class SwiftlyForward(WavePrefetch):
             raise ValueError("subgrid was not in the subgrid_configs plan")
 
     def _wave_b_staged(self, sgs):
-        """stage-by-stage form (one ABI call per kernel group; used when the stages are timed separately)"""
+        """:py:meth:`_wave_b` with K2 always per wave (never per slab) and without the prefetch: what the stage timers of
+        ``get_wave`` bracket"""
         Q, rowmap = self._get_wave_columns(sgs[0].off1)
         self._check_planned(sgs)
-        return _finish_from_columns(self.core, Q, 1, self.facet_configs, sgs, [sg.off0 for sg in sgs], rowmap=rowmap,
-                                    placed=self._placed())
-
-    def _wave_Q(self, off1):
-        """(Q workspace, rowmap, n_rows, needs computing) of wave ``off1``: registered here, computed by the facet-side call"""
-        hit, rowmap, n_rows = self._lookup_Q(off1)
-        if hit is not None:
-            return hit[0], rowmap, n_rows, False
-        core = self.core
-        Q = _torch().empty((len(self.facet_configs), n_rows, core.xM_yN_size), dtype=self.dtype, device=core.device)
-        self.lru.set(("b", off1), (Q, rowmap))
-        return Q, rowmap, n_rows, True
+        return _finish_window(self.core, [(Q, rowmap, Q.shape[1], 0, self.core.xM_yN_size)], self.facet_configs, sgs,
+                              placed=self._placed())
 
     # -- K2 once per column slab of the padded axis instead of once per wave (slabs.py; DESIGN.md sections 3 and 4) --
     @cached_property
@@ -692,51 +678,12 @@ class SwiftlyForward(WavePrefetch):
         self._prefetch_slabs_of(nxt)  # (behind this wave's own K2, if it had to run, and before its K3)
         return pieces
 
-    def _facet_side_slabs(self, sgs, g_out, g_layout):
-        """:py:meth:`_facet_side` with K2 per slab (:py:meth:`_slab_pieces`): K3 + K4a read the window from the two pieces."""
-        core = self.core
-        pieces = self._slab_pieces(sgs)
-        torch = _torch()
-        if g_out is None:
-            m = core.xM_yN_size
-            g_out = torch.empty((len(self.facet_configs), len(sgs), m, m), dtype=self.dtype, device=core.device)
-        core.transform_contributions_pieces(pieces, [cfg.off0 for cfg in self.facet_configs], [sg.off0 for sg in sgs], g_out,
-                                            g_layout=g_layout)
-        return g_out
-
-    def _facet_side(self, sgs, g_out=None, g_layout=None):
-        """Facet side of one wave (K2 + K3 + K4a) in one native call: the blocks ``G[F, S, m, m]`` (returned), or placed by
-        ``g_layout`` inside the flat buffer ``g_out`` (wave_blocks_into).  K2 of the next waves of the announced order
-        (set_wave_order; the plan's own order otherwise) goes to the side stream before this wave's K3 (_prefetch_wave), for
-        both callers (r6: the multi-GPU pass used to compute every K2 on the caller's stream, 41.4 against 35.5 ms at world 1)."""
-        core, off1 = self.core, sgs[0].off1
-        bands = self.prepare_all_facets()
-        if self._slabs_on():
-            return self._facet_side_slabs(sgs, g_out, g_layout)
-        Q, rowmap, n_rows, compute = self._wave_Q(off1)
-        nxt = self._predict_next_waves(off1, _knobs()._PREFETCH_DEPTH)
-        if not compute:
-            self._prefetch_waves(nxt)
-        if g_out is None:
-            m = core.xM_yN_size
-            g_out = _torch().empty((len(self.facet_configs), len(sgs), m, m), dtype=self.dtype, device=core.device)
-        band = self._band
-        if compute:
-            bands, band = self._k2_source(off1)
-        try:
-            core.wave_facet_side(bands, [cfg.off0 for cfg in self.facet_configs], band, off1, rowmap, n_rows, Q, compute,
-                                 [sg.off0 for sg in sgs], g_out, g_layout=g_layout)
-        except Exception:
-            if compute:  # Q was registered before it was computed: a later request must not find garbage
-                self.lru.discard(("b", off1))
-            raise
-        if compute:  # (this wave's own K2 was enqueued on the current stream just now: the next one goes behind it)
-            self._prefetch_waves(nxt)
-        return g_out
-
     def _wave_pieces(self, sgs):
-        """K2 of one wave, and of the next predicted ones on the side stream, without K3: the wave's window as the pieces of
-        ``core.wave_group_finish_pieces`` (the two slabs, or the wave's own ``Q``)."""
+        """K2 of one wave without K3 -- the one place a wave's window comes from: the pieces of
+        ``core.transform_contributions_pieces`` / ``core.wave_group_finish_pieces`` (the two slabs, or the wave's own ``Q``).
+        K2 of the next waves of the announced order (set_wave_order; the plan's own order otherwise) goes to the side stream
+        behind this wave's K2 and before its K3 (_prefetch_wave), for every caller (r6: the multi-GPU pass used to compute
+        every K2 on the caller's stream, 41.4 against 35.5 ms at world 1)."""
         off1 = sgs[0].off1
         self.prepare_all_facets()
         if self._slabs_on():
@@ -745,15 +692,21 @@ class SwiftlyForward(WavePrefetch):
         self._prefetch_waves(self._predict_next_waves(off1, _knobs()._PREFETCH_DEPTH))
         return [(Q, rowmap, Q.shape[1], 0, self.core.xM_yN_size)]
 
+    def _facet_side(self, sgs, g_out=None, g_layout=None):
+        """Facet side of one wave: K2 (:py:meth:`_wave_pieces`), then K3 + K4a from its pieces into the blocks
+        ``G[F, S, m, m]`` (returned), or placed by ``g_layout`` inside the flat buffer ``g_out`` (wave_blocks_into)."""
+        core = self.core
+        pieces = self._wave_pieces(sgs)
+        if g_out is None:
+            m = core.xM_yN_size
+            g_out = _torch().empty((len(self.facet_configs), len(sgs), m, m), dtype=self.dtype, device=core.device)
+        return core.transform_contributions_pieces(pieces, [cfg.off0 for cfg in self.facet_configs], [sg.off0 for sg in sgs],
+                                                   g_out, g_layout=g_layout)
+
     def _wave_b(self, sgs):
-        """One wave = two native calls.  Where the grouped subgrid side exists (:py:func:`group_finish_active`): K2
-        (:py:meth:`_wave_pieces`), then group_finish + sum_finish_facets from its pieces -- the strided axis finished first
-        per facet off1 group, 49 instead of 79 MB per subgrid.  Else facet side (K2 + K3 + K4a, _facet_side) and subgrid
-        side (K4b + K5)."""
+        """One wave: K2 (:py:meth:`_wave_pieces`), then the subgrid side from its pieces (:py:func:`_finish_window`)."""
         self._check_planned(sgs)
-        if group_finish_active(self.core, self.dtype, len(self.facet_configs), self._placed()):
-            return _finish_from_pieces(self.core, self._wave_pieces(sgs), self.facet_configs, sgs)
-        return _finish_from_G(self.core, self._facet_side(sgs), self.facet_configs, sgs, placed=self._placed())
+        return _finish_window(self.core, self._wave_pieces(sgs), self.facet_configs, sgs, placed=self._placed())
 
 
 class _PromotingForward(SwiftlyForward):
@@ -773,31 +726,38 @@ def axis1_first_active(core, wave_axis, dtype):
 def _finish_from_columns(core, src, layout, facet_configs, sgs, window_offs, rowmap=None, band=None, placed=False):
     """K3..K5 without any HBM accumulator: per-(facet, subgrid) axis-0 transforms gathered straight from the
     wave's facet buffers (``src``), facet sum + axis-1 finish on chip, axis-0 finish."""
-    torch = _torch()
-    xM, xA, S = core.xM_size, sgs[0].size, len(sgs)
-    dt, dev = src.dtype, core.device
-    # (complex128: the row-window layout of the band pipeline only; the column-buffer layout 0 stays complex64)
-    if dt != torch.complex64 and not (dt == torch.complex128 and layout == 1):
+    if layout == 1:  # the row-window layout: ``src`` is the wave's whole window, served as every wave of the band pipeline is
+        return _finish_window(core, [(src, rowmap, src.shape[1], 0, core.xM_yN_size)], facet_configs, sgs, placed=placed)
+    if src.dtype != _torch().complex64:  # (the column-buffer layout 0 stays complex64)
         raise NotImplementedError("fused subgrid path is complex64 only")
-    off0s = [cfg.off0 for cfg in facet_configs]
-    off1s = [cfg.off1 for cfg in facet_configs]
-    # (the row-window layout owns K3 and the finish: the same kernels, hence the same bits, as SwiftlyForward._wave_b)
-    if layout == 1 and group_finish_active(core, dt, len(facet_configs), placed):
-        return _finish_from_pieces(core, [(src, rowmap, src.shape[1], 0, core.xM_yN_size)], facet_configs, sgs)
-    G = core.transform_contributions(src, layout, off0s, window_offs, rowmap=rowmap, band=band)
+    G = core.transform_contributions(src, layout, [cfg.off0 for cfg in facet_configs], window_offs, rowmap=rowmap, band=band)
     return _finish_from_G(core, G, facet_configs, sgs, placed=placed)
 
 
 def group_finish_active(core, dtype, n_facets, placed=False):
-    """Does a path that owns both K3 and the finish of a wave (``SwiftlyForward._wave_b``, its staged twin,
-    ``_finish_from_columns`` on the row-window layout) run the grouped subgrid side?  One rule for all of them, so that their
-    results stay bit-identical to each other: complex64 blocks of the default order, an instance for the sizes
-    (``core.supports_group_finish``), and the process-wide switch (``swiftly_hip_group_finish``, SWIFTLY_GROUP_FINISH=0)
-    on.  Paths that hand ``G[F, S, m, m]`` to someone else (wave_blocks, finish_from_blocks, the multi-GPU classes) keep K3 +
-    wave_subgrid_side."""
+    """Does a path that owns both K3 and the finish of a wave run the grouped subgrid side?  Asked by :py:func:`_finish_window`
+    alone, through which all of them go (``SwiftlyForward._wave_b``, its staged twin, ``_finish_from_columns`` on the
+    row-window layout), so that their results stay bit-identical to each other: complex64 blocks of the default order, an
+    instance for the sizes (``core.supports_group_finish``), and the process-wide switch (``swiftly_hip_group_finish``,
+    SWIFTLY_GROUP_FINISH=0) on.  Paths that hand ``G[F, S, m, m]`` to someone else (wave_blocks, finish_from_blocks, the
+    multi-GPU classes) keep K3 + wave_subgrid_side."""
     if placed or dtype != _torch().complex64 or not _lib.load().swiftly_hip_group_finish(-1):
         return False
     return core.supports_group_finish(dtype, n_facets)
+
+
+def _finish_window(core, pieces, facet_configs, sgs, placed=False):
+    """Finished, masked subgrids ``[S, xA, xA]`` of one wave from the pieces of its K2 window (``SwiftlyForward._wave_pieces``).
+    Where the grouped subgrid side exists (:py:func:`group_finish_active`): group_finish + sum_finish_facets from the pieces
+    -- the strided axis finished first per facet off1 group, 49 instead of 79 MB per subgrid.  Else K3 + K4a into
+    ``G[F, S, m, m]`` and the subgrid side K4b + K5 (:py:func:`_finish_from_G`)."""
+    dt = pieces[0][0].dtype
+    if group_finish_active(core, dt, len(facet_configs), placed):
+        return _finish_from_pieces(core, pieces, facet_configs, sgs)
+    m = core.xM_yN_size
+    G = _torch().empty((len(facet_configs), len(sgs), m, m), dtype=dt, device=core.device)
+    core.transform_contributions_pieces(pieces, [cfg.off0 for cfg in facet_configs], [sg.off0 for sg in sgs], G)
+    return _finish_from_G(core, G, facet_configs, sgs, placed=placed)
 
 
 def _finish_from_pieces(core, pieces, facet_configs, sgs):

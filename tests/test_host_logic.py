@@ -342,6 +342,60 @@ def test_planned_wave_prediction_depth():
     assert fwd._predict_next_waves(15, 2) == []          # not a planned wave
 
 
+def test_facet_side_asks_for_k2_then_prefetches_once_then_runs_k3():
+    """SwiftlyForward._facet_side (what wave_blocks_into runs): the wave's own K2 first, the side-stream prefetch exactly
+    once and before K3, whether the wave's Q was cached or had to be computed; a K2 that raises leaves nothing in the
+    cache for a later request to find."""
+    import types
+
+    def forward(k2_raises=False):
+        fwd = _bare_forward((10, 20, 30))
+        fwd.lru = api.LRUCache(2)
+        fwd.wave_axis, fwd.BF_Fs_persist, fwd._bands_own = 1, object(), False  # facets prepared, K2 per wave
+        fwd.facet_configs = [api.FacetConfig(0, 0, 8), api.FacetConfig(64, 0, 8)]
+        fwd.dtype = None
+        log = []
+
+        def k2(off1):
+            hit = fwd.lru.get(("b", off1))
+            log.append(("K2", off1, "cached" if hit is not None else "computed"))
+            if hit is None:
+                if k2_raises:
+                    raise RuntimeError("K2 failed")
+                hit = (numpy.zeros((2, 5, 4)), "rowmap")
+                fwd.lru.set(("b", off1), hit)
+            return hit
+
+        def k3(pieces, facet_off0s, sub_off0s, g_out, g_layout=None):
+            log.append(("K3", pieces, facet_off0s, sub_off0s, g_layout))
+            return g_out
+
+        fwd._get_wave_columns = k2
+        fwd._prefetch_waves = lambda waves: log.append(("prefetch", list(waves)))
+        fwd.core = types.SimpleNamespace(xM_yN_size=4, transform_contributions_pieces=k3)
+        return fwd, log
+
+    sgs = [api.SubgridConfig(7, 10, 8), api.SubgridConfig(9, 10, 8)]
+    for cached in (False, True):
+        fwd, log = forward()
+        if cached:
+            Q = numpy.ones((2, 5, 4))
+            fwd.lru.set(("b", 10), (Q, "rowmap"))
+        flat, layout = object(), ([0, 32], [16, 16])
+        assert fwd._facet_side(sgs, flat, layout) is flat
+        assert [entry[0] for entry in log] == ["K2", "prefetch", "K3"], (cached, log)
+        assert log[0] == ("K2", 10, "cached" if cached else "computed")
+        assert log[1] == ("prefetch", [20, 30][: api._PREFETCH_DEPTH] if api._PREFETCH else [])
+        (piece,), off0s, sub_off0s, g_layout = log[2][1:]
+        assert piece[0] is fwd.lru.get(("b", 10))[0] and piece[1:] == ("rowmap", 5, 0, 4)
+        assert (cached and piece[0] is Q) or not cached
+        assert off0s == [0, 64] and sub_off0s == [7, 9] and g_layout is layout
+    fwd, log = forward(k2_raises=True)
+    with pytest.raises(RuntimeError):
+        fwd._facet_side(sgs, object(), ([0, 32], [16, 16]))
+    assert log == [("K2", 10, "computed")] and not fwd.lru._items
+
+
 def test_wave_predictor_reports_the_miss_that_switches_it_off():
     """WavePredictor on its own, what the tests through SwiftlyForward do not see: only the second miss in a row reports
     the switch-off (one log line), a hit in between starts the count again, and announcing an order leaves the switch alone."""
