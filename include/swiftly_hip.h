@@ -532,6 +532,15 @@ int swiftly_hip_wave_group_finish_pieces(swiftly_hip_t* h, int dtype, int64_t np
  * tests): sets it to on != 0 and returns the previous value; on < 0 only queries.  Initial value 1, or 0 with the
  * environment variable SWIFTLY_GROUP_FINISH=0.  (No reference counterpart: scheduling of this implementation.) */
 int swiftly_hip_group_finish(int on);
+/* How stage 1 (group_finish) walks its tiles -- 16 columns x one subgrid x one facet group each: n = 0 launches one workgroup
+ * per tile; n = 1 launches persistent workgroups, min(tiles, compute units of the handle's device) of them, each walking
+ * the tiles w, w + grid, ... and requesting the next tile's first facet ahead of the inverse transform of the one it
+ * finishes; n > 1 caps that grid at n workgroups (tests: a small problem then makes every workgroup walk many tiles).  The
+ * same bits in every form.  Sets the process-wide value and returns the previous one; n = -1 only queries it; n = -2
+ * returns the grid of the calling thread's last group_finish launch: 0 for the one-workgroup-per-tile kernel, else the
+ * persistent kernel's workgroup count (-1 before the first launch).  Initial value 1, or the environment variable
+ * SWIFTLY_GROUP_FINISH_PERSISTENT, read once.  (No reference counterpart: scheduling of this implementation.) */
+int swiftly_hip_group_finish_persistent(int n);
 
 /* AXIS-1-FIRST forward pipeline (r6; opt-in: the accuracy mode that replaces float64 column passes).  The transforms of
  * the two axes commute (api_helper.py:81-99, 200-210), so the contiguous-axis half of add_to_subgrid (core.py:255-285:

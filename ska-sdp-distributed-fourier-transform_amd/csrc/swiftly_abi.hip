@@ -237,6 +237,10 @@ int swiftly_hip_create(swiftly_hip_t** out, int64_t N, int64_t yN, int64_t xM, d
     static_cast<Sizes&>(*h) = make_sizes(N, yN, xM);
     h->W = W;
     h->device = device;
+    if (hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->cu_count <= 0) {
+        delete h;
+        return fail(SWIFTLY_ERR_HIP, "cannot query the compute unit count of device %d", device);
+    }
     if (const char* e = getenv("SWIFTLY_COL_F64")) h->col_f64 = atoi(e) != 0;
     if (const char* e = getenv("SWIFTLY_COL_F64_STAGES")) h->col_f64_stages = atoi(e) & 7;
     // windows: 1/pswf (Fb, core.py:104-108) and Fn (core.py:110-117)

@@ -82,6 +82,7 @@ struct ScratchLease {
 struct swiftly_hip : Sizes {  // N, yN, xM, m and log_yN, log_xM, log_m (swiftly_caps.h)
     double W;
     int device;
+    int cu_count = 0;  // compute units of `device` (swiftly_hip_create): the grid of the persistent kernels
     float* invp_f = nullptr;    // 1/pswf[k] (k = 0 -> 0)
     double* invp_d = nullptr;
     float* fn_f = nullptr;  // Fn[k], k < m

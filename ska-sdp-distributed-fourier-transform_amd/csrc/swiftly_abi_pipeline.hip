@@ -482,6 +482,11 @@ static void window_piece_roles(int64_t m, int64_t npieces, const int64_t* first,
 static std::atomic<int> g_k3_one_launch{getenv("SWIFTLY_K3_ONE_LAUNCH") ? atoi(getenv("SWIFTLY_K3_ONE_LAUNCH")) != 0 : 1};
 // SWIFTLY_GROUP_FINISH=0: the callers that own K3 and the finish keep K3 + wave_subgrid_side (A/B runs; swiftly_hip_group_finish)
 static std::atomic<int> g_group_finish{getenv("SWIFTLY_GROUP_FINISH") ? atoi(getenv("SWIFTLY_GROUP_FINISH")) != 0 : 1};
+// SWIFTLY_GROUP_FINISH_PERSISTENT: 0 = group_finish on one workgroup per tile, 1 = persistent workgroups, one per compute
+// unit, n > 1 = at most n of them (swiftly_hip_group_finish_persistent); and the grid of the calling thread's last launch
+static std::atomic<int> g_group_finish_persistent{
+    getenv("SWIFTLY_GROUP_FINISH_PERSISTENT") ? std::max(0, atoi(getenv("SWIFTLY_GROUP_FINISH_PERSISTENT"))) : 1};
+static thread_local int t_group_finish_last_grid = -1;
 
 extern "C" {
 int swiftly_hip_k3_one_launch(int on) {
@@ -829,6 +834,11 @@ int swiftly_hip_group_finish(int on) {
     return on < 0 ? g_group_finish.load() : g_group_finish.exchange(on ? 1 : 0);
 }
 
+int swiftly_hip_group_finish_persistent(int n) {
+    if (n == -2) return t_group_finish_last_grid;
+    return n < 0 ? g_group_finish_persistent.load() : g_group_finish_persistent.exchange(n);
+}
+
 int swiftly_hip_wave_group_finish_pieces(swiftly_hip_t* h, int dtype, int64_t npieces, const void* const* q,
                                          const int64_t* q_facet_strides, const int32_t* const* rowmaps,
                                          const int64_t* n_rows, const int64_t* first, const int64_t* count,
@@ -914,9 +924,12 @@ int swiftly_hip_wave_group_finish_pieces(swiftly_hip_t* h, int dtype, int64_t np
                 a.ldc[b] = w.base;
                 a.st_a[b] = subgrid_in_padded_subgrid(*h, xA, sub_off0s[b0 + b]).a;
             }
-            if (int rc = launch_status(launch_group_finish(h->log_m, h->log_xM, a, nb, ngroups, (hipStream_t)stream), "group_finish",
-                                       "no instance"))
+            const int persistent = g_group_finish_persistent.load();
+            const int grid_cap = persistent == 1 ? h->cu_count : persistent;
+            if (int rc = launch_status(launch_group_finish(h->log_m, h->log_xM, a, nb, ngroups, grid_cap, (hipStream_t)stream),
+                                       "group_finish", "no instance"))
                 return rc;
+            t_group_finish_last_grid = (int)std::min<int64_t>((int64_t)((m + 15) / 16) * nb * ngroups, grid_cap);
         }
         if (stages & 2) {
             r.in = (const cx<float>*)t_work + b0 * r.in_bs;

@@ -170,6 +170,181 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel(c
     });
 }
 
-int launch_group_finish(int logm, int logx, const GroupFinishArgs& a, int nbatch, int ngroups, hipStream_t s);
+// The same tiles on a PERSISTENT grid: workgroup w walks the tiles t = w, w + gridDim.x, ... of the index space
+// (column tile, subgrid, group), column tile fastest -- a static walk: no counter in memory, no workgroup waits for
+// another.  A tile's arithmetic is group_finish_kernel's, call for call (same fft_phases, same placement adds in the same
+// order, same products, same stores): every output bit is the same.  What changes is what is in flight when.
+//
+// gfx950 counts a wave's loads AND stores in one in-order counter (vmcnt): waiting for any of them waits for everything
+// requested before it.  In group_finish_kernel every transform phase fetches its twiddles, every placement its Fn value
+// and every store its mask value from global memory, so the rows of facet n + 1, requested "ahead", are waited for at the
+// first table value of facet n's transform, each store is waited for at the next mask value, and from the last m-point
+// transform to the exit nothing is in flight at all.  Here
+//   - the tables (both twiddle tables, Fn) are copied once per workgroup into the LDS the exchange buffer leaves free, and
+//     the tile's window rows (a function of the thread-row only: M values, not M x 16) are looked up once per tile into
+//     LDS as well: the transforms make no global request, and what is in flight stays in flight under them;
+//   - x is waited for (touch) BEFORE the next rows are requested, never after;
+//   - the first facet of tile t + gridDim.x is requested before the inverse transform of tile t and waited for behind it,
+//     ahead of the tile's stores; the mask values are requested together, ahead of the first store; the stores then drain
+//     under the next tile's facet loop.
+// tr and c16 are made opaque once per tile: every per-lane LDS address of every phase derives from them, and hoisted out
+// of the tile loop they would all stay live across it (152 - 176 bytes of scratch per lane).
+template <int LOGM, int LOGX>
+struct GFPersistentLds {
+    static constexpr int M = 1 << LOGM, X = 1 << LOGX;
+    // behind the exchange buffer: tw_x[X], tw_m[M] (complex), Fn[M] (float), window rows[M] (int)
+    static constexpr size_t TW_X = GFGeo<LOGM, LOGX>::LDS_BYTES, TW_M = TW_X + X * sizeof(cx<float>),
+                            FN = TW_M + M * sizeof(cx<float>), ROWS = FN + M * sizeof(float), BYTES = ROWS + M * sizeof(int);
+};
+
+template <int LOGM, int LOGX>
+__global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel_persistent(const GroupFinishArgs A, const int nbatch,
+                                                                                          const int ntiles) {
+    using S = GFGeo<LOGM, LOGX>;
+    using GM = typename S::GM;
+    using GX = typename S::GX;
+    using L = GFPersistentLds<LOGM, LOGX>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int M = 1 << LOGM, X = 1 << LOGX, T = S::T, PM = GM::P, PX = GX::P, RATIO = X / M, NT = S::NT;
+    static_assert(PX == PM * RATIO, "accumulator slots");
+    static_assert(M <= NT, "one thread per window row");
+    cx<float>* const tw_x = reinterpret_cast<cx<float>*>(smem + L::TW_X);
+    cx<float>* const tw_m = reinterpret_cast<cx<float>*>(smem + L::TW_M);
+    float* const fn = reinterpret_cast<float*>(smem + L::FN);
+    int* const rows = reinterpret_cast<int*>(smem + L::ROWS);
+    int tr = threadIdx.x >> 4, c16 = threadIdx.x & 15;
+    const int ntx = (A.ncols + 15) >> 4;
+
+    // (column tile, subgrid, group) of tile t: workgroup-uniform, kept in scalar registers
+    auto decode = [&](int t, int& tx, int& b, int& g) {
+        const int q = t / ntx;
+        tx = __builtin_amdgcn_readfirstlane(t - q * ntx);
+        g = __builtin_amdgcn_readfirstlane(q / nbatch);
+        b = __builtin_amdgcn_readfirstlane(q - g * nbatch);
+    };
+    // window row ci (threads below M: ci = threadIdx.x) of a tile (tx, b): group_finish_kernel's in_row, once per thread-row
+    auto window_row = [&](int tx, int b) {
+        const int* __restrict__ rowmap = tx * 16 < A.split ? A.rowmap_b : A.rowmap_a;
+        const int q = (((int)threadIdx.x ^ (M >> 1)) + A.lda[b]) & (M - 1);
+        int idx = q + A.ldc[b];
+        if (idx >= A.yN) idx -= A.yN;
+        return rowmap ? rowmap[idx] : idx;
+    };
+    // the rows of facet entry n for tile (tx, b), whose window rows are in `rows`
+    auto load_rows = [&](cx<float> (&dst)[PM], int n, int tx) {
+        const bool from_b = tx * 16 < A.split;  // the tile's piece
+        const int col = tx * 16 + c16;
+        const bool live = col < A.ncols;
+        const cx<float>* __restrict__ in =
+            (from_b ? A.in_b : A.in_a) + col + (long long)A.fidx[n] * (from_b ? A.in_fs_b : A.in_fs_a);
+        static_for<0, PM>([&](auto vI) {
+            constexpr int v = decltype(vI)::value;
+            const int row = rows[tr + v * T];
+            cx<float> val = {0.f, 0.f};
+            if (row >= 0 && live) val = cp_load<true>(in + (unsigned)row * A.in_pitch);
+            dst[v] = val;
+        });
+    };
+    // every request for x has been answered from here on (the compiler's own wait would stand at x's first use: behind
+    // the requests made in between, which the one counter then waits for too)
+    auto touch = [](cx<float> (&v)[PM]) {
+        static_for<0, PM>([&](auto vI) {
+            const float re = v[decltype(vI)::value].x, im = v[decltype(vI)::value].y;
+            asm volatile("" ::"v"(re), "v"(im) : "memory");
+        });
+    };
+
+    int t = blockIdx.x, tx, b, g;
+    if (t >= ntiles) return;
+    decode(t, tx, b, g);
+    for (int i = threadIdx.x; i < X; i += NT) tw_x[i] = A.tw_x[i];
+    for (int i = threadIdx.x; i < M; i += NT) {
+        tw_m[i] = A.tw_m[i];
+        fn[i] = A.fn[i];
+    }
+    if (threadIdx.x < M) rows[threadIdx.x] = window_row(tx, b);
+    __syncthreads();
+    cx<float> x[PM], xn[PM];
+    if (A.gstart[g] < A.gstart[g + 1]) load_rows(x, A.gstart[g], tx);
+    touch(x);
+    for (;;) {  // workgroup-uniform
+        asm volatile("" : "+v"(tr), "+v"(c16));
+        // the next tile's window rows: requested here, parked in LDS behind the facet loop
+        const int t_next = t + gridDim.x;
+        const bool more = t_next < ntiles;
+        int tx_next = 0, b_next = 0, g_next = 0, row_next = 0;
+        if (more) {
+            decode(t_next, tx_next, b_next, g_next);
+            if (threadIdx.x < M) row_next = window_row(tx_next, b_next);
+        }
+        cx<float> y[PX];
+        static_for<0, PX>([&](auto vI) { y[decltype(vI)::value] = cx<float>{0.f, 0.f}; });
+        const int n_end = A.gstart[g + 1];
+        for (int n = A.gstart[g]; n < n_end; n++) {
+            const int sp = A.sp0[n];
+            if (n + 1 < n_end) load_rows(xn, n + 1, tx);
+            fft_phases<GM, float, 0>(x, tr, c16, true, smem, tw_m, [&](int e, cx<float> v, auto sI) {
+                constexpr int LR = GM::LOGN % GM::LOGP == 0 ? GM::LOGP : GM::LOGN % GM::LOGP, RAD = 1 << LR, NBL = PM / RAD;
+                constexpr int slot = (decltype(sI)::value / RAD) + NBL * (decltype(sI)::value % RAD);
+                const int ck = e ^ (M >> 1);
+                const int kk = (ck - sp) & (M - 1);
+                const int p = (kk - (M >> 1) + sp) & (X - 1);
+                const int c = p >> LOGM;
+                const float w = fn[kk];
+                static_for<0, RATIO>([&](auto cI) {
+                    constexpr int cc = decltype(cI)::value;
+                    const float wc = c == cc ? w : 0.f;
+                    y[slot + PM * cc].x += v.x * wc;
+                    y[slot + PM * cc].y += v.y * wc;
+                });
+            });
+            static_for<0, PM>([&](auto vI) { x[decltype(vI)::value] = xn[decltype(vI)::value]; });
+            touch(x);
+        }
+
+        // what the finishing tile's stores need
+        const int col = tx * 16 + c16;
+        const bool live = col < A.ncols;
+        cx<float>* __restrict__ out = A.out + (long long)g * A.out_gs + (long long)b * A.out_bs + col;
+        const float* __restrict__ mask = A.mask ? A.mask + (long long)b * A.mask_bs : nullptr;
+        const int st_a = A.st_a[b];
+        // the next tile's first facet: in flight under the inverse transform.  (Every lane is behind the last barrier of
+        // the facet loop, so behind every read of `rows`; every exchange ends with a barrier behind its gather and the last
+        // phase touches no LDS, so nothing of x is in the exchange buffer)
+        t = t_next; tx = tx_next; b = b_next; g = g_next;
+        asm volatile("" ::"v"(row_next) : "memory");  // (its wait, for every lane: not left to the branch below)
+        if (more) {
+            if (threadIdx.x < M) rows[threadIdx.x] = row_next;
+            __syncthreads();
+            if (A.gstart[g] < A.gstart[g + 1]) load_rows(x, A.gstart[g], tx);
+        }
+
+        // ---- xM-point inverse transform (conj . FFT . conj), crop, mask0, store
+        static_for<0, PX>([&](auto vI) { y[decltype(vI)::value].y = -y[decltype(vI)::value].y; });
+        const float scale = 1.f / (float)X;
+        cx<float> z[PX];
+        int d[PX];
+        fft_phases<GX, float, 0>(y, tr, c16, true, smem, tw_x, [&](int e, cx<float> v, auto sI) {
+            z[decltype(sI)::value] = v;
+            d[decltype(sI)::value] = ((e ^ (X >> 1)) + st_a) & (X - 1);
+        });
+        touch(x);
+        float w[PX];
+        static_for<0, PX>([&](auto sI) { w[decltype(sI)::value] = scale; });
+        if (mask)  // (the rows the crop drops read the last entry of the mask row: in bounds, not used)
+            static_for<0, PX>([&](auto sI) {
+                constexpr int s = decltype(sI)::value;
+                w[s] *= mask[d[s] < A.xA ? d[s] : A.xA - 1];
+            });
+        static_for<0, PX>([&](auto sI) {
+            constexpr int s = decltype(sI)::value;
+            if (d[s] < A.xA && live) cp_store<true>(out + (unsigned)d[s] * (unsigned)A.ncols, cx<float>{z[s].x * w[s], -z[s].y * w[s]});
+        });
+        if (!more) break;
+    }
+}
+
+// grid_cap = 0: one workgroup per tile (group_finish_kernel); > 0: the persistent kernel on min(tiles, grid_cap) workgroups
+int launch_group_finish(int logm, int logx, const GroupFinishArgs& a, int nbatch, int ngroups, int grid_cap, hipStream_t s);
 
 }  // namespace swf

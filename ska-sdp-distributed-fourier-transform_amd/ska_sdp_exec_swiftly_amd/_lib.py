@@ -150,6 +150,8 @@ def _declare(lib):
     ]
     lib.swiftly_hip_group_finish.restype = c_int
     lib.swiftly_hip_group_finish.argtypes = [c_int]
+    lib.swiftly_hip_group_finish_persistent.restype = c_int
+    lib.swiftly_hip_group_finish_persistent.argtypes = [c_int]
     lib.swiftly_hip_wave_subgrid_side.restype = c_int
     lib.swiftly_hip_wave_subgrid_side.argtypes = [
         vp, c_int, vp, i64, i64, i64, pi64, pi64, i64, pi64, pi64, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp,
