@@ -116,9 +116,12 @@ enum {
     SWIFTLY_FEATURE_REAL_FACETS_OUT = 9,        /* finish_facet_band_real (dtype = the INPUT type): the sizes of BACKWARD_BAND
                                                    in complex64 with a power-of-two yN_size; no complex128, no Q * 2^k.  The
                                                    gate the entry point refuses through */
-    SWIFTLY_FEATURE_GROUP_FINISH = 10           /* wave_group_finish_pieces (dtype, n_facets): FUSED_SUBGRID in complex64 with
+    SWIFTLY_FEATURE_GROUP_FINISH = 10,          /* wave_group_finish_pieces (dtype, n_facets): FUSED_SUBGRID in complex64 with
                                                    (m, xM) = (128, 256) or (512, 1024) and n_facets * xM / m <= 64.  The gate
                                                    the entry point refuses through */
+    SWIFTLY_FEATURE_REAL_WINDOW_ROWS = 11       /* prepare_facet_window_rows_real (dtype = the OUTPUT type), size part: the
+                                                   sizes of WINDOW_ROWS that are also sizes of REAL_FACETS in complex64.  The
+                                                   gate the entry point refuses through ("real window rows: ...") */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -585,6 +588,19 @@ int swiftly_hip_prepare_facet_window_rows(swiftly_hip_t* h, int dtype, const voi
                                           int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                           int64_t other_axis_row0, const int32_t* window_starts, int64_t nwindows,
                                           int64_t out_window_stride, void* stream);
+/* prepare_facet_window_rows for REAL-VALUED facets kept as float32: `in` points to float32, in_row_stride counts reals and
+ * `dtype` is the OUTPUT type (SWIFTLY_C64); every other argument as above.  The whole-row kernel loads a lane's two
+ * adjacent reals with one 8-byte load (half the bytes read, half the resident facet) and computes with a zero imaginary
+ * part, so `out` holds the values prepare_facet_window_rows gives for the facet promoted to complex64 (at most the sign
+ * of a zero differs).  Sizes: SWIFTLY_FEATURE_REAL_WINDOW_ROWS; per call what prepare_facet_window_rows needs, with an
+ * even real row stride and an 8-byte-aligned `in` (there is no 4-byte-load form: SWIFTLY_ERR_UNSUPPORTED, nothing is
+ * written -- promote the facet, or use prepare_facet_band_real + finish_axis1_rows).  swiftly_hip_last_band_instance
+ * reports family 1 (whole row), st 3 and real 1 for it. */
+int swiftly_hip_prepare_facet_window_rows_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                               int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                               int64_t band_start, int64_t band_len, int64_t other_axis_size,
+                                               int64_t other_axis_row0, const int32_t* window_starts, int64_t nwindows,
+                                               int64_t out_window_stride, void* stream);
 /* Backward subgrid side for all facets at once (mirror of sum_finish_facets): in[b] = [xM, subgrid_size] =
  * prepare_subgrid of subgrid b along axis 0 ONLY (core.py:328-368); out[f][b] = [m, m] contiguous = the contribution
  * of subgrid b to facet f, i.e. api_helper.prepare_and_split_subgrid (api_helper.py:115-139): prepare_subgrid along

@@ -233,6 +233,7 @@ static BandCall band_call_of(int logn, const RowPassArgs& a, const Win4Cache* w4
     c.has_twc = w4 && w4->twc;
     c.table_available = table_available;
     c.stage_columns = row_pass_whole_stage_columns(), c.max_windows = kWholeMaxWindows;
+    c.whole_real = true;  // row_whole.hip has the real window-rows instances
     return c;
 }
 // per thread: the instance the last call with rows settled on, and the number of such calls (last_band_instance)
@@ -260,7 +261,7 @@ int launch_row_pass_band_n(int logn, const RowPassArgs& a0, const cx<float>* tw_
     a.seg_rot = inst.seg_rot;
     a.ld_win4 = inst.ld_win4 ? table : nullptr;
     a.twc = inst.twc ? w4->twc : nullptr;
-    if (inst.family == kBandWholeRow) return launch_row_pass_whole(a, inst.nseg, tw_half, tw_full, s);
+    if (inst.family == kBandWholeRow) return launch_row_pass_whole(a, inst.nseg, inst.real, tw_half, tw_full, s);
     const unsigned blocks = (unsigned)(((a.nrows + 7) / 8) * 16);
 #define SWF_BAND_LAUNCH(G, WIN, ST, PAIR, NSEG, CJ, W4, REAL, REAL_ST)                                                       \
     if (inst.geo == k##G && inst.win == WIN && inst.st == ST && inst.pair == PAIR && inst.nseg == NSEG && inst.cj == CJ &&   \

@@ -34,17 +34,27 @@ int row_pass_whole_grid() {  // one workgroup per CU (256 VGPRs x 512 threads: a
     return v;
 }
 
-template <int NSEG, bool WIN = false>
+template <int NSEG, bool WIN = false, bool REAL = false>
 static int launch_whole_inst(const RowPassArgs& a, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s) {
     const int grid = a.nrows < row_pass_whole_grid() ? a.nrows : row_pass_whole_grid();
-    return launch_lds<row_pass_whole_kernel<NSEG, WIN>, (WIN ? kWholeWinLds : RGeoWhole::LDS_BYTES)>(
+    return launch_lds<row_pass_whole_kernel<NSEG, WIN, REAL>, (WIN ? kWholeWinLds : RGeoWhole::LDS_BYTES)>(
         dim3((unsigned)grid), dim3(RGeoWhole::NT), s, a, a.in, a.out, tw14, tw_full, a.row_win, a.in_rowmap);
 }
 
 // forward K1 with the re-laid-out window (a.ld_win4) and the compact twiddle sections (a.twc) set, a.seg_rot chosen for
-// `nseg` data segments; a.win_full: the window-rows store.  Whether a call runs this form is choose_band_instance's
-// decision (swiftly_rowinst.h); -1: no instance for `nseg`
-int launch_row_pass_whole(const RowPassArgs& a, int nseg, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s) {
+// `nseg` data segments; a.win_full: the window-rows store; `real` (BandInst::real): float32 rows (a.in_real), which only
+// the window-rows store has instances for.  Whether a call runs this form is choose_band_instance's decision
+// (swiftly_rowinst.h); -1: no instance for `nseg` / `real`
+int launch_row_pass_whole(const RowPassArgs& a, int nseg, int real, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s) {
+    if (real || a.in_real) {
+        if (real != 1 || !a.in_real || !a.win_full) return -1;
+        switch (nseg) {
+            case 16: return launch_whole_inst<16, true, true>(a, tw14, tw_full, s);
+            case 22: return launch_whole_inst<22, true, true>(a, tw14, tw_full, s);
+            case 24: return launch_whole_inst<24, true, true>(a, tw14, tw_full, s);
+            default: return -1;
+        }
+    }
     switch (nseg) {
         case 16: return a.win_full ? launch_whole_inst<16, true>(a, tw14, tw_full, s) : launch_whole_inst<16>(a, tw14, tw_full, s);
         case 22: return a.win_full ? launch_whole_inst<22, true>(a, tw14, tw_full, s) : launch_whole_inst<22>(a, tw14, tw_full, s);

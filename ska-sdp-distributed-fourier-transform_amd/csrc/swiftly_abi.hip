@@ -1304,7 +1304,10 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
                     (long long)rows, (long long)other_axis_size);
     DeviceGuard device_guard_(h->device);
     CHECK_DTYPE();
-    if (real_in) {  // float32 rows: the capability rule of SWIFTLY_FEATURE_REAL_FACETS
+    if (real_in && win_d) {  // float32 rows into the window-rows store: SWIFTLY_FEATURE_REAL_WINDOW_ROWS
+        if (const std::string why = why_not_real_window_rows(*h, dtype); !why.empty())
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_window_rows_real: %s", why.c_str());
+    } else if (real_in) {  // float32 rows: the capability rule of SWIFTLY_FEATURE_REAL_FACETS
         if (const std::string why = why_not_real_facets(*h, dtype); !why.empty())
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_real: %s", why.c_str());
     }
@@ -1371,7 +1374,8 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
     int e = launch_row_pass_band_n(h->log_yN, r, twh, twf, (hipStream_t)stream, &h->win4);
     if (e == -2)
         return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_window_rows: needs yN_size 32768, contribution size 512, even facet "
-                    "size / offset / row stride and a band of at most %d physical columns", row_pass_whole_stage_columns());
+                    "size / offset / row stride and a band of at most %d physical columns%s", row_pass_whole_stage_columns(),
+                    real_in ? ", an even real row stride and an 8-byte-aligned input" : "");
     return launch_status(e);
 }
 
@@ -1413,6 +1417,22 @@ int swiftly_hip_prepare_facet_window_rows(swiftly_hip_t* h, int dtype, const voi
                     (long long)out_row_stride, (long long)out_window_stride);
     return prepare_facet_band_rows_impl(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
                                         band_len, other_axis_size, other_axis_row0, window_starts, nwindows, out_window_stride, stream);
+}
+// the same for float32 rows (`in` real, in_row_stride in reals, dtype = the output type): the REAL window-rows instances of
+// the whole-row kernel, refused through SWIFTLY_FEATURE_REAL_WINDOW_ROWS
+int swiftly_hip_prepare_facet_window_rows_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                               int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                               int64_t band_start, int64_t band_len, int64_t other_axis_size,
+                                               int64_t other_axis_row0, const int32_t* window_starts, int64_t nwindows,
+                                               int64_t out_window_stride, void* stream) {
+    if (!window_starts || nwindows <= 0) return fail(SWIFTLY_ERR_PARAM, "prepare_facet_window_rows_real: no windows");
+    if (h && (out_window_stride < h->m || out_row_stride < h->m ||
+              (out_window_stride < rows * out_row_stride && out_row_stride < nwindows * out_window_stride)))
+        return fail(SWIFTLY_ERR_PARAM, "prepare_facet_window_rows_real: the window rows of the output overlap (row stride %lld, window stride %lld)",
+                    (long long)out_row_stride, (long long)out_window_stride);
+    return prepare_facet_band_rows_impl(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
+                                        band_len, other_axis_size, other_axis_row0, window_starts, nwindows, out_window_stride, stream,
+                                        true);
 }
 
 // finish_facet_band and its real-output twin (`out` float32, out_row_stride in reals; real_out): one implementation

@@ -274,5 +274,12 @@ inline std::string why_not_window_rows(const Sizes& s) {
     return reason("window rows: needs yN %d, m %d and xM <= %d; got yN %lld, m %lld, xM %lld", 1 << kWindowRowsLogYN,
                   1 << kWindowRowsLogM, 1 << kPlacedMaxLogXM, (long long)s.yN, (long long)s.m, (long long)s.xM);
 }
+// size part of prepare_facet_window_rows_real (float32 rows into the whole-row K1; dtype = the output type): the sizes both
+// the window rows and the real-load K1 exist for
+inline std::string why_not_real_window_rows(const Sizes& s, int dtype) {
+    if (std::string why = why_not_real_facets(s, dtype); !why.empty()) return "real window rows: " + why;
+    if (std::string why = why_not_window_rows(s); !why.empty()) return "real window rows: " + why;
+    return {};
+}
 
 }  // namespace swf

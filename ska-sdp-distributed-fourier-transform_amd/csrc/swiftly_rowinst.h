@@ -9,6 +9,8 @@
 //  * A real call differs from that complex call in the window path only: the complex K1 takes the window table at
 //    SWIFTLY_K1_WIN4 = 1 (RGeoPre with W4) where the real K1 has no such instance and keeps the plain window loads; and
 //    4-byte real loads (real = 2) never take W4.  Both paths multiply by the same window values.
+//  * The window-rows store of real rows (BandCall::whole_real, a fact about the whole-row family like stage_columns) is the
+//    complex window-rows call for the promoted row with real = 1, or a refusal (-2): it has 8-byte loads only.
 #pragma once
 
 namespace swf {
@@ -33,6 +35,7 @@ struct BandCall {
     bool has_twc = false;               // ... with compact twiddle sections
     bool table_available = false;       // Win4Cache::get would return a table
     int stage_columns = 0, max_windows = 0;  // row_pass_whole_stage_columns(), kWholeMaxWindows
+    bool whole_real = false;            // the whole-row family has real window-rows instances (row_whole.hip)
 };
 
 enum BandStatus { kBandChosen = 0, kBandNone = -1, kBandNotWindowRows = -2 };
@@ -111,12 +114,16 @@ inline BandInst choose_band_instance(const BandCall& c) {
 
     // -- what exists at all ----------------------------------------------------------------------------------------
     // real input: the forward K1 of the band pipeline (window, band store, the facet at the start of its rows)
-    if (c.in_real && (!c.ld_win || !band || c.win_full || c.ld_c != 0 || c.ld_mod != c.ld_len)) return refuse(kBandNone);
+    const bool real_windows = c.in_real && c.win_full && c.whole_real;  // (without whole_real: no such instance, as ever)
+    if (c.in_real && !real_windows && (!c.ld_win || !band || c.win_full || c.ld_c != 0 || c.ld_mod != c.ld_len))
+        return refuse(kBandNone);
     if (out_real && (!mapped || c.win_full)) return refuse(kBandNone);  // real output: the mapped store only
     if (c.win_full) {
         // window-rows store (whole-row kernel): 32768-point rows, 512-column windows, 16-byte loads
         if (c.logn != 15 || c.win_logm != 9 || c.nwin <= 0 || !c.win_d || !band) return refuse(kBandNotWindowRows);
         if (!pair_ok || !c.ld_win || !inv) return refuse(kBandNotWindowRows);
+        // real rows: two adjacent reals are one 8-byte load (there is no real = 2 form), the facet at the start of its rows
+        if (real_windows && (!load8 || c.ld_c != 0 || c.ld_mod != c.ld_len)) return refuse(kBandNotWindowRows);
     }
 
     // -- geometry --------------------------------------------------------------------------------------------------
@@ -150,7 +157,7 @@ inline BandInst choose_band_instance(const BandCall& c) {
                 r.key_n = 1 << c.logn, r.key_ns = ns, r.key_seglen = kBandSegLen;
                 r.key_c = (int)(((long long)c.ld_a + r.key_n / 2 + (long long)first * kBandSegLen) % r.key_n);
             }
-            if (r.twc && !c.in_real && (c.win_full || c.whole_enabled)) {
+            if (r.twc && (c.in_real ? real_windows : c.win_full || c.whole_enabled)) {
                 if (c.win_full && (c.nwin > c.max_windows || !c.win_fn || !c.win_tw_m || !c.win_twc_m ||
                                    2 * c.band_half > c.stage_columns))
                     return refuse(kBandNotWindowRows);

@@ -898,7 +898,7 @@ int launch_row_pass_band_n(int logn, const RowPassArgs& a, const cx<float>* tw_h
 struct BandInst;
 long long last_band_instance(BandInst* out);
 int row_pass_band_occupancy();
-int launch_row_pass_whole(const RowPassArgs& a, int nseg, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s);
+int launch_row_pass_whole(const RowPassArgs& a, int nseg, int real, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s);
 int row_pass_whole_grid();  // workgroups of a whole-row launch (one per CU)
 int row_pass_whole_enabled();  // SWIFTLY_K1_WHOLE (read once per process)
 

@@ -111,7 +111,12 @@ __device__ __forceinline__ void opaque_values(cx<float> (&v)[K]) {
 // epilogue finishes the contiguous axis for every planned window (see RowPassArgs) -- the K1 of the axis-1-first pipeline.
 // exchange buffer | Fn | window table of the window epilogue (kWholeMaxWindows entries, swiftly_caps.h)
 constexpr size_t kWholeWinLds = RGeoWhole::LDS_BYTES + 512 * sizeof(float) + kWholeMaxWindows * sizeof(int);
-template <int NSEG, bool WIN = false>
+// REAL (forward K1 of real-valued facets, RowPassArgs::in_real; WIN only): the row is float32 and in_pitch counts reals.  Same
+// element-to-lane map, segments, window table, twiddles and schedule; a lane's two adjacent points are ONE 8-byte load over a
+// descriptor of ld_len * 4 bytes at half the byte offset, so a data load of the next row holds two VGPRs instead of four while
+// it is in flight.  The window product is (x w, 0) and every operation on a zero imaginary part is exact: the window rows hold
+// the values the complex instance computes from the promoted row (at most the sign of a zero differs).
+template <int NSEG, bool WIN = false, bool REAL = false>
 __global__ __launch_bounds__(512, 2) void row_pass_whole_kernel(const RowPassArgs A, const cx<float>* __restrict__ gin,
                                                                 cx<float>* __restrict__ gout,
                                                                 const cx<float>* __restrict__ tw,
@@ -124,6 +129,8 @@ __global__ __launch_bounds__(512, 2) void row_pass_whole_kernel(const RowPassArg
     constexpr int R1 = 16, SEG = H / R1, SEGLEN = 2 * T;      // radix-16 first phase: points j + r * SEG, j = 2t + u
     constexpr int NS = NSEG, NB1 = NS - R1;
     static_assert(P == 32 && T == 512 && NS >= R1 && NS % 2 == 0 && NS <= 32, "forward K1 geometry");
+    static_assert(!REAL || WIN, "real rows: the window-rows store only");
+    constexpr int LSH = REAL ? 2 : 3;                          // log2 of the bytes of a point of the input row
     constexpr int NGA = NB1, NG = NB1 + (R1 - NB1) / 2;       // load groups: (r, r + 16) for r < NB1, then (r, r + 1)
     constexpr int LOGR1 = G::LOGN % G::LOGP;                   // 4
     constexpr int LNS1 = LOGR1, LNS2 = LOGR1 + G::LOGP;        // phase boundaries 4 and 9
@@ -134,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void row_pass_whole_kernel(const RowPassArg
 
     // -- constants of the lane (the same for every row) -----------------------------------------------------------
     const __amdgpu_buffer_rsrc_t rs_w4 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.ld_win4), (short)0, (NS / 2) * T * 16, 0x00020000);
-    const unsigned base8 = (unsigned)((2 * t + A.ld_a + (N >> 1) + rot) & (N - 1)) << 3;
+    const unsigned base8 = (unsigned)((2 * t + A.ld_a + (N >> 1) + rot) & (N - 1)) << LSH;
     // inter-half twiddle of the odd outputs: W_N^j, j = 2t + u + SEG r = W_N^(2t+u) * W_64^(2r)
     const f32x4 wt = *reinterpret_cast<const f32x4*>(tw_full + 2 * t);
     const cx<float> w0 = {wt.x, wt.y}, w1 = {wt.z, wt.w};
@@ -159,12 +166,21 @@ __global__ __launch_bounds__(512, 2) void row_pass_whole_kernel(const RowPassArg
         in_row = __builtin_amdgcn_readfirstlane(in_row);   // wave-uniform: the descriptor must live in SGPRs
         const bool dead = in_row < 0 || !live;   // absent from a compacted input / no further row: an empty descriptor
         if (in_row < 0) in_row = 0;
-        const char* inb = reinterpret_cast<const char*>(gin + (long long)in_row * A.in_pitch);
+        // (REAL: in_pitch counts 4-byte elements)
+        const char* inb = REAL ? reinterpret_cast<const char*>(reinterpret_cast<const float*>(gin) + (long long)in_row * A.in_pitch)
+                               : reinterpret_cast<const char*>(gin + (long long)in_row * A.in_pitch);
         const unsigned valid = (dead || (SWF_WHOLE_ABL & 1)) ? 0u : (unsigned)A.ld_len;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(inb), (short)0, (int)(valid << 3), 0x00020000);
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(inb), (short)0, (int)(valid << LSH), 0x00020000);
     };
 
-    f32x4 gw[NG], g0[NG], g1[NG];
+    // (REAL: a data load is 8 bytes, two adjacent reals -- two VGPRs instead of four)
+    using gdata = std::conditional_t<REAL, f32x2, f32x4>;
+    f32x4 gw[NG];
+    gdata g0[NG], g1[NG];
+    auto load_data = [](const __amdgpu_buffer_rsrc_t& rs_in, unsigned off) {
+        if constexpr (REAL) return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_in, (int)off, 0, 0));
+        else return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)off, 0, 0));
+    };
     auto issue_win = [&](auto gI, int t) {
         constexpr int g = decltype(gI)::value;
         gw[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w4, (g * T + t) << 4, 0, 0));
@@ -173,10 +189,10 @@ __global__ __launch_bounds__(512, 2) void row_pass_whole_kernel(const RowPassArg
         constexpr int g = decltype(gI)::value;
         constexpr int r0 = g < NGA ? g : NGA + 2 * (g - NGA);   // first slot of the group
         constexpr int s0 = r0, s1 = g < NGA ? r0 + R1 : r0 + 1; // its two segments
-        const unsigned o0 = (base8 + (unsigned)((s0 * SEG) << 3)) & (unsigned)((N << 3) - 1);
-        const unsigned o1 = (base8 + (unsigned)((s1 * SEG) << 3)) & (unsigned)((N << 3) - 1);
-        g0[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)o0, 0, 0));
-        g1[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)o1, 0, 0));
+        const unsigned o0 = (base8 + (unsigned)((s0 * SEG) << LSH)) & (unsigned)((N << LSH) - 1);
+        const unsigned o1 = (base8 + (unsigned)((s1 * SEG) << LSH)) & (unsigned)((N << LSH) - 1);
+        g0[g] = load_data(rs_in, o0);
+        g1[g] = load_data(rs_in, o1);
     };
     auto wmul = [&](f32x4 val, f32x2 w, cx<float>& e0, cx<float>& e1) {  // (x w, -y w) per point: window + conjugation
         const f32x2 p0 = {val.x, val.y}, p1 = {val.z, val.w};
@@ -261,8 +277,16 @@ __global__ __launch_bounds__(512, 2) void row_pass_whole_kernel(const RowPassArg
             constexpr int g = decltype(gI)::value;
             constexpr int r0 = g < NGA ? g : NGA + 2 * (g - NGA);
             cx<float> a0[2], a1[2];
-            wmul(g0[g], f32x2{gw[g].x, gw[g].y}, a0[0], a0[1]);
-            wmul(g1[g], f32x2{gw[g].z, gw[g].w}, a1[0], a1[1]);
+            if constexpr (REAL) {  // (x w, 0) for the two points of each load
+                const f32x2 p0 = g0[g] * f32x2{gw[g].x, gw[g].y}, p1 = g1[g] * f32x2{gw[g].z, gw[g].w};
+                a0[0] = cx<float>{p0.x, 0.f};
+                a0[1] = cx<float>{p0.y, 0.f};
+                a1[0] = cx<float>{p1.x, 0.f};
+                a1[1] = cx<float>{p1.y, 0.f};
+            } else {
+                wmul(g0[g], f32x2{gw[g].x, gw[g].y}, a0[0], a0[1]);
+                wmul(g1[g], f32x2{gw[g].z, gw[g].w}, a1[0], a1[1]);
+            }
             static_for<0, 2>([&](auto uI) {
                 constexpr int u = decltype(uI)::value;
                 if constexpr (g < NGA) {
@@ -430,8 +454,8 @@ __global__ __launch_bounds__(512, 2) void row_pass_whole_kernel(const RowPassArg
                 constexpr int g = E3 + i / 2;
                 constexpr int r0 = g < NGA ? g : NGA + 2 * (g - NGA);
                 constexpr int sg = (i & 1) ? (g < NGA ? r0 + R1 : r0 + 1) : r0;
-                const unsigned o = (b8 + (unsigned)((sg * SEG) << 3)) & (unsigned)((N << 3) - 1);
-                const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsn, (int)o, 0, 0));
+                const unsigned o = (b8 + (unsigned)((sg * SEG) << LSH)) & (unsigned)((N << LSH) - 1);
+                const gdata v = load_data(rsn, o);
                 if constexpr (i & 1) g1[g] = v; else g0[g] = v;
             } else if constexpr (i >= 2 * (NG - E3) && i < NLATE) {
                 issue_win(std::integral_constant<int, i - 2 * (NG - E3)>{}, tt);

@@ -18,7 +18,7 @@ ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
 # swiftly_hip_supports / swiftly_hip_limit (include/swiftly_hip.h)
 (FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
  FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE, FEATURE_REAL_FACETS,
- FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH) = range(11)
+ FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH, FEATURE_REAL_WINDOW_ROWS) = range(12)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None
@@ -162,6 +162,9 @@ def _declare(lib):
     lib.swiftly_hip_prepare_facet_window_rows.argtypes = [
         vp, c_int, vp, i64, i64, i64, vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, vp,
     ]
+    # float32 rows into the whole-row K1 (same arguments; `in` is real, the row stride counts reals, dtype = output type)
+    lib.swiftly_hip_prepare_facet_window_rows_real.restype = c_int
+    lib.swiftly_hip_prepare_facet_window_rows_real.argtypes = list(lib.swiftly_hip_prepare_facet_window_rows.argtypes)
     lib.swiftly_hip_finish_axis1_rows.restype = c_int
     lib.swiftly_hip_finish_axis1_rows.argtypes = [vp, c_int, vp, i64, i64, i64, i64, pi64, i64, i64, i64, vp, i64, i64, vp]
     lib.swiftly_hip_accumulate_facet_columns.restype = c_int

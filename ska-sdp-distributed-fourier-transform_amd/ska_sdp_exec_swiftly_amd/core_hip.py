@@ -674,13 +674,16 @@ class SwiftlyCoreHip:
         m, yN = self.xM_yN_size, self.yN_size
         return [((yN // 2 - m // 2 + int(o) * yN // self.N) - int(band[0])) % yN for o in wave_off1s]
 
-    def supports_window_rows(self, band, facet_size, facet_off1s, n_windows=1):
+    def supports_window_rows(self, band, facet_size, facet_off1s, n_windows=1, real=False):
         """can K1 finish the contiguous axis for every planned window in its epilogue (``prepare_facet_window_rows``)?
         (sizes with a whole-row kernel and a placed subgrid side, the band fits the LDS stage, no more windows than its
-        table holds -- all three from the native library -- and 16-byte loads possible)"""
+        table holds -- all three from the native library -- and 16-byte loads possible).  ``real=True``: for float32
+        facets as they are (``swiftly_hip_prepare_facet_window_rows_real``; 8-byte loads, i.e. rows at an even pitch on an
+        8-byte-aligned base, which the call itself checks)."""
         return (
             0 < int(n_windows) <= int(_lib.load().swiftly_hip_limit(_lib.LIMIT_WINDOW_ROWS_WINDOWS)) and
             self._supports(_lib.FEATURE_WINDOW_ROWS) and
+            (not real or self._supports(_lib.FEATURE_REAL_WINDOW_ROWS, _torch().complex64)) and
             self.band_columns(band) <= self.WINDOW_ROWS_STAGE_COLUMNS and int(band[1]) < self.yN_size and
             int(facet_size) % 2 == 0 and all(int(o) % 2 == 0 for o in facet_off1s)
         )
@@ -692,7 +695,17 @@ class SwiftlyCoreHip:
         for wave ``w`` (the parity-split window band of ``Fn * cfft_m``).  ``window_starts``: int32 DEVICE tensor
         (``window_starts(band, off1s)``); ``out``: ``[nwin, rows, m]`` (wave-major: K2 of a wave reads one contiguous block)
         or ``[rows, nwin * m]`` (the windows of a row side by side).  Hand ``out[w]`` (or the column block) to K2 with the
-        band ``(window start, m)`` and run ``wave_subgrid_side(..., placed=True)``."""
+        band ``(window start, m)`` and run ``wave_subgrid_side(..., placed=True)``.
+
+        A real-valued facet may be passed as a float32 tensor (``swiftly_hip_prepare_facet_window_rows_real``; ``out`` must be
+        complex64): the kernel loads the reals and ``out`` holds the values the promoted facet gives.  Its rows need an even
+        pitch and an 8-byte-aligned base -- ``NotImplementedError`` with the library's reason otherwise, never a copy."""
+        torch = _torch()
+        real = facet.dtype == torch.float32
+        if real and out.dtype != torch.complex64:
+            raise ValueError(f"Output array is {out.dtype}, a float32 facet needs {torch.complex64}!")
+        entry = self._lib.swiftly_hip_prepare_facet_window_rows_real if real else self._lib.swiftly_hip_prepare_facet_window_rows
+        code = _lib.C64 if real else self._code(facet)
         m = self.xM_yN_size
         nwin = int(window_starts.numel())
         if facet.dim() != 2 or facet.stride(1) != 1 or out.stride(-1) != 1:
@@ -707,8 +720,8 @@ class SwiftlyCoreHip:
         size, row0 = rows_of if rows_of is not None else (facet.shape[0], 0)
         cvp = ctypes.c_void_p
         _lib.check(
-            self._lib.swiftly_hip_prepare_facet_window_rows(
-                self._handle, self._code(facet), cvp(facet.data_ptr()), int(facet.shape[0]), int(facet.shape[1]),
+            entry(
+                self._handle, code, cvp(facet.data_ptr()), int(facet.shape[0]), int(facet.shape[1]),
                 facet.stride(0), cvp(out.data_ptr()), row_stride, int(facet_off), int(band[0]), int(band[1]),
                 int(size) if fold_other_axis_window else 0, int(row0), cvp(window_starts.data_ptr()), nwin, win_stride,
                 self._stream(),

@@ -43,8 +43,8 @@ class SwiftlyForward(WavePrefetch):
         numpy array or a torch tensor (complex64 or complex128; it is uploaded
         once and stays in HBM).  Real-valued facets given as float32 stay float32 -- on the host, on the wire and in HBM,
         half the bytes -- when every facet is float32, the object runs ``wave_axis == 1`` with a K1 that loads reals
-        (``core.supports_real_facets()``, not the whole-row K1 of ``axis1_first=True``); see :py:attr:`facet_dtype`.
-        In every other case they are promoted to complex64
+        (``core.supports_real_facets()``; under ``axis1_first=True``, whose whole-row K1 finishes the contiguous axis, only
+        when ``facet_dtype`` asks for it); see :py:attr:`facet_dtype`.  In every other case they are promoted to complex64
     :param lru_forward: number of subgrid columns (distinct ``off0``) whose
         prepared facet columns ``NMBF_BF`` are kept
     :param queue_size: bound on unfinished subgrid tasks (reference
@@ -52,13 +52,22 @@ class SwiftlyForward(WavePrefetch):
         while that many earlier results are still being computed
     :param subgrid_configs: optional (extension) list of all subgrids that will
         be requested; enables row-compacted ``BF_F`` for sparse subgrid sets
+    :param facet_dtype: ``None`` (default), or ``torch.float32`` / ``"float32"``: "my facets are real-valued, keep them
+        float32 wherever a real K1 exists" -- the accurate order included (``SwiftlyConfig(axis1_first=True)`` with a plan:
+        the real window-rows form of the whole-row K1, ``core.supports_window_rows(..., real=True)``), which the default
+        leaves on promoted complex64 facets.  Every facet must then be float32 (``ValueError`` otherwise).  Where no real K1
+        exists (``wave_axis=0``, ``yN_size`` = Q * 2^k, facets above 23552 pixels at ``yN_size`` 32768, device rows that
+        are not 8-byte aligned at an even pitch under the accurate order, the multi-GPU classes) the facets are promoted as
+        before and :py:attr:`facet_dtype` says complex64.  The results are those of the promoted facets bit for bit.
+        Any other value: ``ValueError``
     """
 
     # pylint: disable=too-many-arguments,too-many-instance-attributes
     def __init__(
         self, swiftly_config, facet_tasks, lru_forward=1, queue_size=20, client=None, subgrid_configs=None,
-        wave_axis=None, delayed=False,
+        wave_axis=None, delayed=False, facet_dtype=None,
     ):
+        self._facet_dtype_asked = self._parse_facet_dtype(facet_dtype)
         WavePrefetch.__init__(self)
         self.delayed = bool(delayed)  # hand out DeviceTask handles instead of bare device tensors
         facet_tasks = [(cfg, _unwrap(data)) for cfg, data in facet_tasks]
@@ -94,6 +103,8 @@ class SwiftlyForward(WavePrefetch):
         if len(dtypes) > 1:
             raise ValueError("all facets must have the same dtype")
         self.dtype = dtypes.pop() if dtypes else torch.complex64
+        if self._facet_dtype_asked is not None and not self._ingest.all_float32:
+            raise ValueError("facet_dtype=float32 needs every facet as a row-major float32 array")
         if wave_axis is None:
             # default: the reference's schedule (waves keyed by off0) -- unless the caller hands over the plan of
             # subgrids it is going to request AND the contiguous-axis-first kernels exist for this configuration:
@@ -129,17 +140,39 @@ class SwiftlyForward(WavePrefetch):
         :py:attr:`dtype` (the complex dtype everything downstream of K1 computes in)"""
         return _torch().float32 if self._ingest.real else self.dtype
 
+    @staticmethod
+    def _parse_facet_dtype(facet_dtype):
+        """``facet_dtype`` as given to the constructor: ``None``, or float32 (torch dtype, or anything ``numpy.dtype`` reads
+        as float32, parsed as in ``SwiftlyBackward._parse_facet_dtype``) -> ``torch.float32``; ``ValueError`` otherwise"""
+        if facet_dtype is None:
+            return None
+        torch = _torch()
+        if not isinstance(facet_dtype, torch.dtype):
+            try:
+                facet_dtype = torch.float32 if numpy.dtype(facet_dtype) == numpy.dtype(numpy.float32) else None
+            except TypeError:
+                facet_dtype = None
+        if facet_dtype != torch.float32:
+            raise ValueError("facet_dtype must be float32 or None")
+        return facet_dtype
+
     def _k1_loads_reals(self):
         """would K1 of this object take float32 facets as they are?  Every facet float32, the contiguous-axis-first
         pipeline (``wave_axis == 1``), a real-load form of its row kernel for these sizes (``core.supports_real_facets``),
-        and not axis-1-first mode 2, whose whole-row K1 has no real form."""
+        and not axis-1-first mode 2 -- unless the caller asked (``facet_dtype=float32``) and the whole-row K1 of mode 2
+        has its real form for this plan and can load these facets eight bytes at a time."""
         core = self.core
         if not (self._ingest.all_float32 and self.wave_axis == 1 and core.supports_real_facets()):
             return False
         if not all(core._real_rows_match_promoted(info[1][1]) for info in self._facet_info):
             return False
         band = core.band_for_offsets([sg.off1 for sg in self._plan]) if self._plan is not None else (0, core.yN_size)
-        return self._axis1_mode_for(band, real=False) != 2
+        if self._axis1_mode_for(band, real=False) != 2:
+            return True
+        # (device facets are read in place: two adjacent reals must be one aligned 8-byte load; uploads are contiguous)
+        aligned = all(ten is None or ten.device != core.device or (ten.stride(0) % 2 == 0 and ten.data_ptr() % 8 == 0)
+                      for ten in self._ingest.tensors)
+        return self._facet_dtype_asked is not None and aligned and self._axis1_mode_for(band, real=True) == 2
 
     # -- tables derived from the plan: each built on first use by ONE walk over the plan (505 configs x 25 waves on every
     # pass otherwise), and not at all for objects that never need it
@@ -527,13 +560,13 @@ class SwiftlyForward(WavePrefetch):
         needs a plan -- the windows are the plan's waves -- and a configuration with core.supports_window_rows)."""
         if not axis1_first_active(self.core, self.wave_axis, self.dtype):
             return 0
-        # (``real``: the facets are resident as float32.  The whole-row K1 of mode 2 has no real-load form: _k1_loads_reals
-        # keeps them real only when the plan's own band does not lead to mode 2, and band buffers installed from outside
-        # never get it)
+        # (``real``: the facets are resident as float32.  The whole-row K1 of mode 2 loads reals only for a caller who asked
+        # (``facet_dtype=float32``): without the keyword _k1_loads_reals keeps them real only when the plan's own band does
+        # not lead to mode 2, and band buffers installed from outside never get it)
         if (self.core.axis1_first is True and self.axis1_fused and self._plan is not None and band is not None and
-                not real and
+                (not real or self._facet_dtype_asked is not None) and
                 self.core.supports_window_rows(band, self._facet_info[0][1][1], [cfg.off1 for cfg in self.facet_configs],
-                                               n_windows=len(self._planned_keys))):
+                                               n_windows=len(self._planned_keys), real=bool(real))):
             return 2
         return 1
 
