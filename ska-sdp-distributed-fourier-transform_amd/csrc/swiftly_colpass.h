@@ -281,7 +281,7 @@ __device__ __forceinline__ void col_pass_body(const ColPassArgs& A, const cx<ST>
     constexpr bool RAW_LD = MODE == 1, RAW_ST = MODE == 0;
     constexpr bool NT_LD = RAW_LD ? SNT : true, NT_ST = RAW_ST ? SNT : true;
     // last Stockham phase: radix 2^LR at stride 2^LNS  (phases are LOGP, LOGP, ..., remainder)
-    constexpr int LR = G::LOGN <= G::LOGP ? G::LOGN : (G::LOGN % G::LOGP == 0 ? G::LOGP : G::LOGN % G::LOGP);
+    constexpr int LR = last_phase_logr<G>();
     constexpr int LNS = G::LOGN - LR;
     const int hw = HALF ? lane >> 5 : 0;              // which half-wave (32-column tiles: two rows per wave)
     const int t = HALF ? 2 * wave + hw : wave;        // thread-row id: owns rows t + v*T

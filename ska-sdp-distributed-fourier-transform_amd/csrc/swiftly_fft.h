@@ -429,6 +429,18 @@ __device__ __forceinline__ void phase_scatter(const cx<R> (&x)[G::P], int t, F&&
         });
     });
 }
+// The last phase of fft_phases<G, R, 0> (phases of LOGP, LOGP, ..., remainder bits): its radix, and the register slot v
+// (e = t + T * v) that holds its output `s`, the slot number phase_scatter hands to f: s = u * RAD + r is element
+// e = t + T * (u + NB * r), because the last phase's stride is N / RAD = T * NB.
+template <class G>
+constexpr int last_phase_logr() {
+    return G::LOGN <= G::LOGP ? G::LOGN : (G::LOGN % G::LOGP == 0 ? G::LOGP : G::LOGN % G::LOGP);
+}
+template <class G>
+constexpr int last_phase_slot(int s) {
+    constexpr int RAD = 1 << last_phase_logr<G>(), NB = G::P / RAD;
+    return s / RAD + NB * (s % RAD);
+}
 
 // Exchange through LDS: scatter phase output, then gather x[v] = buf[t + v*T].
 // Addresses are one runtime base per butterfly (scatter) / per thread (gather)

@@ -21,13 +21,14 @@
 // Geometry: 16-column tiles (128-byte row segments), 64 thread-rows, 1024 threads: thread (tr, c) owns the points
 // tr + 64 v of column c in BOTH transforms (m/64 and xM/64 points per lane).  The accumulator of a lane is the register
 // image of its xM-point input: output e of the m-point transform lands, placed, at a plain inverse-transform index that
-// is congruent to e modulo m (see sum_finish_facets_kernel, "ACCUMULATOR IN REGISTERS"), i.e. in one of the SAME lane's
+// is congruent to e modulo m (swiftly_place.h, shared with sum_finish_facets_kernel), i.e. in one of the SAME lane's
 // inputs, so the placement is xM/m weighted adds per output and neither an accumulator nor a hand-over plane sits in LDS
 // (the r3 form of this kernel, tools/experiments/swiftly_groupfinish.h, went through a [m][16] plane and two more
 // barriers per facet).  One exchange buffer [xM][16] serves both transforms.
 #pragma once
 #include "swiftly_caps.h"  // GF_PAIRS, kGroupFinishMaxFacets
 #include "swiftly_colpass.h"
+#include "swiftly_place.h"
 
 namespace swf {
 
@@ -82,35 +83,67 @@ struct GFGeo {
     static constexpr size_t LDS_BYTES = GX::LDS_BYTES;
 };
 
+// ---- The pieces of one tile (column tile tx, subgrid b, group g) that both kernels below are made of.  What differs
+// between the kernels -- where the tables and the window rows live, what is requested when -- stays in the kernels.
+
+// the piece of column tile tx (workgroup-uniform): its row map, column col of its facet 0, its facet stride
+__device__ __forceinline__ bool gf_from_b(const GroupFinishArgs& A, int tx) { return tx * 16 < A.split; }
+__device__ __forceinline__ const int* gf_rowmap(const GroupFinishArgs& A, int tx) { return gf_from_b(A, tx) ? A.rowmap_b : A.rowmap_a; }
+__device__ __forceinline__ const cx<float>* gf_piece_column(const GroupFinishArgs& A, int tx, int col) {
+    return (gf_from_b(A, tx) ? A.in_b : A.in_a) + col;
+}
+__device__ __forceinline__ long long gf_facet_stride(const GroupFinishArgs& A, int tx) { return gf_from_b(A, tx) ? A.in_fs_b : A.in_fs_a; }
+// physical row of input point i of the m-point transform (the same for every facet: the window only depends on the
+// subgrid); negative = absent
+template <int M>
+__device__ __forceinline__ int gf_window_row(const GroupFinishArgs& A, const int* rowmap, int b, int i) {
+    const int ci = i ^ (M >> 1);
+    const int q = (ci + A.lda[b]) & (M - 1);
+    int idx = q + A.ldc[b];
+    if (idx >= A.yN) idx -= A.yN;
+    return rowmap ? rowmap[idx] : idx;
+}
+// the rows of one facet: dst[v] = point tr + v * T of column col, whose physical row is row_of(v); src = the piece's
+// column col, facet = the facet's index in the piece, fs = the piece's facet stride
+template <int PM, class RowOf>
+__device__ __forceinline__ void gf_load_rows(const GroupFinishArgs& A, cx<float> (&dst)[PM], const cx<float>* src, int facet, long long fs,
+                                             int col, RowOf&& row_of) {
+    const bool live = col < A.ncols;
+    const cx<float>* __restrict__ in = src + (long long)facet * fs;
+    static_for<0, PM>([&](auto vI) {
+        const int row = row_of(vI);
+        cx<float> val = {0.f, 0.f};
+        if (row >= 0 && live) val = cp_load<true>(in + (unsigned)row * A.in_pitch);
+        dst[decltype(vI)::value] = val;
+    });
+}
+// where the tile's column goes (element d of the cropped axis at + d * ncols), and the mask row of its subgrid, if any
+__device__ __forceinline__ cx<float>* gf_out_column(const GroupFinishArgs& A, int col, int b, int g) {
+    return A.out + (long long)g * A.out_gs + (long long)b * A.out_bs + col;
+}
+__device__ __forceinline__ const float* gf_mask_row(const GroupFinishArgs& A, int b) {
+    return A.mask ? A.mask + (long long)b * A.mask_bs : nullptr;
+}
+
+// One workgroup per tile: window rows in registers, tables read from global memory, mask loaded inside the store callback.
 template <int LOGM, int LOGX>
 __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel(const GroupFinishArgs A) {
     using S = GFGeo<LOGM, LOGX>;
     using GM = typename S::GM;
     using GX = typename S::GX;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int M = 1 << LOGM, X = 1 << LOGX, T = S::T, PM = GM::P, PX = GX::P, RATIO = X / M;
-    static_assert(PX == PM * RATIO, "accumulator slots");
+    constexpr int M = 1 << LOGM, X = 1 << LOGX, T = S::T, PM = GM::P, PX = GX::P;
     const int tr = threadIdx.x >> 4, c16 = threadIdx.x & 15;
     const int col = blockIdx.x * 16 + c16;
     const bool live = col < A.ncols;
     const int b = blockIdx.y;  // subgrid of the wave
     const int g = blockIdx.z;  // off1 group
-    // the tile's piece (workgroup-uniform)
-    const bool from_b = (int)blockIdx.x * 16 < A.split;
-    const cx<float>* __restrict__ src = (from_b ? A.in_b : A.in_a) + col;
-    const long long in_fs = from_b ? A.in_fs_b : A.in_fs_a;
-    const int* __restrict__ rowmap = from_b ? A.rowmap_b : A.rowmap_a;
+    const cx<float>* __restrict__ src = gf_piece_column(A, blockIdx.x, col);
+    const long long in_fs = gf_facet_stride(A, blockIdx.x);
+    const int* __restrict__ rowmap = gf_rowmap(A, blockIdx.x);
 
-    // input rows of the m-point transform (the same for every facet: the window only depends on the subgrid)
     int in_row[PM];
-    static_for<0, PM>([&](auto vI) {
-        constexpr int v = decltype(vI)::value;
-        const int ci = (tr + v * T) ^ (M >> 1);
-        const int q = (ci + A.lda[b]) & (M - 1);
-        int idx = q + A.ldc[b];
-        if (idx >= A.yN) idx -= A.yN;
-        in_row[v] = rowmap ? rowmap[idx] : idx;
-    });
+    static_for<0, PM>([&](auto vI) { in_row[decltype(vI)::value] = gf_window_row<M>(A, rowmap, b, tr + decltype(vI)::value * T); });
 
     cx<float> y[PX];  // the lane's part of the padded column, y[v] = column[tr + v * T] at its plain inverse-transform index
     static_for<0, PX>([&](auto vI) { y[decltype(vI)::value] = cx<float>{0.f, 0.f}; });
@@ -118,13 +151,7 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel(c
     // the rows of facet n+1 are requested before facet n is transformed (the workgroup is alone on its CU: nothing else
     // hides the HBM latency)
     auto load_rows = [&](cx<float> (&dst)[PM], int n) {
-        const cx<float>* __restrict__ in = src + (long long)A.fidx[n] * in_fs;
-        static_for<0, PM>([&](auto vI) {
-            constexpr int v = decltype(vI)::value;
-            cx<float> val = {0.f, 0.f};
-            if (in_row[v] >= 0 && live) val = cp_load<true>(in + (unsigned)in_row[v] * A.in_pitch);
-            dst[v] = val;
-        });
+        gf_load_rows(A, dst, src, A.fidx[n], in_fs, col, [&](auto vI) { return in_row[decltype(vI)::value]; });
     };
     const int n_end = A.gstart[g + 1];
     cx<float> x[PM], xn[PM];
@@ -133,20 +160,7 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel(c
         const int sp = A.sp0[n];
         if (n + 1 < n_end) load_rows(xn, n + 1);
         fft_phases<GM, float, 0>(x, tr, c16, true, smem, A.tw_m, [&](int e, cx<float> v, auto sI) {
-            // slot = u * RAD + r of the last phase (radix RAD = 2^LR, NBL = PM / RAD blocks): e = tr + T * (u + NBL * r)
-            constexpr int LR = GM::LOGN % GM::LOGP == 0 ? GM::LOGP : GM::LOGN % GM::LOGP, RAD = 1 << LR, NBL = PM / RAD;
-            constexpr int slot = (decltype(sI)::value / RAD) + NBL * (decltype(sI)::value % RAD);
-            const int ck = e ^ (M >> 1);
-            const int kk = (ck - sp) & (M - 1);              // row of G = Fn[kk] * F[(kk + s') mod m]
-            const int p = (kk - (M >> 1) + sp) & (X - 1);    // plain inverse-transform index of the placed element
-            const int c = p >> LOGM;
-            const float w = A.fn[kk];
-            static_for<0, RATIO>([&](auto cI) {
-                constexpr int cc = decltype(cI)::value;
-                const float wc = c == cc ? w : 0.f;
-                y[slot + PM * cc].x += v.x * wc;
-                y[slot + PM * cc].y += v.y * wc;
-            });
+            place_output<GM, LOGX, decltype(sI)::value>(y, e, sp, v, A.fn);
         });
         // (every exchange ends with a barrier behind its gather and the last phase touches no LDS: the next transform may
         // scatter at once)
@@ -154,14 +168,13 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel(c
     }
 
     // ---- xM-point inverse transform (conj . FFT . conj), crop, mask0, store
-    static_for<0, PX>([&](auto vI) { y[decltype(vI)::value].y = -y[decltype(vI)::value].y; });
-    cx<float>* __restrict__ out = A.out + (long long)g * A.out_gs + (long long)b * A.out_bs + col;
-    const float* __restrict__ mask = A.mask ? A.mask + (long long)b * A.mask_bs : nullptr;
+    conj_regs(y);
+    cx<float>* __restrict__ out = gf_out_column(A, col, b, g);
+    const float* __restrict__ mask = gf_mask_row(A, b);
     const int st_a = A.st_a[b];
     const float scale = 1.f / (float)X;
     fft_phases<GX, float, 0>(y, tr, c16, true, smem, A.tw_x, [&](int e, cx<float> v) {
-        const int ck = e ^ (X >> 1);
-        const int d = (ck + st_a) & (X - 1);
+        const int d = crop_index<X>(e, st_a);
         if (d < A.xA && live) {
             float w = scale;
             if (mask) w *= mask[d];
@@ -172,8 +185,8 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel(c
 
 // The same tiles on a PERSISTENT grid: workgroup w walks the tiles t = w, w + gridDim.x, ... of the index space
 // (column tile, subgrid, group), column tile fastest -- a static walk: no counter in memory, no workgroup waits for
-// another.  A tile's arithmetic is group_finish_kernel's, call for call (same fft_phases, same placement adds in the same
-// order, same products, same stores): every output bit is the same.  What changes is what is in flight when.
+// another.  A tile's arithmetic is group_finish_kernel's: the same tile pieces (above), fft_phases, place_output and
+// products, so every output bit is the same.  What changes is what is in flight when.
 //
 // gfx950 counts a wave's loads AND stores in one in-order counter (vmcnt): waiting for any of them waits for everything
 // requested before it.  In group_finish_kernel every transform phase fetches its twiddles, every placement its Fn value
@@ -205,8 +218,7 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel_p
     using GX = typename S::GX;
     using L = GFPersistentLds<LOGM, LOGX>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int M = 1 << LOGM, X = 1 << LOGX, T = S::T, PM = GM::P, PX = GX::P, RATIO = X / M, NT = S::NT;
-    static_assert(PX == PM * RATIO, "accumulator slots");
+    constexpr int M = 1 << LOGM, X = 1 << LOGX, T = S::T, PM = GM::P, PX = GX::P, NT = S::NT;
     static_assert(M <= NT, "one thread per window row");
     cx<float>* const tw_x = reinterpret_cast<cx<float>*>(smem + L::TW_X);
     cx<float>* const tw_m = reinterpret_cast<cx<float>*>(smem + L::TW_M);
@@ -223,27 +235,12 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel_p
         b = __builtin_amdgcn_readfirstlane(q - g * nbatch);
     };
     // window row ci (threads below M: ci = threadIdx.x) of a tile (tx, b): group_finish_kernel's in_row, once per thread-row
-    auto window_row = [&](int tx, int b) {
-        const int* __restrict__ rowmap = tx * 16 < A.split ? A.rowmap_b : A.rowmap_a;
-        const int q = (((int)threadIdx.x ^ (M >> 1)) + A.lda[b]) & (M - 1);
-        int idx = q + A.ldc[b];
-        if (idx >= A.yN) idx -= A.yN;
-        return rowmap ? rowmap[idx] : idx;
-    };
+    auto window_row = [&](int tx, int b) { return gf_window_row<M>(A, gf_rowmap(A, tx), b, (int)threadIdx.x); };
     // the rows of facet entry n for tile (tx, b), whose window rows are in `rows`
     auto load_rows = [&](cx<float> (&dst)[PM], int n, int tx) {
-        const bool from_b = tx * 16 < A.split;  // the tile's piece
         const int col = tx * 16 + c16;
-        const bool live = col < A.ncols;
-        const cx<float>* __restrict__ in =
-            (from_b ? A.in_b : A.in_a) + col + (long long)A.fidx[n] * (from_b ? A.in_fs_b : A.in_fs_a);
-        static_for<0, PM>([&](auto vI) {
-            constexpr int v = decltype(vI)::value;
-            const int row = rows[tr + v * T];
-            cx<float> val = {0.f, 0.f};
-            if (row >= 0 && live) val = cp_load<true>(in + (unsigned)row * A.in_pitch);
-            dst[v] = val;
-        });
+        gf_load_rows(A, dst, gf_piece_column(A, tx, col), A.fidx[n], gf_facet_stride(A, tx), col,
+                     [&](auto vI) { return rows[tr + decltype(vI)::value * T]; });
     };
     // every request for x has been answered from here on (the compiler's own wait would stand at x's first use: behind
     // the requests made in between, which the one counter then waits for too)
@@ -284,19 +281,7 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel_p
             const int sp = A.sp0[n];
             if (n + 1 < n_end) load_rows(xn, n + 1, tx);
             fft_phases<GM, float, 0>(x, tr, c16, true, smem, tw_m, [&](int e, cx<float> v, auto sI) {
-                constexpr int LR = GM::LOGN % GM::LOGP == 0 ? GM::LOGP : GM::LOGN % GM::LOGP, RAD = 1 << LR, NBL = PM / RAD;
-                constexpr int slot = (decltype(sI)::value / RAD) + NBL * (decltype(sI)::value % RAD);
-                const int ck = e ^ (M >> 1);
-                const int kk = (ck - sp) & (M - 1);
-                const int p = (kk - (M >> 1) + sp) & (X - 1);
-                const int c = p >> LOGM;
-                const float w = fn[kk];
-                static_for<0, RATIO>([&](auto cI) {
-                    constexpr int cc = decltype(cI)::value;
-                    const float wc = c == cc ? w : 0.f;
-                    y[slot + PM * cc].x += v.x * wc;
-                    y[slot + PM * cc].y += v.y * wc;
-                });
+                place_output<GM, LOGX, decltype(sI)::value>(y, e, sp, v, fn);
             });
             static_for<0, PM>([&](auto vI) { x[decltype(vI)::value] = xn[decltype(vI)::value]; });
             touch(x);
@@ -305,8 +290,8 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel_p
         // what the finishing tile's stores need
         const int col = tx * 16 + c16;
         const bool live = col < A.ncols;
-        cx<float>* __restrict__ out = A.out + (long long)g * A.out_gs + (long long)b * A.out_bs + col;
-        const float* __restrict__ mask = A.mask ? A.mask + (long long)b * A.mask_bs : nullptr;
+        cx<float>* __restrict__ out = gf_out_column(A, col, b, g);
+        const float* __restrict__ mask = gf_mask_row(A, b);
         const int st_a = A.st_a[b];
         // the next tile's first facet: in flight under the inverse transform.  (Every lane is behind the last barrier of
         // the facet loop, so behind every read of `rows`; every exchange ends with a barrier behind its gather and the last
@@ -320,13 +305,13 @@ __global__ __launch_bounds__((GFGeo<LOGM, LOGX>::NT)) void group_finish_kernel_p
         }
 
         // ---- xM-point inverse transform (conj . FFT . conj), crop, mask0, store
-        static_for<0, PX>([&](auto vI) { y[decltype(vI)::value].y = -y[decltype(vI)::value].y; });
+        conj_regs(y);
         const float scale = 1.f / (float)X;
         cx<float> z[PX];
         int d[PX];
         fft_phases<GX, float, 0>(y, tr, c16, true, smem, tw_x, [&](int e, cx<float> v, auto sI) {
             z[decltype(sI)::value] = v;
-            d[decltype(sI)::value] = ((e ^ (X >> 1)) + st_a) & (X - 1);
+            d[decltype(sI)::value] = crop_index<X>(e, st_a);
         });
         touch(x);
         float w[PX];

@@ -12,6 +12,7 @@
 #pragma once
 #include "swiftly_caps.h"  // kSumFinishMaxFacets, the (m, xM) instance tables
 #include "swiftly_fft.h"
+#include "swiftly_place.h"
 
 namespace swf {
 
@@ -222,140 +223,163 @@ struct SumFinishFacetArgs {
     int placed;
 };
 
-// (register form, 1024-point rows: 4 waves per SIMD = 16 rows per CU, which the 8.7 KB of LDS per row now allow)
-// R = double: complex128 G / out, double Fn / mask / twiddle tables (the pointers of SumFinishFacetArgs reinterpreted), plain
-// (not compact) twiddle tables; register form only
-// (complex128: at least two waves per SIMD, i.e. up to 256 VGPRs -- the accumulator row of doubles spills at 128)
-template <int LOGM, int LOGX, typename R = float>
-__global__ __launch_bounds__((SFGeo<LOGM, LOGX, R>::NT), (!std::is_same_v<R, float> ? 2 : LOGX <= 10 ? 4 : 1)) void sum_finish_facets_kernel(const SumFinishFacetArgs A) {
+// The pointers of SumFinishFacetArgs as an instance sees them (R = double: complex128 G / out, double Fn / mask /
+// twiddle tables, plain -- not compact -- twiddle tables)
+template <typename R>
+struct SFFacetPtrs {
+    const cx<R>* in;
+    cx<R>* out;
+    const R *fn, *mask;
+    const cx<R>*tw_m, *tw_x, *twc_m, *twc_x;
+};
+
+// Wave-parallel form (SFWide: 4096-point rows, complex64): accumulator row in LDS behind the m-point exchange buffers
+template <int LOGM, int LOGX>
+__device__ __forceinline__ void sum_finish_facets_wide(const SumFinishFacetArgs& A, const SFFacetPtrs<float>& P) {
+    using R = float;
     using S = SFGeo<LOGM, LOGX, R>;
     using GX = typename S::GX;
     using W = SFWide<LOGM, LOGX>;
-    using GM = std::conditional_t<W::ON, typename W::GM, typename S::GM>;
-    static_assert(std::is_same_v<R, float> || !W::ON, "complex128: register form only");
+    using GM = typename W::GM;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    cx<R>* ex_m = reinterpret_cast<cx<R>*>(smem);
+    cx<R>* acc = reinterpret_cast<cx<R>*>(smem + W::LDS_M);
+    constexpr int M = GM::N, X = GX::N, PM = GM::P, PX = GX::P, TR = S::TR;
+    static_assert(S::RB == 1, "one row per workgroup");
+    const int t = threadIdx.x % TR, rb = threadIdx.x / TR;
+    const int b = blockIdx.y;
+    const int row = (int)(blockIdx.x * S::RB) + rb;
+    const bool live = row < A.nrows;
+
+    static_for<0, PX>([&](auto vI) {
+        constexpr int v = decltype(vI)::value;
+        acc[lds_pos<GX>(rb, t + v * TR, false)] = cx<R>{(R)0, (R)0};
+    });
+    row_sync<GX>(false);
+
+    constexpr int NBW = 2, NW = S::NT / 64;  // NBW rows of one group in flight per wave (16 points per lane each); NW waves
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int r = 0; r < A.nrounds; r++) {  // workgroup-uniform
+        for (int i0 = A.rstart[r]; i0 < A.rstart[r + 1]; i0 += NW) {
+            const int i = i0 + wv;  // wave-uniform
+            if (i < A.rstart[r + 1]) {
+                const int g = A.rgroup[i];
+                cx<R> xs[PM];
+                static_for<0, PM>([&](auto vI) { xs[decltype(vI)::value] = cx<R>{(R)0, (R)0}; });
+                bool anyg = false;
+                int n = A.gstart[g];
+                const int ne = A.gstart[g + 1];
+                while (n < ne) {
+                    int fs[NBW];
+                    int cnt = 0;
+                    for (; n < ne && cnt < NBW; n++) {
+                        const bool any = live && ((row - A.base0[n]) & (X - 1)) < M;
+                        if (any) fs[cnt++] = n;
+                    }
+                    if (cnt == 0) break;
+                    anyg = true;
+                    cx<R> x[NBW][PM];
+                    static_for<0, NBW>([&](auto sI) {
+                        constexpr int sl = decltype(sI)::value;
+                        if (sl < cnt) {  // wave-uniform
+                            const int nn = fs[sl];
+                            const int k = (row - A.base0[nn]) & (X - 1);
+                            const cx<R>* __restrict__ in = P.in + (long long)A.fidx[nn] * A.in_fs +
+                                                               (long long)b * A.in_bs + (long long)(live ? k : 0) * A.in_rs;
+                            static_for<0, PM>([&](auto vI) {
+                                constexpr int v = decltype(vI)::value;
+                                x[sl][v] = in[(lane + v * 64) ^ (M >> 1)];  // plain index -> centred element
+                            });
+                        }
+                    });
+                    const R lw = live ? (R)1 : (R)0;
+                    static_for<0, NBW>([&](auto sI) {
+                        constexpr int sl = decltype(sI)::value;
+                        if (sl < cnt) {
+                            static_for<0, PM>([&](auto vI) {
+                                constexpr int v = decltype(vI)::value;
+                                xs[v].x += x[sl][v].x * lw;
+                                xs[v].y += x[sl][v].y * lw;
+                            });
+                        }
+                    });
+                }
+                if (anyg) {
+                    const int sp = A.gsp1[g];
+                    fft_phases<SFCompact<GM>, R, 0>(xs, lane, wv, false, ex_m, P.tw_m, [&](int e, cx<R> v) {
+                        const int ck = e ^ (M >> 1);
+                        const int kk = (ck - sp) & (M - 1);
+                        const int dest = (kk + (X >> 1) - (M >> 1) + sp) & (X - 1);
+                        const R w = P.fn[kk];
+                        cx<R>* p = acc + lds_pos<GX>(0, dest ^ (X >> 1), false);
+                        cx<R> o = *p;
+                        o.x += v.x * w;
+                        o.y += v.y * w;
+                        *p = o;
+                    }, nullptr, P.twc_m);
+                }
+            }
+        }
+        __syncthreads();  // the next round's windows overlap this round's
+    }
+
+    cx<R> y[PX];
+    static_for<0, PX>([&](auto vI) {
+        constexpr int v = decltype(vI)::value;
+        cx<R> val = acc[lds_pos<GX>(rb, t + v * TR, false)];
+        val.y = -val.y;  // inverse transform = conj(FFT(conj(.)))
+        y[v] = val;
+    });
+    row_sync<GX>(false);
+    cx<R>* __restrict__ out = P.out + (long long)b * A.out_bs + (long long)(live ? row : 0) * A.out_rs;
+    const R* __restrict__ mask = A.mask ? P.mask + (long long)b * A.mask_bs : nullptr;
+    const int st_a = A.st_a[b];
+    const R scale = (R)1 / (R)X;
+    fft_phases<SFCompact<GX>, R, 0>(y, t, rb, false, acc, P.tw_x, [&](int e, cx<R> v) {
+        const int d = crop_index<X>(e, st_a);
+        if (d < A.xA && live) {
+            R w = scale;
+            if (mask) w *= mask[d];
+            out[d] = cx<R>{v.x * w, -v.y * w};
+        }
+    }, nullptr, P.twc_x);
+}
+
+// Register form, one wave per row (r4): the accumulator row lives in REGISTERS (swiftly_place.h), so LDS only holds ONE
+// exchange buffer per row -- used by the m-point transforms first, by the xM-point transform last -- and Fn
+// (1024-point rows: 4 waves per SIMD = 16 rows per CU, which the 8.7 KB of LDS per row allow).
+template <int LOGM, int LOGX, typename R>
+__device__ __forceinline__ void sum_finish_facets_reg(const SumFinishFacetArgs& A, const SFFacetPtrs<R>& P) {
+    using S = SFGeo<LOGM, LOGX, R>;
+    using GX = typename S::GX;
+    using GM = typename S::GM;
     constexpr bool F32 = std::is_same_v<R, float>;
     using GMC = std::conditional_t<F32, SFCompact<GM>, GM>;
     using GXC = std::conditional_t<F32, SFCompact<GX>, GX>;
-    const cx<R>* g_in = reinterpret_cast<const cx<R>*>(A.in);
-    cx<R>* g_out = reinterpret_cast<cx<R>*>(A.out);
-    const R* g_fn = reinterpret_cast<const R*>(A.fn);
-    const R* g_mask = reinterpret_cast<const R*>(A.mask);
-    const cx<R>* tw_m = reinterpret_cast<const cx<R>*>(A.tw_m);
-    const cx<R>* tw_x = reinterpret_cast<const cx<R>*>(A.tw_x);
-    const cx<R>* twc_m = F32 ? reinterpret_cast<const cx<R>*>(A.twc_m) : nullptr;
-    const cx<R>* twc_x = F32 ? reinterpret_cast<const cx<R>*>(A.twc_x) : nullptr;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    cx<R>* ex_m = reinterpret_cast<cx<R>*>(smem);
-    // (wave-parallel form: accumulator row in LDS behind the m-point exchange buffers; register form: one exchange
-    // buffer per row shared by both transforms, then the Fn table)
-    cx<R>* acc = reinterpret_cast<cx<R>*>(smem + (W::ON ? W::LDS_M : 0));
     constexpr int M = GM::N, X = GX::N, PM = GM::P, PX = GX::P, TR = S::TR;
     const int t = threadIdx.x % TR, rb = threadIdx.x / TR;
     const int b = blockIdx.y;
     const int row0 = blockIdx.x * S::RB;
     const int row = row0 + rb;
     const bool live = row < A.nrows;
-    cx<R> y[PX];  // register form: the lane's part of the accumulator row, y[v] = row[t + v * TR]
-
-    if constexpr (W::ON) {
-        static_for<0, PX>([&](auto vI) {
-            constexpr int v = decltype(vI)::value;
-            acc[lds_pos<GX>(rb, t + v * TR, false)] = cx<R>{(R)0, (R)0};
-        });
-        row_sync<GX>(false);
-    }
-
-    if constexpr (W::ON) {
-        static_assert(S::RB == 1, "one row per workgroup");
-        constexpr int NBW = 2;  // rows of one group in flight per wave (16 points per lane each)
-        const int lane = threadIdx.x & 63;
-        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        constexpr int NW = S::NT / 64;
-        for (int r = 0; r < A.nrounds; r++) {  // workgroup-uniform
-            for (int i0 = A.rstart[r]; i0 < A.rstart[r + 1]; i0 += NW) {
-                const int i = i0 + wv;  // wave-uniform
-                if (i < A.rstart[r + 1]) {
-                    const int g = A.rgroup[i];
-                    cx<R> xs[PM];
-                    static_for<0, PM>([&](auto vI) { xs[decltype(vI)::value] = cx<R>{(R)0, (R)0}; });
-                    bool anyg = false;
-                    int n = A.gstart[g];
-                    const int ne = A.gstart[g + 1];
-                    while (n < ne) {
-                        int fs[NBW];
-                        int cnt = 0;
-                        for (; n < ne && cnt < NBW; n++) {
-                            const bool any = live && ((row - A.base0[n]) & (X - 1)) < M;
-                            if (any) fs[cnt++] = n;
-                        }
-                        if (cnt == 0) break;
-                        anyg = true;
-                        cx<R> x[NBW][PM];
-                        static_for<0, NBW>([&](auto sI) {
-                            constexpr int sl = decltype(sI)::value;
-                            if (sl < cnt) {  // wave-uniform
-                                const int nn = fs[sl];
-                                const int k = (row - A.base0[nn]) & (X - 1);
-                                const cx<R>* __restrict__ in = g_in + (long long)A.fidx[nn] * A.in_fs +
-                                                                   (long long)b * A.in_bs + (long long)(live ? k : 0) * A.in_rs;
-                                static_for<0, PM>([&](auto vI) {
-                                    constexpr int v = decltype(vI)::value;
-                                    x[sl][v] = in[(lane + v * 64) ^ (M >> 1)];  // plain index -> centred element
-                                });
-                            }
-                        });
-                        const R lw = live ? (R)1 : (R)0;
-                        static_for<0, NBW>([&](auto sI) {
-                            constexpr int sl = decltype(sI)::value;
-                            if (sl < cnt) {
-                                static_for<0, PM>([&](auto vI) {
-                                    constexpr int v = decltype(vI)::value;
-                                    xs[v].x += x[sl][v].x * lw;
-                                    xs[v].y += x[sl][v].y * lw;
-                                });
-                            }
-                        });
-                    }
-                    if (anyg) {
-                        const int sp = A.gsp1[g];
-                        fft_phases<GMC, R, 0>(xs, lane, wv, false, ex_m, tw_m, [&](int e, cx<R> v) {
-                            const int ck = e ^ (M >> 1);
-                            const int kk = (ck - sp) & (M - 1);
-                            const int dest = (kk + (X >> 1) - (M >> 1) + sp) & (X - 1);
-                            const R w = g_fn[kk];
-                            cx<R>* p = acc + lds_pos<GX>(0, dest ^ (X >> 1), false);
-                            cx<R> o = *p;
-                            o.x += v.x * w;
-                            o.y += v.y * w;
-                            *p = o;
-                        }, nullptr, twc_m);
-                    }
-                }
-            }
-            __syncthreads();  // the next round's windows overlap this round's
-        }
-    } else {
 
     // Per off1 group: the rows of the group's facets whose band covers this workgroup's rows are requested SF_NB at a
     // time (a wave pays the HBM latency once per batch, not once per facet; r2: one facet at a time -- 4.5 dependent
     // round trips per row on the 3x3 cover, SQ_WAIT_ANY 58 % of the wave cycles at 12 waves per CU) and summed in
-    // registers; the sum is transformed, weighted and scattered into the accumulator row once.  (Requesting the NEXT
+    // registers; the sum is transformed, weighted and placed into the accumulator once.  (Requesting the NEXT
     // batch before the current group is transformed -- measured r3 on the 4096-point rows of the N = 32768 workload,
     // whose 8 groups per row are 8 dependent load -> transform steps: 114.5 vs 111-113 ms for the subgrid side, no
     // gain; the 4-points-per-lane m-point transforms with their 9 workgroup barriers each are the cost there.)
-    // r4: ACCUMULATOR IN REGISTERS.  Output e of the m-point transform of lane t is e = t (mod 64) (Stockham: every
-    // output of a lane is congruent to its lane index modulo the thread count), and its place in the padded row, taken
-    // at its plain inverse-transform index p = (kk - m/2 + s') mod xM, is congruent to e modulo m -- so it lands in one
-    // of lane t's OWN inputs y[v] = row[t + 64 v] of the xM-point transform, v = (e - t) / 64 + (m / 64) c with
-    // c = p / m in [0, xM / m).  The placement becomes xM / m multiply-adds per output with weights Fn[kk] * (c == c')
-    // instead of a read-modify-write of an LDS row: no accumulator row (13.3 -> 8.7 KB of LDS per row: 16 instead of
-    // 12 waves per CU), no zero fill, no final read-back, and Fn from a copy in LDS.
+    // r4: ACCUMULATOR IN REGISTERS (place_add): against a read-modify-write of an LDS row there is no accumulator row
+    // (13.3 -> 8.7 KB of LDS per row: 16 instead of 12 waves per CU), no zero fill, no final read-back, and Fn comes
+    // from a copy in LDS.
     static_assert(S::LDS_X >= S::LDS_M, "one exchange buffer per row, sized by the longer transform");
-    constexpr int RATIO = X / M;
-    static_assert(PX == PM * RATIO, "accumulator slots");
     cx<R>* ex_row = reinterpret_cast<cx<R>*>(smem) + (size_t)rb * GX::PITCH;  // this row's exchange buffer (rb = 0 addressing)
     R* fn_l = reinterpret_cast<R*>(smem + (S::LDS_X > S::LDS_M ? S::LDS_X : S::LDS_M));
-    for (int i = threadIdx.x; i < M; i += S::NT) fn_l[i] = g_fn[i];
+    for (int i = threadIdx.x; i < M; i += S::NT) fn_l[i] = P.fn[i];
+    cx<R> y[PX];  // the lane's part of the accumulator row, y[v] = row[t + v * TR]
     static_for<0, PX>([&](auto vI) { y[decltype(vI)::value] = cx<R>{(R)0, (R)0}; });
     __syncthreads();
     // (8 points per lane and 1024-point rows: two facets in flight keep the kernel at 128 VGPRs without spills)
@@ -386,7 +410,7 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX, R>::NT), (!std::is_same_v<R, flo
                     const int k = (row - A.base0[nn]) & (X - 1);
                     const bool on = live && k < M;
                     const cx<R>* __restrict__ in =
-                        g_in + (long long)A.fidx[nn] * A.in_fs + (long long)b * A.in_bs + (long long)(on ? k : 0) * A.in_rs;
+                        P.in + (long long)A.fidx[nn] * A.in_fs + (long long)b * A.in_bs + (long long)(on ? k : 0) * A.in_rs;
                     wgt[sl] = on ? (R)1 : (R)0;
                     // placed rows are indexed by kk = (centred output index - s'1) mod m of the slot the value lands in
                     const int rot = A.placed ? A.gsp1[g] : 0;
@@ -409,89 +433,58 @@ __global__ __launch_bounds__((SFGeo<LOGM, LOGX, R>::NT), (!std::is_same_v<R, flo
         }
         if (!anyg) continue;
         const int sp = A.gsp1[g];
-        if (A.placed) {  // workgroup-uniform: xs[v] = sum of the group's rows at element kk_v (loaded below in that order)
+        if (A.placed) {  // workgroup-uniform: xs[v] = sum of the group's rows at element kk_v (loaded above in that order)
             static_for<0, PM>([&](auto vI) {
                 constexpr int v = decltype(vI)::value;
-                const int ck = (t + v * TR) ^ (M >> 1);
-                const int kk = (ck - sp) & (M - 1);
-                const int p = (kk - (M >> 1) + sp) & (X - 1);
-                const int c = p >> LOGM;
-                static_for<0, RATIO>([&](auto cI) {
-                    constexpr int cc = decltype(cI)::value;
-                    const R wc = c == cc ? (R)1 : (R)0;
-                    y[v + PM * cc].x += xs[v].x * wc;
-                    y[v + PM * cc].y += xs[v].y * wc;
-                });
+                place_add<LOGM, LOGX, v>(y, (t + v * TR) ^ (M >> 1), sp, xs[v], [](int) { return (R)1; });
             });
             continue;
         }
-        fft_phases<GMC, R, 0>(xs, t, 0, false, ex_row, tw_m, [&](int e, cx<R> v, auto sI) {
-            // slot = u * RAD + r of the last phase (radix RAD = 2^LR, NB = PM / RAD blocks): e = t + TR * (u + NB * r)
-            constexpr int LR = GM::LOGN % GM::LOGP == 0 ? GM::LOGP : GM::LOGN % GM::LOGP, RAD = 1 << LR, NBL = PM / RAD;
-            constexpr int slot = (decltype(sI)::value / RAD) + NBL * (decltype(sI)::value % RAD);
-            const int ck = e ^ (M >> 1);
-            const int kk = (ck - sp) & (M - 1);
-            const int p = (kk - (M >> 1) + sp) & (X - 1);  // plain inverse-transform index of the placed element
-            const int c = p >> LOGM;
-            const R w = fn_l[kk];
-            static_for<0, RATIO>([&](auto cI) {
-                constexpr int cc = decltype(cI)::value;
-                const R wc = c == cc ? w : (R)0;
-                y[slot + PM * cc].x += v.x * wc;
-                y[slot + PM * cc].y += v.y * wc;
-            });
-        }, nullptr, twc_m);
+        fft_phases<GMC, R, 0>(xs, t, 0, false, ex_row, P.tw_m, [&](int e, cx<R> v, auto sI) {
+            place_output<GM, LOGX, decltype(sI)::value>(y, e, sp, v, fn_l);
+        }, nullptr, P.twc_m);
         row_sync<GX>(false);  // the exchange buffer is reused by the next group
     }
-    static_for<0, PX>([&](auto vI) { y[decltype(vI)::value].y = -y[decltype(vI)::value].y; });  // inverse = conj(FFT(conj(.)))
-    acc = ex_row - (size_t)rb * GX::PITCH;  // the xM-point transform exchanges through the same rows
+    conj_regs(y);
+    // the xM-point transform exchanges through the same rows, addressed by rb: the workgroup's base, derived from the
+    // row's (written as smem it compiles to other register allocations: 1 VGPR apart on four instances)
+    cx<R>* const ex = ex_row - (size_t)rb * GX::PITCH;
 
-    }  // !W::ON
-
-    if constexpr (W::ON) {
-        static_for<0, PX>([&](auto vI) {
-            constexpr int v = decltype(vI)::value;
-            cx<R> val = acc[lds_pos<GX>(rb, t + v * TR, false)];
-            val.y = -val.y;  // inverse transform = conj(FFT(conj(.)))
-            y[v] = val;
-        });
-        row_sync<GX>(false);
-    }
-    cx<R>* __restrict__ out = g_out + (long long)b * A.out_bs + (long long)(live ? row : 0) * A.out_rs;
-    const R* __restrict__ mask = A.mask ? g_mask + (long long)b * A.mask_bs : nullptr;
+    cx<R>* __restrict__ out = P.out + (long long)b * A.out_bs + (long long)(live ? row : 0) * A.out_rs;
+    const R* __restrict__ mask = A.mask ? P.mask + (long long)b * A.mask_bs : nullptr;
     const int st_a = A.st_a[b];
     const R scale = (R)1 / (R)X;
-    if constexpr (!W::ON) {
-        // r4: the mask values of the lane's PX outputs are requested together BEFORE the transform (output slot s of the
-        // last phase is element e = t + TR * (u + NB r)) instead of inside the store loop (fewer branches; measured r4,
-        // same box: 251.9 vs 253.7 us per wave for sum_finish + K5b, i.e. no difference)
-        constexpr int LRX = GX::LOGN % GX::LOGP == 0 ? GX::LOGP : GX::LOGN % GX::LOGP, RADX = 1 << LRX, NBX = PX / RADX;
-        R mw[PX];
-        static_for<0, PX>([&](auto sI) {
-            constexpr int sl = decltype(sI)::value;
-            constexpr int vi = (sl / RADX) + NBX * (sl % RADX);
-            const int d = (((t + TR * vi) ^ (X >> 1)) + st_a) & (X - 1);
-            const bool ok = d < A.xA && live;
-            mw[sl] = mask ? mask[ok ? d : 0] : (R)1;
-        });
-        fft_phases<GXC, R, 0>(y, t, rb, false, acc, tw_x, [&](int e, cx<R> v, auto sI) {
-            constexpr int sl = decltype(sI)::value;
-            const int ck = e ^ (X >> 1);
-            const int d = (ck + st_a) & (X - 1);
-            const R w = scale * mw[sl];
-            if (d < A.xA && live) out[d] = cx<R>{v.x * w, -v.y * w};
-        }, nullptr, twc_x);
-        return;
-    }
-    fft_phases<GXC, R, 0>(y, t, rb, false, acc, tw_x, [&](int e, cx<R> v) {
-        const int ck = e ^ (X >> 1);
-        const int d = (ck + st_a) & (X - 1);
-        if (d < A.xA && live) {
-            R w = scale;
-            if (mask) w *= mask[d];
-            out[d] = cx<R>{v.x * w, -v.y * w};
-        }
-    }, nullptr, twc_x);
+    // r4: the mask values of the lane's PX outputs are requested together BEFORE the transform (output s of the last
+    // phase is element t + TR * last_phase_slot(s)) instead of inside the store loop (fewer branches; measured r4, same
+    // box: 251.9 vs 253.7 us per wave for sum_finish + K5b, i.e. no difference)
+    R mw[PX];
+    static_for<0, PX>([&](auto sI) {
+        constexpr int sl = decltype(sI)::value;
+        const int d = crop_index<X>(t + TR * last_phase_slot<GX>(sl), st_a);
+        const bool ok = d < A.xA && live;
+        mw[sl] = mask ? mask[ok ? d : 0] : (R)1;
+    });
+    fft_phases<GXC, R, 0>(y, t, rb, false, ex, P.tw_x, [&](int e, cx<R> v, auto sI) {
+        const int d = crop_index<X>(e, st_a);
+        const R w = scale * mw[decltype(sI)::value];
+        if (d < A.xA && live) out[d] = cx<R>{v.x * w, -v.y * w};
+    }, nullptr, P.twc_x);
+}
+
+// (complex128: register form only; at least two waves per SIMD, i.e. up to 256 VGPRs -- the accumulator row of doubles
+// spills at 128)
+template <int LOGM, int LOGX, typename R = float>
+__global__ __launch_bounds__((SFGeo<LOGM, LOGX, R>::NT), (!std::is_same_v<R, float> ? 2 : LOGX <= 10 ? 4 : 1)) void sum_finish_facets_kernel(const SumFinishFacetArgs A) {
+    constexpr bool F32 = std::is_same_v<R, float>;
+    static_assert(F32 || !SFWide<LOGM, LOGX>::ON, "complex128: register form only");
+    using CP = const cx<R>*;
+    const SFFacetPtrs<R> P = {reinterpret_cast<CP>(A.in),   reinterpret_cast<cx<R>*>(A.out), reinterpret_cast<const R*>(A.fn),
+                              reinterpret_cast<const R*>(A.mask), reinterpret_cast<CP>(A.tw_m), reinterpret_cast<CP>(A.tw_x),
+                              F32 ? reinterpret_cast<CP>(A.twc_m) : nullptr, F32 ? reinterpret_cast<CP>(A.twc_x) : nullptr};
+    if constexpr (SFWide<LOGM, LOGX>::ON)
+        sum_finish_facets_wide<LOGM, LOGX>(A, P);
+    else
+        sum_finish_facets_reg<LOGM, LOGX, R>(A, P);
 }
 
 // ---------------------------------------------------------------------------------------------------------
