@@ -119,9 +119,12 @@ enum {
     SWIFTLY_FEATURE_GROUP_FINISH = 10,          /* wave_group_finish_pieces (dtype, n_facets): FUSED_SUBGRID in complex64 with
                                                    (m, xM) = (128, 256) or (512, 1024) and n_facets * xM / m <= 64.  The gate
                                                    the entry point refuses through */
-    SWIFTLY_FEATURE_REAL_WINDOW_ROWS = 11       /* prepare_facet_window_rows_real (dtype = the OUTPUT type), size part: the
+    SWIFTLY_FEATURE_REAL_WINDOW_ROWS = 11,      /* prepare_facet_window_rows_real (dtype = the OUTPUT type), size part: the
                                                    sizes of WINDOW_ROWS that are also sizes of REAL_FACETS in complex64.  The
                                                    gate the entry point refuses through ("real window rows: ...") */
+    SWIFTLY_FEATURE_REAL_FACETS_RFFT = 12       /* prepare_facet_band_rfft / prepare_facet_band_rows_rfft (dtype = the OUTPUT
+                                                   type), size part: the sizes of REAL_FACETS with yN_size 32768.  The gate both
+                                                   entry points refuse through ("real facets, half-length: ...") */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -384,6 +387,24 @@ int swiftly_hip_prepare_facet_band_real(swiftly_hip_t* h, int dtype, const void*
                                         int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                         int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream);
 int swiftly_hip_prepare_facet_band_rows_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                             int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                             int64_t band_start, int64_t band_len, int64_t other_axis_size,
+                                             int64_t other_axis_row0, void* stream);
+/* K1 of a real-valued facet as a HALF-LENGTH transform: the argument lists and the stored quantity of the two _real entry
+ * points above (`in` float32, in_row_stride in reals, `dtype` the OUTPUT type; inverse-transform convention of prepare_facet,
+ * 1 / yN_size, the folded window of the other axis; parity-split band), computed by ONE workgroup per row from one
+ * yN_size / 2-point complex transform of z[n] = x[2n] + i x[2n+1] and the recombination
+ * S[k] = E[k] + W^k O[k], S[k + yN_size/2] = E[k] - W^k O[k] (csrc/swiftly_rowreal.h).  The values ROUND DIFFERENTLY from
+ * those of the _real entry points (same bound against the exact transform, not the same bits), which is why this is a door
+ * of its own that nothing else routes to.  Sizes: SWIFTLY_FEATURE_REAL_FACETS_RFFT (REAL_FACETS with yN_size 32768).  Per
+ * call the adjacent reals are fetched with 8-byte loads, so an odd facet_size, an odd position of the facet in the padded
+ * row (facet_off + yN_size/2 - facet_size/2 odd), an odd in_row_stride or an `in` that is not 8-byte aligned is REFUSED with
+ * SWIFTLY_ERR_UNSUPPORTED ("real facets, half-length: ..."): nothing is written and no other kernel runs instead.  Parameter
+ * errors as in the _real entry points.  swiftly_hip_last_band_instance does not count these calls. */
+int swiftly_hip_prepare_facet_band_rfft(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                        int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                        int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream);
+int swiftly_hip_prepare_facet_band_rows_rfft(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                              int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                              int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                              int64_t other_axis_row0, void* stream);

@@ -1401,6 +1401,64 @@ int swiftly_hip_prepare_facet_band_real(swiftly_hip_t* h, int dtype, const void*
                                                     band_start, band_len, fold_other_axis_window ? rows : 0, 0, stream);
 }
 
+// K1 of a real-valued facet as a half-length transform (swiftly_rowreal.h): its own kernel and its own refusals -- a call the
+// kernel does not take is refused before anything is written, never handed to the band row kernel
+int swiftly_hip_prepare_facet_band_rows_rfft(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                             int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                             int64_t band_start, int64_t band_len, int64_t other_axis_size,
+                                             int64_t other_axis_row0, void* stream) {
+    const int fold_other_axis_window = other_axis_size > 0;
+    if (!h || !in || !out) return fail(SWIFTLY_ERR_PARAM, "null argument");
+    if (fold_other_axis_window && (other_axis_row0 < 0 || other_axis_row0 + rows > other_axis_size))
+        return fail(SWIFTLY_ERR_PARAM, "rows [%lld, +%lld) are not inside a facet of %lld rows", (long long)other_axis_row0,
+                    (long long)rows, (long long)other_axis_size);
+    DeviceGuard device_guard_(h->device);
+    CHECK_DTYPE();
+    if (const std::string why = why_not_real_facets_rfft(*h, dtype); !why.empty())
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: %s", why.c_str());
+    CHECK_FACET_SIZE();
+    if (rows < 0 || rows > 0x7fffffff) return fail(SWIFTLY_ERR_PARAM, "bad row count");
+    CHECK_BAND();
+    if (fold_other_axis_window && (other_axis_size <= 0 || other_axis_size >= h->yN))
+        return fail(SWIFTLY_ERR_PARAM, "other-axis facet size %lld must be in [1, yN_size - 1]", (long long)other_axis_size);
+    const Map facet = facet_in_padded_facet(*h, facet_size, facet_off);
+    // two adjacent reals per 8-byte load: z[n] = (x[2n], x[2n+1]) must be one aligned pair of every row
+    if (facet_size & 1)
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: odd facet size %lld", (long long)facet_size);
+    if (facet.a & 1)
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: the facet starts at an odd index of the "
+                    "padded row (load offset %d, facet offset %lld)", facet.a, (long long)facet_off);
+    if (in_row_stride & 1)
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: odd row stride %lld", (long long)in_row_stride);
+    if (reinterpret_cast<uintptr_t>(in) & 7)
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: input is not 8-byte aligned");
+    if (rows == 0) return 0;
+    RowPassArgs r;
+    std::memset(&r, 0, sizeof r);
+    r.in = (const cx<float>*)in; r.out = (cx<float>*)out;
+    r.in_pitch = in_row_stride; r.out_pitch = out_row_stride;
+    r.in_real = 1;
+    r.nrows = (int)rows;
+    r.ld_a = facet.a; r.ld_len = facet.len; r.ld_c = facet.c; r.ld_mod = facet.mod;
+    r.ld_win = h->invp_f + facet_lo(*h, facet_size);
+    r.st_len = (int)h->yN; r.st_mod = (int)h->yN;
+    r.scale = (float)(1.0 / (double)h->yN);
+    r.conj_ld = r.conj_st = 1;
+    r.row_win = fold_other_axis_window ? h->invp_f + (facet_lo(*h, other_axis_size) + (int)other_axis_row0) : nullptr;
+    r.band_start = (int)band_start; r.band_len = (int)band_len; r.band_half = (int)band_half_columns(band_len);
+    r.twc = compact_twiddles(h, 14, 5);
+    const cx<float>* twh = twiddles<float>(h, h->log_yN - 1);
+    const cx<float>* twf = twiddles<float>(h, h->log_yN);
+    if (!twh || !twf || !r.twc) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
+    return launch_status(launch_row_real_band(r, twh, twf, (hipStream_t)stream));
+}
+int swiftly_hip_prepare_facet_band_rfft(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                        int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                        int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream) {
+    return swiftly_hip_prepare_facet_band_rows_rfft(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
+                                                    band_start, band_len, fold_other_axis_window ? rows : 0, 0, stream);
+}
+
 // (r6, axis-1-first pipeline) prepare_facet_band_rows that finishes the contiguous axis COMPLETELY inside K1: one persistent
 // workgroup per CU owns whole rows (both output parities; swiftly_rowwhole.h), stages the band of a row in LDS and stores, for every
 // window w, what swiftly_hip_finish_axis1_rows would produce for wave w from that band:

@@ -26,6 +26,7 @@
 #include "swiftly_geometry.h"
 #include "swiftly_launch.h"
 #include "swiftly_rowpass.h"
+#include "swiftly_rowreal.h"
 #include "swiftly_sumfinish.h"
 #include "swiftly_rows.h"
 #include "swiftly_rowslong.h"

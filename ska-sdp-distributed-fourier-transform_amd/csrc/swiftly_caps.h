@@ -268,6 +268,16 @@ inline std::string why_not_real_facets_out(const Sizes& s, int dtype) {
     if (s.log_yN < 0) return reason("real facet output: yN %lld is Q * 2^k: the radix-Q pass has no real store", (long long)s.yN);
     return {};
 }
+// real-valued facets through the half-length K1 (prepare_facet_band_rfft / prepare_facet_band_rows_rfft, swiftly_rowreal.h):
+// the sizes of the real-load K1 at which the one-workgroup 16384-point form exists (the per-call conditions -- even facet
+// size, position and row stride, an 8-byte-aligned input -- are the entry point's)
+constexpr int kRealRfftLogYN = 15;
+inline std::string why_not_real_facets_rfft(const Sizes& s, int dtype) {
+    if (std::string why = why_not_real_facets(s, dtype); !why.empty()) return "real facets, half-length: " + why;
+    if (s.log_yN != kRealRfftLogYN)
+        return reason("real facets, half-length: needs yN %d; got yN %lld", 1 << kRealRfftLogYN, (long long)s.yN);
+    return {};
+}
 // size part of prepare_facet_window_rows (the band, the facets and the windows are per call)
 inline std::string why_not_window_rows(const Sizes& s) {
     if (s.log_yN == kWindowRowsLogYN && s.log_m == kWindowRowsLogM && s.xM <= (int64_t(1) << kPlacedMaxLogXM)) return {};

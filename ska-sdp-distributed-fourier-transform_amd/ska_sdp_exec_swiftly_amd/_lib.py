@@ -18,7 +18,7 @@ ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
 # swiftly_hip_supports / swiftly_hip_limit (include/swiftly_hip.h)
 (FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
  FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE, FEATURE_REAL_FACETS,
- FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH, FEATURE_REAL_WINDOW_ROWS) = range(12)
+ FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH, FEATURE_REAL_WINDOW_ROWS, FEATURE_REAL_FACETS_RFFT) = range(13)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None
@@ -116,6 +116,11 @@ def _declare(lib):
     lib.swiftly_hip_prepare_facet_band_real.argtypes = list(lib.swiftly_hip_prepare_facet_band.argtypes)
     lib.swiftly_hip_prepare_facet_band_rows_real.restype = c_int
     lib.swiftly_hip_prepare_facet_band_rows_real.argtypes = list(lib.swiftly_hip_prepare_facet_band_rows.argtypes)
+    # ... as ONE half-length transform per row (same arguments; a door of its own: rounds differently, refuses odd layouts)
+    lib.swiftly_hip_prepare_facet_band_rfft.restype = c_int
+    lib.swiftly_hip_prepare_facet_band_rfft.argtypes = list(lib.swiftly_hip_prepare_facet_band.argtypes)
+    lib.swiftly_hip_prepare_facet_band_rows_rfft.restype = c_int
+    lib.swiftly_hip_prepare_facet_band_rows_rfft.argtypes = list(lib.swiftly_hip_prepare_facet_band_rows.argtypes)
     lib.swiftly_hip_prepare_facet_columns.restype = c_int
     lib.swiftly_hip_prepare_facet_columns.argtypes = [vp, c_int, vp, i64, i64, i64, i64, pi64, i64, i64, i64, vp, i64, i64, vp, vp]
     lib.swiftly_hip_transform_contributions.restype = c_int

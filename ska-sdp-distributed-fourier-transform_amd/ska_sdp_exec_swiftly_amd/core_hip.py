@@ -588,6 +588,13 @@ class SwiftlyCoreHip:
         False ``_lib.last_error()`` says why."""
         return self._supports(_lib.FEATURE_REAL_FACETS, _torch().complex64)
 
+    def supports_real_facets_rfft(self):
+        """True when the half-length K1 of real-valued facets exists for these sizes (``prepare_facet_band(...,
+        half_length=True)``; ``swiftly_hip_prepare_facet_band_rfft``): :py:meth:`supports_real_facets` at ``yN_size`` 32768.
+        Per call it also needs an even facet size, an even position of the facet in the padded row, an even row pitch and
+        8-byte-aligned rows.  After a False ``_lib.last_error()`` says why."""
+        return self._supports(_lib.FEATURE_REAL_FACETS_RFFT, _torch().complex64)
+
     def _real_rows_match_promoted(self, facet_size):
         """Does the real-load K1 give a row of ``facet_size`` reals bit for bit the values of the promoted row?  Not at
         ``yN_size`` 32768 when the row can cover more than 24 of the 32 load segments of 1024 points (``facet_size`` above
@@ -614,7 +621,8 @@ class SwiftlyCoreHip:
         """physical columns of a band buffer"""
         return int(self._lib.swiftly_hip_band_columns_for(self._handle, int(band[1])))
 
-    def prepare_facet_band(self, facet, facet_off, band, out=None, fold_other_axis_window=True, rows_of=None):
+    def prepare_facet_band(self, facet, facet_off, band, out=None, fold_other_axis_window=True, rows_of=None,
+                           half_length=False):
         """K1 (contiguous axis first): ``prepare_facet(facet, facet_off, axis=1)`` for every row of a row-major
         device facet, keeping only the band of output columns (parity-split layout, see include/swiftly_hip.h),
         times the 1/PSWF window of axis 0 when ``fold_other_axis_window``.  ``rows_of=(size, row0)``: ``facet`` is
@@ -623,20 +631,30 @@ class SwiftlyCoreHip:
 
         A real-valued facet may be passed as a float32 tensor where :py:meth:`supports_real_facets` says so: the kernel
         loads the reals and the complex64 output holds the values the promoted facet gives (``NotImplementedError`` with
-        the library's reason elsewhere)."""
+        the library's reason elsewhere).
+
+        ``half_length=True`` (float32 facets only, :py:meth:`supports_real_facets_rfft`): every row through ONE half-length
+        transform (``swiftly_hip_prepare_facet_band_rfft``) -- the same quantity within the same bound, not the bits of
+        the promoted facet.  An unsupported configuration or call (odd facet size, position or pitch, rows not 8-byte
+        aligned) raises ``NotImplementedError``; nothing else runs in its place."""
         torch = _torch()
         if facet.dim() != 2 or facet.stride(1) != 1:
             raise ValueError("prepare_facet_band needs a row-major 2-D device tensor")
         if facet.dtype not in (torch.complex64, torch.complex128, torch.float32):
             raise ValueError(f"prepare_facet_band takes complex64, complex128 or float32 facets, not {facet.dtype}")
         real = facet.dtype == torch.float32
-        if real and self.supports_real_facets() and not self._real_rows_match_promoted(facet.shape[1]):
+        if half_length and not real:
+            raise ValueError(f"prepare_facet_band(half_length=True) takes float32 facets, not {facet.dtype}")
+        if real and not half_length and self.supports_real_facets() and not self._real_rows_match_promoted(facet.shape[1]):
             facet, real = facet.to(torch.complex64), False  # (keeps the values of the promoted facet: see there)
         out_dtype = torch.complex64 if real else facet.dtype
         code = _lib.C64 if real else self._code(facet)
         lib = self._lib
-        band_rows = lib.swiftly_hip_prepare_facet_band_rows_real if real else lib.swiftly_hip_prepare_facet_band_rows
-        band_whole = lib.swiftly_hip_prepare_facet_band_real if real else lib.swiftly_hip_prepare_facet_band
+        if half_length:
+            band_rows, band_whole = lib.swiftly_hip_prepare_facet_band_rows_rfft, lib.swiftly_hip_prepare_facet_band_rfft
+        else:
+            band_rows = lib.swiftly_hip_prepare_facet_band_rows_real if real else lib.swiftly_hip_prepare_facet_band_rows
+            band_whole = lib.swiftly_hip_prepare_facet_band_real if real else lib.swiftly_hip_prepare_facet_band
         ncols = self.band_columns(band)
         if out is None:
             out = torch.empty((facet.shape[0], ncols), dtype=out_dtype, device=self._device)

@@ -60,14 +60,24 @@ class SwiftlyForward(WavePrefetch):
         are not 8-byte aligned at an even pitch under the accurate order, the multi-GPU classes) the facets are promoted as
         before and :py:attr:`facet_dtype` says complex64.  The results are those of the promoted facets bit for bit.
         Any other value: ``ValueError``
+    :param half_length_k1: ``True`` (with ``facet_dtype=float32``, ``ValueError`` without): K1 of the real facets as ONE
+        half-length transform per row (``core.prepare_facet_band(..., half_length=True)``) where that form exists
+        (``core.supports_real_facets_rfft()``: ``yN_size`` 32768) and every facet can be loaded as pairs -- an even facet
+        size, even positions in the padded row, device rows 8-byte aligned at an even pitch -- in the modes that store the
+        band (axis-1-first mode 2 keeps its window-rows K1).  The results are those of the promoted facets within the same
+        bound, not bit for bit; such facets stay float32 whatever their size.  Where the form is not available the object
+        runs exactly what it runs without the keyword; :py:attr:`half_length_k1` says which happened
     """
 
     # pylint: disable=too-many-arguments,too-many-instance-attributes
     def __init__(
         self, swiftly_config, facet_tasks, lru_forward=1, queue_size=20, client=None, subgrid_configs=None,
-        wave_axis=None, delayed=False, facet_dtype=None,
+        wave_axis=None, delayed=False, facet_dtype=None, half_length_k1=False,
     ):
         self._facet_dtype_asked = self._parse_facet_dtype(facet_dtype)
+        if half_length_k1 and self._facet_dtype_asked is None:
+            raise ValueError("half_length_k1=True needs facet_dtype=float32")
+        self._half_length_asked, self._half_length = bool(half_length_k1), False
         WavePrefetch.__init__(self)
         self.delayed = bool(delayed)  # hand out DeviceTask handles instead of bare device tensors
         facet_tasks = [(cfg, _unwrap(data)) for cfg, data in facet_tasks]
@@ -131,7 +141,8 @@ class SwiftlyForward(WavePrefetch):
         self._result_budget = int(float(os.environ.get("SWIFTLY_RESULT_CACHE_GB", "16")) * 2**30)
         # float32 facets: kept as they are when this object's K1 loads reals, promoted to complex64 otherwise -- decided
         # before the first upload
-        self._ingest.settle(self._keep_real_facets and self._k1_loads_reals())
+        self._half_length = self._keep_real_facets and self._k1_half_length()
+        self._ingest.settle(self._half_length or (self._keep_real_facets and self._k1_loads_reals()))
         self._ingest.prefetch(0)
 
     @property
@@ -139,6 +150,30 @@ class SwiftlyForward(WavePrefetch):
         """dtype of the facets as they are resident: ``torch.float32`` when real-valued facets were kept real, else
         :py:attr:`dtype` (the complex dtype everything downstream of K1 computes in)"""
         return _torch().float32 if self._ingest.real else self.dtype
+
+    @property
+    def half_length_k1(self):
+        """does K1 of this object run the half-length transform of real rows (the ``half_length_k1`` keyword, where the form
+        exists and every facet can be loaded as pairs)?"""
+        return self._half_length
+
+    def _k1_half_length(self):
+        """would K1 of this object run the half-length form?  The caller asked, every facet is float32, the object stores
+        the band (``wave_axis == 1``, not axis-1-first mode 2), the library has the form for these sizes and would refuse
+        none of the facets: even size, even position in the padded row, device rows 8-byte aligned at an even pitch."""
+        core = self.core
+        if not (self._half_length_asked and self._ingest.all_float32 and self.wave_axis == 1 and core.supports_real_facets_rfft()):
+            return False
+        band = core.band_for_offsets([sg.off1 for sg in self._plan]) if self._plan is not None else (0, core.yN_size)
+        if 2 in (self._axis1_mode_for(band, real=False), self._axis1_mode_for(band, real=True)):
+            return False
+        yN = core.yN_size
+        even = all(info[1][1] % 2 == 0 and (int(cfg.off1) + yN // 2 - info[1][1] // 2) % 2 == 0
+                   for info, cfg in zip(self._facet_info, self.facet_configs))
+        # (device facets are read in place; uploads are contiguous)
+        aligned = all(ten is None or ten.device != core.device or (ten.stride(0) % 2 == 0 and ten.data_ptr() % 8 == 0)
+                      for ten in self._ingest.tensors)
+        return even and aligned
 
     @staticmethod
     def _parse_facet_dtype(facet_dtype):
@@ -507,7 +542,7 @@ class SwiftlyForward(WavePrefetch):
                 if mode == 2:
                     core.prepare_facet_window_rows(data, cfg.off1, self._band, starts, bands[j])
                 else:
-                    core.prepare_facet_band(data, cfg.off1, self._band, out=bands[j])
+                    core.prepare_facet_band(data, cfg.off1, self._band, out=bands[j], half_length=self._half_length)
                 if timer is not None:
                     timer.stop("K1_full_facet_transform", t0)
                 self._ingest.prefetch(j + 1)
