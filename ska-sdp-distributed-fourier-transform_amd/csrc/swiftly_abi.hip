@@ -496,7 +496,7 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
     if (!r.tw) return false;
     r.scale = a.scale; r.conj_ld = a.conj_ld; r.conj_st = a.conj_st; r.accumulate = a.accumulate;
     const int mode = ident_st ? 0 : (ident_ld ? 1 : 2);
-    if (a.real_in) {  // real input: 8192-point rows of the plain band layout only (longer ones: prepare_facet_band_rows_impl)
+    if (a.real_in) {  // real input: 8192-point rows of the plain band layout only (longer ones: prepare_facet_k1)
         if (logn != kRowPassMinLog || mode != 0) return false;
         *rc_out = launch_status(launch_row_pass(logn, mode, r, st));
         return true;
@@ -1281,22 +1281,28 @@ int swiftly_hip_finish_facet(swiftly_hip_t* h, int dtype, const void* in, int64_
                                           mask, 1, 0, 0, nullptr, 0, stream);
 }
 
-int swiftly_hip_prepare_facet_band(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
-                                   int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
-                                   int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream) {
-    return swiftly_hip_prepare_facet_band_rows(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
-                                               band_start, band_len, fold_other_axis_window ? rows : 0, 0, stream);
-}
-
-// prepare_facet_band for the rows [other_axis_row0, other_axis_row0 + rows) of a facet whose other axis has
-// other_axis_size pixels: the folded window of the other axis is that facet's, not the one of a `rows`-pixel facet
-// (cooperative facets of the multi-GPU pass: every rank transforms a block of rows of the same facet);
-// other_axis_size = 0: no window of the other axis.
-static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
-                                        int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
-                                        int64_t band_start, int64_t band_len, int64_t other_axis_size,
-                                        int64_t other_axis_row0, const int32_t* win_d, int64_t nwin, int64_t win_full,
-                                        void* stream, bool real_in = false) {
+// The seven K1 entry points below are one implementation: prepare_facet_band for the rows [other_axis_row0,
+// other_axis_row0 + rows) of a facet whose other axis has other_axis_size pixels -- the folded window of the other axis is
+// that facet's, not the one of a `rows`-pixel facet (cooperative facets of the multi-GPU pass: every rank transforms a block
+// of rows of the same facet); other_axis_size = 0: no window of the other axis.  The forms differ in the capability rule they
+// consult, the window fields and the launcher; the real forms read float32 rows (in_row_stride counts reals, dtype = the
+// output type).
+enum class K1Form {
+    Band,            // the band row kernel (or, for short rows and complex128, the generic contiguous-axis prepare_facet)
+    RealBand,        // ... loading float32 rows: SWIFTLY_FEATURE_REAL_FACETS
+    HalfLengthBand,  // one half-length transform per real row (swiftly_rowreal.h), SWIFTLY_FEATURE_REAL_FACETS_RFFT: its own
+                     // kernel and its own refusals -- a call the kernel does not take is refused before anything is written,
+                     // never handed to the band row kernel
+    WindowRows,      // the whole-row kernel storing complete window rows (swiftly_rowwhole.h)
+    RealWindowRows,  // ... loading float32 rows: SWIFTLY_FEATURE_REAL_WINDOW_ROWS
+};
+static int prepare_facet_k1(K1Form form, swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                            int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off, int64_t band_start,
+                            int64_t band_len, int64_t other_axis_size, int64_t other_axis_row0, void* stream,
+                            const int32_t* win_d = nullptr, int64_t nwin = 0, int64_t win_stride = 0) {
+    const bool half = form == K1Form::HalfLengthBand;
+    const bool windows = form == K1Form::WindowRows || form == K1Form::RealWindowRows;
+    const bool real_in = form != K1Form::Band && form != K1Form::WindowRows;
     const int fold_other_axis_window = other_axis_size > 0;
     if (!h || !in || !out) return fail(SWIFTLY_ERR_PARAM, "null argument");
     if (fold_other_axis_window && (other_axis_row0 < 0 || other_axis_row0 + rows > other_axis_size))
@@ -1304,12 +1310,13 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
                     (long long)rows, (long long)other_axis_size);
     DeviceGuard device_guard_(h->device);
     CHECK_DTYPE();
-    if (real_in && win_d) {  // float32 rows into the window-rows store: SWIFTLY_FEATURE_REAL_WINDOW_ROWS
-        if (const std::string why = why_not_real_window_rows(*h, dtype); !why.empty())
-            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_window_rows_real: %s", why.c_str());
-    } else if (real_in) {  // float32 rows: the capability rule of SWIFTLY_FEATURE_REAL_FACETS
-        if (const std::string why = why_not_real_facets(*h, dtype); !why.empty())
-            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_real: %s", why.c_str());
+    if (real_in) {  // float32 rows: the capability rule of the form's feature
+        const std::string why = form == K1Form::RealWindowRows ? why_not_real_window_rows(*h, dtype)
+                                : half                         ? why_not_real_facets_rfft(*h, dtype)
+                                                               : why_not_real_facets(*h, dtype);
+        if (!why.empty())
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "%s: %s", form == K1Form::RealWindowRows ? "prepare_facet_window_rows_real"
+                        : half ? "prepare_facet_band_rfft" : "prepare_facet_band_real", why.c_str());
     }
     CHECK_FACET_SIZE();
     const int yN = (int)h->yN;
@@ -1320,7 +1327,7 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: complex128 needs a power-of-two yN_size of 8 .. 32768, got %d", yN);
         if (band_start != 0 || band_len != yN)
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: complex128 keeps the whole padded axis (band must be (0, yN_size))");
-        if (win_d) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_window_rows: complex64 only");
+        if (windows) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_window_rows: complex64 only");
         if (rows < 0 || rows > 0x7fffffff) return fail(SWIFTLY_ERR_PARAM, "bad row count");
         if (fold_other_axis_window && (other_axis_row0 != 0 || other_axis_size != rows))
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rows: complex128 has no row blocks");
@@ -1335,8 +1342,20 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
     CHECK_BAND();
     if (fold_other_axis_window && (other_axis_size <= 0 || other_axis_size >= h->yN))
         return fail(SWIFTLY_ERR_PARAM, "other-axis facet size %lld must be in [1, yN_size - 1]", (long long)other_axis_size);
+    const Map facet = facet_in_padded_facet(*h, facet_size, facet_off);
+    if (half) {  // two adjacent reals per 8-byte load: z[n] = (x[2n], x[2n+1]) must be one aligned pair of every row
+        if (facet_size & 1)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: odd facet size %lld", (long long)facet_size);
+        if (facet.a & 1)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: the facet starts at an odd index of the "
+                        "padded row (load offset %d, facet offset %lld)", facet.a, (long long)facet_off);
+        if (in_row_stride & 1)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: odd row stride %lld", (long long)in_row_stride);
+        if (reinterpret_cast<uintptr_t>(in) & 7)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: input is not 8-byte aligned");
+    }
     if (rows == 0) return 0;
-    if (!band_is_split(h)) {
+    if (!band_is_split(h)) {  // (never the half-length form: its capability rule needs yN_size 32768)
         // short rows: the generic contiguous-axis prepare_facet, whole padded axis, plain column order
         if (band_start != 0 || band_len != yN)
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: yN_size %d keeps the whole padded axis (band must be (0, yN_size))", yN);
@@ -1345,7 +1364,6 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
         return do_prepare_facet<float>(h, in, rows, facet_size, in_row_stride, 1, out, out_row_stride, 1, facet_off, INT64_MIN,
                                        nullptr, nullptr, fold_other_axis_window, 0, (hipStream_t)stream, real_in);
     }
-    const Map facet = facet_in_padded_facet(*h, facet_size, facet_off);
     RowPassArgs r;
     std::memset(&r, 0, sizeof r);
     r.in = (const cx<float>*)in; r.out = (cx<float>*)out;
@@ -1359,12 +1377,14 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
     r.conj_ld = r.conj_st = 1;
     r.row_win = fold_other_axis_window ? h->invp_f + (facet_lo(*h, other_axis_size) + (int)other_axis_row0) : nullptr;
     r.band_start = (int)band_start; r.band_len = (int)band_len; r.band_half = (int)band_half_columns(band_len);
+    if (half) r.twc = compact_twiddles(h, 14, 5);
     const cx<float>* twh = twiddles<float>(h, h->log_yN - 1);
     const cx<float>* twf = twiddles<float>(h, h->log_yN);
-    if (!twh || !twf) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
-    if (win_d && win_full) {  // complete window rows (whole-row kernel)
+    if (!twh || !twf || (half && !r.twc)) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
+    if (half) return launch_status(launch_row_real_band(r, twh, twf, (hipStream_t)stream));
+    if (windows) {  // complete window rows (whole-row kernel)
         r.win_full = 1;
-        r.win_pitch = win_full;  // (the flag carries the window stride)
+        r.win_pitch = win_stride;
         r.win_d = win_d; r.nwin = (int)nwin; r.win_logm = h->log_m;
         r.win_sp = pmod(facet_shift(*h, facet_off), h->m);
         r.win_fn = h->fn_f;
@@ -1379,20 +1399,26 @@ static int prepare_facet_band_rows_impl(swiftly_hip_t* h, int dtype, const void*
     return launch_status(e);
 }
 
+// the entry points: every band form for a row block (`_rows`) and for a whole facet (the block that is all of its rows)
 int swiftly_hip_prepare_facet_band_rows(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                         int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                         int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                         int64_t other_axis_row0, void* stream) {
-    return prepare_facet_band_rows_impl(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
-                                        band_len, other_axis_size, other_axis_row0, nullptr, 0, 0, stream);
+    return prepare_facet_k1(K1Form::Band, h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
+                            band_start, band_len, other_axis_size, other_axis_row0, stream);
 }
-
+int swiftly_hip_prepare_facet_band(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                   int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                   int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream) {
+    return swiftly_hip_prepare_facet_band_rows(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
+                                               band_start, band_len, fold_other_axis_window ? rows : 0, 0, stream);
+}
 int swiftly_hip_prepare_facet_band_rows_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                              int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                              int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                              int64_t other_axis_row0, void* stream) {
-    return prepare_facet_band_rows_impl(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
-                                        band_len, other_axis_size, other_axis_row0, nullptr, 0, 0, stream, true);
+    return prepare_facet_k1(K1Form::RealBand, h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
+                            band_start, band_len, other_axis_size, other_axis_row0, stream);
 }
 int swiftly_hip_prepare_facet_band_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                         int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
@@ -1400,57 +1426,12 @@ int swiftly_hip_prepare_facet_band_real(swiftly_hip_t* h, int dtype, const void*
     return swiftly_hip_prepare_facet_band_rows_real(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
                                                     band_start, band_len, fold_other_axis_window ? rows : 0, 0, stream);
 }
-
-// K1 of a real-valued facet as a half-length transform (swiftly_rowreal.h): its own kernel and its own refusals -- a call the
-// kernel does not take is refused before anything is written, never handed to the band row kernel
 int swiftly_hip_prepare_facet_band_rows_rfft(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                              int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                              int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                              int64_t other_axis_row0, void* stream) {
-    const int fold_other_axis_window = other_axis_size > 0;
-    if (!h || !in || !out) return fail(SWIFTLY_ERR_PARAM, "null argument");
-    if (fold_other_axis_window && (other_axis_row0 < 0 || other_axis_row0 + rows > other_axis_size))
-        return fail(SWIFTLY_ERR_PARAM, "rows [%lld, +%lld) are not inside a facet of %lld rows", (long long)other_axis_row0,
-                    (long long)rows, (long long)other_axis_size);
-    DeviceGuard device_guard_(h->device);
-    CHECK_DTYPE();
-    if (const std::string why = why_not_real_facets_rfft(*h, dtype); !why.empty())
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: %s", why.c_str());
-    CHECK_FACET_SIZE();
-    if (rows < 0 || rows > 0x7fffffff) return fail(SWIFTLY_ERR_PARAM, "bad row count");
-    CHECK_BAND();
-    if (fold_other_axis_window && (other_axis_size <= 0 || other_axis_size >= h->yN))
-        return fail(SWIFTLY_ERR_PARAM, "other-axis facet size %lld must be in [1, yN_size - 1]", (long long)other_axis_size);
-    const Map facet = facet_in_padded_facet(*h, facet_size, facet_off);
-    // two adjacent reals per 8-byte load: z[n] = (x[2n], x[2n+1]) must be one aligned pair of every row
-    if (facet_size & 1)
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: odd facet size %lld", (long long)facet_size);
-    if (facet.a & 1)
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: the facet starts at an odd index of the "
-                    "padded row (load offset %d, facet offset %lld)", facet.a, (long long)facet_off);
-    if (in_row_stride & 1)
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: odd row stride %lld", (long long)in_row_stride);
-    if (reinterpret_cast<uintptr_t>(in) & 7)
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: input is not 8-byte aligned");
-    if (rows == 0) return 0;
-    RowPassArgs r;
-    std::memset(&r, 0, sizeof r);
-    r.in = (const cx<float>*)in; r.out = (cx<float>*)out;
-    r.in_pitch = in_row_stride; r.out_pitch = out_row_stride;
-    r.in_real = 1;
-    r.nrows = (int)rows;
-    r.ld_a = facet.a; r.ld_len = facet.len; r.ld_c = facet.c; r.ld_mod = facet.mod;
-    r.ld_win = h->invp_f + facet_lo(*h, facet_size);
-    r.st_len = (int)h->yN; r.st_mod = (int)h->yN;
-    r.scale = (float)(1.0 / (double)h->yN);
-    r.conj_ld = r.conj_st = 1;
-    r.row_win = fold_other_axis_window ? h->invp_f + (facet_lo(*h, other_axis_size) + (int)other_axis_row0) : nullptr;
-    r.band_start = (int)band_start; r.band_len = (int)band_len; r.band_half = (int)band_half_columns(band_len);
-    r.twc = compact_twiddles(h, 14, 5);
-    const cx<float>* twh = twiddles<float>(h, h->log_yN - 1);
-    const cx<float>* twf = twiddles<float>(h, h->log_yN);
-    if (!twh || !twf || !r.twc) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
-    return launch_status(launch_row_real_band(r, twh, twf, (hipStream_t)stream));
+    return prepare_facet_k1(K1Form::HalfLengthBand, h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
+                            band_start, band_len, other_axis_size, other_axis_row0, stream);
 }
 int swiftly_hip_prepare_facet_band_rfft(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                         int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
@@ -1463,34 +1444,37 @@ int swiftly_hip_prepare_facet_band_rfft(swiftly_hip_t* h, int dtype, const void*
 // workgroup per CU owns whole rows (both output parities; swiftly_rowwhole.h), stages the band of a row in LDS and stores, for every
 // window w, what swiftly_hip_finish_axis1_rows would produce for wave w from that band:
 // out[row][w*m ..] = parity-split window band of  Fn[k] cfft_m(window w)[(k + s'1) mod m].
+static int prepare_facet_window_rows(K1Form form, const char* name, swiftly_hip_t* h, int dtype, const void* in, int64_t rows,
+                                     int64_t facet_size, int64_t in_row_stride, void* out, int64_t out_row_stride,
+                                     int64_t facet_off, int64_t band_start, int64_t band_len, int64_t other_axis_size,
+                                     int64_t other_axis_row0, const int32_t* window_starts, int64_t nwindows,
+                                     int64_t out_window_stride, void* stream) {
+    if (!window_starts || nwindows <= 0) return fail(SWIFTLY_ERR_PARAM, "%s: no windows", name);
+    if (h && (out_window_stride < h->m || out_row_stride < h->m ||
+              (out_window_stride < rows * out_row_stride && out_row_stride < nwindows * out_window_stride)))
+        return fail(SWIFTLY_ERR_PARAM, "%s: the window rows of the output overlap (row stride %lld, window stride %lld)", name,
+                    (long long)out_row_stride, (long long)out_window_stride);
+    return prepare_facet_k1(form, h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
+                            band_len, other_axis_size, other_axis_row0, stream, window_starts, nwindows, out_window_stride);
+}
 int swiftly_hip_prepare_facet_window_rows(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                           int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                           int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                           int64_t other_axis_row0, const int32_t* window_starts, int64_t nwindows,
                                           int64_t out_window_stride, void* stream) {
-    if (!window_starts || nwindows <= 0) return fail(SWIFTLY_ERR_PARAM, "prepare_facet_window_rows: no windows");
-    if (h && (out_window_stride < h->m || out_row_stride < h->m ||
-              (out_window_stride < rows * out_row_stride && out_row_stride < nwindows * out_window_stride)))
-        return fail(SWIFTLY_ERR_PARAM, "prepare_facet_window_rows: the window rows of the output overlap (row stride %lld, window stride %lld)",
-                    (long long)out_row_stride, (long long)out_window_stride);
-    return prepare_facet_band_rows_impl(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
-                                        band_len, other_axis_size, other_axis_row0, window_starts, nwindows, out_window_stride, stream);
+    return prepare_facet_window_rows(K1Form::WindowRows, "prepare_facet_window_rows", h, dtype, in, rows, facet_size,
+                                     in_row_stride, out, out_row_stride, facet_off, band_start, band_len, other_axis_size,
+                                     other_axis_row0, window_starts, nwindows, out_window_stride, stream);
 }
-// the same for float32 rows (`in` real, in_row_stride in reals, dtype = the output type): the REAL window-rows instances of
-// the whole-row kernel, refused through SWIFTLY_FEATURE_REAL_WINDOW_ROWS
+// the same for float32 rows: the REAL window-rows instances of the whole-row kernel
 int swiftly_hip_prepare_facet_window_rows_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                                int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                                int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                                int64_t other_axis_row0, const int32_t* window_starts, int64_t nwindows,
                                                int64_t out_window_stride, void* stream) {
-    if (!window_starts || nwindows <= 0) return fail(SWIFTLY_ERR_PARAM, "prepare_facet_window_rows_real: no windows");
-    if (h && (out_window_stride < h->m || out_row_stride < h->m ||
-              (out_window_stride < rows * out_row_stride && out_row_stride < nwindows * out_window_stride)))
-        return fail(SWIFTLY_ERR_PARAM, "prepare_facet_window_rows_real: the window rows of the output overlap (row stride %lld, window stride %lld)",
-                    (long long)out_row_stride, (long long)out_window_stride);
-    return prepare_facet_band_rows_impl(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off, band_start,
-                                        band_len, other_axis_size, other_axis_row0, window_starts, nwindows, out_window_stride, stream,
-                                        true);
+    return prepare_facet_window_rows(K1Form::RealWindowRows, "prepare_facet_window_rows_real", h, dtype, in, rows, facet_size,
+                                     in_row_stride, out, out_row_stride, facet_off, band_start, band_len, other_axis_size,
+                                     other_axis_row0, window_starts, nwindows, out_window_stride, stream);
 }
 
 // finish_facet_band and its real-output twin (`out` float32, out_row_stride in reals; real_out): one implementation

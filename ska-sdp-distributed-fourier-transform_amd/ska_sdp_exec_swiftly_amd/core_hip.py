@@ -648,13 +648,6 @@ class SwiftlyCoreHip:
         if real and not half_length and self.supports_real_facets() and not self._real_rows_match_promoted(facet.shape[1]):
             facet, real = facet.to(torch.complex64), False  # (keeps the values of the promoted facet: see there)
         out_dtype = torch.complex64 if real else facet.dtype
-        code = _lib.C64 if real else self._code(facet)
-        lib = self._lib
-        if half_length:
-            band_rows, band_whole = lib.swiftly_hip_prepare_facet_band_rows_rfft, lib.swiftly_hip_prepare_facet_band_rfft
-        else:
-            band_rows = lib.swiftly_hip_prepare_facet_band_rows_real if real else lib.swiftly_hip_prepare_facet_band_rows
-            band_whole = lib.swiftly_hip_prepare_facet_band_real if real else lib.swiftly_hip_prepare_facet_band
         ncols = self.band_columns(band)
         if out is None:
             out = torch.empty((facet.shape[0], ncols), dtype=out_dtype, device=self._device)
@@ -662,21 +655,30 @@ class SwiftlyCoreHip:
             raise ValueError(f"Output array has shape {tuple(out.shape)}, expected {(facet.shape[0], ncols)}!")
         elif real and out.dtype != out_dtype:
             raise ValueError(f"Output array is {out.dtype}, a float32 facet needs {out_dtype}!")
-        if rows_of is not None:
-            _lib.check(
-                band_rows(
-                    self._handle, code, ctypes.c_void_p(facet.data_ptr()), int(facet.shape[0]),
-                    int(facet.shape[1]), facet.stride(0), ctypes.c_void_p(out.data_ptr()), out.stride(0), int(facet_off),
-                    int(band[0]), int(band[1]), int(rows_of[0]) if fold_other_axis_window else 0, int(rows_of[1]),
-                    self._stream(),
-                )
-            )
-            return out
+        form = "half_length_band" if half_length else "real_band" if real else "band"
+        return self._k1_call(form, facet, out, out.stride(0), facet_off, band, fold_other_axis_window, rows_of)
+
+    #: the C entry point (``swiftly_hip_`` + name) of every K1 form, by (form, a row block was given); the window-rows
+    #: forms always take one
+    _K1_ENTRY = {
+        ("band", False): "prepare_facet_band", ("band", True): "prepare_facet_band_rows",
+        ("real_band", False): "prepare_facet_band_real", ("real_band", True): "prepare_facet_band_rows_real",
+        ("half_length_band", False): "prepare_facet_band_rfft", ("half_length_band", True): "prepare_facet_band_rows_rfft",
+        ("window_rows", True): "prepare_facet_window_rows", ("real_window_rows", True): "prepare_facet_window_rows_real",
+    }
+
+    def _k1_call(self, form, facet, out, out_row_stride, facet_off, band, fold_other_axis_window, rows_of, windows=()):
+        """the one native K1 call: ``facet`` (float32 in the real forms, whose dtype code is that of the output) into ``out``;
+        ``rows_of``: ``(size, row0)`` of the row block or None; ``windows``: the trailing arguments of the window-rows forms"""
+        entry = getattr(self._lib, "swiftly_hip_" + self._K1_ENTRY[form, rows_of is not None])
+        fold = (int(bool(fold_other_axis_window)),) if rows_of is None else (
+            int(rows_of[0]) if fold_other_axis_window else 0, int(rows_of[1]))
+        cvp = ctypes.c_void_p
         _lib.check(
-            band_whole(
-                self._handle, code, ctypes.c_void_p(facet.data_ptr()), int(facet.shape[0]),
-                int(facet.shape[1]), facet.stride(0), ctypes.c_void_p(out.data_ptr()), out.stride(0), int(facet_off),
-                int(band[0]), int(band[1]), int(bool(fold_other_axis_window)), self._stream(),
+            entry(
+                self._handle, _lib.C64 if facet.dtype == _torch().float32 else self._code(facet), cvp(facet.data_ptr()),
+                int(facet.shape[0]), int(facet.shape[1]), facet.stride(0), cvp(out.data_ptr()), out_row_stride, int(facet_off),
+                int(band[0]), int(band[1]), *fold, *windows, self._stream(),
             )
         )
         return out
@@ -722,8 +724,6 @@ class SwiftlyCoreHip:
         real = facet.dtype == torch.float32
         if real and out.dtype != torch.complex64:
             raise ValueError(f"Output array is {out.dtype}, a float32 facet needs {torch.complex64}!")
-        entry = self._lib.swiftly_hip_prepare_facet_window_rows_real if real else self._lib.swiftly_hip_prepare_facet_window_rows
-        code = _lib.C64 if real else self._code(facet)
         m = self.xM_yN_size
         nwin = int(window_starts.numel())
         if facet.dim() != 2 or facet.stride(1) != 1 or out.stride(-1) != 1:
@@ -735,17 +735,9 @@ class SwiftlyCoreHip:
         else:
             raise ValueError(f"Output array has shape {tuple(out.shape)}, expected {(nwin, facet.shape[0], m)} or "
                              f"{(facet.shape[0], nwin * m)}!")
-        size, row0 = rows_of if rows_of is not None else (facet.shape[0], 0)
-        cvp = ctypes.c_void_p
-        _lib.check(
-            entry(
-                self._handle, code, cvp(facet.data_ptr()), int(facet.shape[0]), int(facet.shape[1]),
-                facet.stride(0), cvp(out.data_ptr()), row_stride, int(facet_off), int(band[0]), int(band[1]),
-                int(size) if fold_other_axis_window else 0, int(row0), cvp(window_starts.data_ptr()), nwin, win_stride,
-                self._stream(),
-            )
-        )
-        return out
+        return self._k1_call("real_window_rows" if real else "window_rows", facet, out, row_stride, facet_off, band,
+                             fold_other_axis_window, rows_of if rows_of is not None else (facet.shape[0], 0),
+                             windows=(ctypes.c_void_p(window_starts.data_ptr()), nwin, win_stride))
 
     def prepare_facet_columns(self, bands, facet_off0s, band, subgrid_off1, rowmap=None, n_rows=None, out=None):
         """K2 (contiguous axis first): for every facet ``f``, gather the window of subgrid offset

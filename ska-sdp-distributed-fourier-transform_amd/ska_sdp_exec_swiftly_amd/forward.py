@@ -12,6 +12,7 @@ import numpy
 from . import _lib, slabs
 from .core_hip import band_range
 from .ingest import _FacetIngest, _mask_table
+from .k1_form import K1Facts, axis1_active, choose_k1, may_fuse
 from .prefetch import WavePrefetch, _knobs
 from .tasks import DeviceTask, LRUCache, TaskQueue, _torch, _unwrap
 
@@ -77,7 +78,7 @@ class SwiftlyForward(WavePrefetch):
         self._facet_dtype_asked = self._parse_facet_dtype(facet_dtype)
         if half_length_k1 and self._facet_dtype_asked is None:
             raise ValueError("half_length_k1=True needs facet_dtype=float32")
-        self._half_length_asked, self._half_length = bool(half_length_k1), False
+        self._half_length_asked, self._k1 = bool(half_length_k1), None  # (the K1 form: _decide_k1)
         WavePrefetch.__init__(self)
         self.delayed = bool(delayed)  # hand out DeviceTask handles instead of bare device tensors
         facet_tasks = [(cfg, _unwrap(data)) for cfg, data in facet_tasks]
@@ -89,9 +90,10 @@ class SwiftlyForward(WavePrefetch):
         self.queue_size = queue_size
         self._client = client
         self.lru = LRUCache(lru_forward)
-        # valid for one set of band buffers (set_band / install_bands): the buffers, their band, the axis-1-first mode and
-        # mode 2's {wave key: window}; the event behind K1, the one the side stream waited for, "a prefetched K2 has forked"
-        self.BF_Fs_persist, self._band, self._axis1_mode, self._window_of = None, None, None, None
+        # valid for one set of band buffers (set_band / install_bands): the buffers, their band (with it the axis-1-first mode
+        # of ``_k1``) and mode 2's {wave key: window}; the event behind K1, the one the side stream waited for, "a prefetched
+        # K2 has forked"
+        self.BF_Fs_persist, self._band, self._window_of = None, None, None
         self._bands_ready, self._side_waited, self._k2_chain_forked = None, None, False
         self._bands_own = False  # the band buffers are this object's own K1 output (not injected through install_bands)
         # column slabs of K2 (slabs.py): a cache of their own, so that the two slabs of the wave being served fit whatever
@@ -140,9 +142,8 @@ class SwiftlyForward(WavePrefetch):
         self._result_bytes = 0
         self._result_budget = int(float(os.environ.get("SWIFTLY_RESULT_CACHE_GB", "16")) * 2**30)
         # float32 facets: kept as they are when this object's K1 loads reals, promoted to complex64 otherwise -- decided
-        # before the first upload
-        self._half_length = self._keep_real_facets and self._k1_half_length()
-        self._ingest.settle(self._half_length or (self._keep_real_facets and self._k1_loads_reals()))
+        # before the first upload, for the band its own K1 will get
+        self._ingest.settle(self._decide_k1(own=True).facets_real)
         self._ingest.prefetch(0)
 
     @property
@@ -155,25 +156,7 @@ class SwiftlyForward(WavePrefetch):
     def half_length_k1(self):
         """does K1 of this object run the half-length transform of real rows (the ``half_length_k1`` keyword, where the form
         exists and every facet can be loaded as pairs)?"""
-        return self._half_length
-
-    def _k1_half_length(self):
-        """would K1 of this object run the half-length form?  The caller asked, every facet is float32, the object stores
-        the band (``wave_axis == 1``, not axis-1-first mode 2), the library has the form for these sizes and would refuse
-        none of the facets: even size, even position in the padded row, device rows 8-byte aligned at an even pitch."""
-        core = self.core
-        if not (self._half_length_asked and self._ingest.all_float32 and self.wave_axis == 1 and core.supports_real_facets_rfft()):
-            return False
-        band = core.band_for_offsets([sg.off1 for sg in self._plan]) if self._plan is not None else (0, core.yN_size)
-        if 2 in (self._axis1_mode_for(band, real=False), self._axis1_mode_for(band, real=True)):
-            return False
-        yN = core.yN_size
-        even = all(info[1][1] % 2 == 0 and (int(cfg.off1) + yN // 2 - info[1][1] // 2) % 2 == 0
-                   for info, cfg in zip(self._facet_info, self.facet_configs))
-        # (device facets are read in place; uploads are contiguous)
-        aligned = all(ten is None or ten.device != core.device or (ten.stride(0) % 2 == 0 and ten.data_ptr() % 8 == 0)
-                      for ten in self._ingest.tensors)
-        return even and aligned
+        return self._k1.half_length
 
     @staticmethod
     def _parse_facet_dtype(facet_dtype):
@@ -191,23 +174,37 @@ class SwiftlyForward(WavePrefetch):
             raise ValueError("facet_dtype must be float32 or None")
         return facet_dtype
 
-    def _k1_loads_reals(self):
-        """would K1 of this object take float32 facets as they are?  Every facet float32, the contiguous-axis-first
-        pipeline (``wave_axis == 1``), a real-load form of its row kernel for these sizes (``core.supports_real_facets``),
-        and not axis-1-first mode 2 -- unless the caller asked (``facet_dtype=float32``) and the whole-row K1 of mode 2
-        has its real form for this plan and can load these facets eight bytes at a time."""
-        core = self.core
-        if not (self._ingest.all_float32 and self.wave_axis == 1 and core.supports_real_facets()):
-            return False
-        if not all(core._real_rows_match_promoted(info[1][1]) for info in self._facet_info):
-            return False
-        band = core.band_for_offsets([sg.off1 for sg in self._plan]) if self._plan is not None else (0, core.yN_size)
-        if self._axis1_mode_for(band, real=False) != 2:
-            return True
-        # (device facets are read in place: two adjacent reals must be one aligned 8-byte load; uploads are contiguous)
-        aligned = all(ten is None or ten.device != core.device or (ten.stride(0) % 2 == 0 and ten.data_ptr() % 8 == 0)
-                      for ten in self._ingest.tensors)
-        return self._facet_dtype_asked is not None and aligned and self._axis1_mode_for(band, real=True) == 2
+    def _own_band(self):
+        """the band this object's own K1 stores: the plan's (complex128, or no plan: the whole padded axis, plain band layout)"""
+        planned = self._plan is not None and self.dtype == _torch().complex64
+        return self.core.band_for_offsets([sg.off1 for sg in self._plan]) if planned else (0, self.core.yN_size)
+
+    def _decide_k1(self, band=None, own=False):
+        """The K1 form of this object for ``band`` (``own``: the band of its own K1, worked out only where it matters): gathers
+        the facts of ``k1_form.K1Facts``, asks ``k1_form.choose_k1`` and stores the answer.  The first call (the constructor's)
+        decides whether float32 facets stay float32 and whether K1 runs the half-length form; later ones (``set_band``) only
+        the axis-1-first mode."""
+        # (``reals``: only then does what is asked of the library and of the tensors matter)
+        core, ingest, reals = self.core, self._ingest, self._ingest.all_float32 and self.wave_axis == 1
+        sizes, off1s = [info[1][-1] for info in self._facet_info], [int(cfg.off1) for cfg in self.facet_configs]
+        facts = K1Facts(
+            wave_axis=self.wave_axis, complex64=self.dtype == _torch().complex64, all_float32=ingest.all_float32,
+            float32_asked=self._facet_dtype_asked is not None, half_length_asked=self._half_length_asked,
+            keeps_real=self._keep_real_facets, axis1_first=getattr(core, "axis1_first", False), axis1_fused=self.axis1_fused,
+            planned=self._plan is not None, real_facets=reals and core.supports_real_facets(),
+            real_facets_rfft=reals and core.supports_real_facets_rfft(),
+            rows_match_promoted=all(core._real_rows_match_promoted(n) for n in sizes),  # pylint: disable=protected-access
+            even=all(n % 2 == 0 and (off1 + core.yN_size // 2 - n // 2) % 2 == 0 for n, off1 in zip(sizes, off1s)),
+            # (device facets are read in place: two adjacent reals must be one aligned 8-byte load; uploads are contiguous)
+            aligned=reals and all(t is None or t.device != core.device or (t.stride(0) % 2 == 0 and t.data_ptr() % 8 == 0)
+                                  for t in ingest.tensors), settled=self._k1)
+        # (only then are the window rows asked about: they need the plan's waves and a facet -- a rank may own none)
+        if (own or band is not None) and sizes and may_fuse(facts):
+            band = self._own_band() if own else band
+            rows = [core.supports_window_rows(band, sizes[0], off1s, len(self._planned_keys), real) for real in (False, True)]
+            facts = facts._replace(window_rows=rows[0], window_rows_real=rows[1])
+        self._k1 = choose_k1(facts)
+        return self._k1
 
     # -- tables derived from the plan: each built on first use by ONE walk over the plan (505 configs x 25 waves on every
     # pass otherwise), and not at all for objects that never need it
@@ -521,11 +518,7 @@ class SwiftlyForward(WavePrefetch):
             self._check_band_pipeline()
             torch = _torch()
             core = self.core
-            # (complex128: K1 keeps the whole padded axis in the plain band layout)
-            mode = self.set_band(
-                core.band_for_offsets([sg.off1 for sg in self._plan])
-                if self._plan is not None and self.dtype == torch.complex64 else (0, core.yN_size)
-            )
+            mode = self.set_band(self._own_band())
             F, yB = len(self._facet_info), self._facet_info[0][1][0]
             if mode == 2:
                 # axis-1-first pipeline, contiguous-axis finish fused into K1: per facet row, for every planned window, the
@@ -542,7 +535,7 @@ class SwiftlyForward(WavePrefetch):
                 if mode == 2:
                     core.prepare_facet_window_rows(data, cfg.off1, self._band, starts, bands[j])
                 else:
-                    core.prepare_facet_band(data, cfg.off1, self._band, out=bands[j], half_length=self._half_length)
+                    core.prepare_facet_band(data, cfg.off1, self._band, out=bands[j], half_length=self._k1.half_length)
                 if timer is not None:
                     timer.stop("K1_full_facet_transform", t0)
                 self._ingest.prefetch(j + 1)
@@ -558,9 +551,8 @@ class SwiftlyForward(WavePrefetch):
         """First step of installing band buffers: the band they cover decides the axis-1-first mode (returned) and, in mode
         2, the window table -- and with them the shape of the buffers (``[F, W, yB, m]`` against ``[F, yB, band columns]``)."""
         self._band = band
-        self._axis1_mode = self._choose_axis1_mode()
-        self._window_of = {k: w for w, k in enumerate(sorted(self._planned_keys))} if self._axis1_mode == 2 else None
-        return self._axis1_mode
+        self._window_of = {k: w for w, k in enumerate(sorted(self._planned_keys))} if self._decide_k1(band).axis1_mode == 2 else None
+        return self._k1.axis1_mode
 
     def install_bands(self, bands, ready=None):
         """Second step: the finished buffers (this object's own K1 output, or what the band-row exchange of the multi-GPU
@@ -585,33 +577,13 @@ class SwiftlyForward(WavePrefetch):
     #: may float32 facets stay float32 (see the constructor)?  The multi-GPU classes, which have no real form, switch it off.
     _keep_real_facets = True
 
-    def _choose_axis1_mode(self):
-        """the axis-1-first mode for the installed band and the facets as they are resident"""
-        return self._axis1_mode_for(self._band, self._ingest.real)
-
-    def _axis1_mode_for(self, band, real):
-        """0: default order; 1: axis-1-first with a row pass per wave (core.finish_axis1_rows; ``axis1_first="rows"``, or
-        ``True`` where 2 is not available); 2: axis-1-first with the finish in the epilogue of K1 (``axis1_first=True``;
-        needs a plan -- the windows are the plan's waves -- and a configuration with core.supports_window_rows)."""
-        if not axis1_first_active(self.core, self.wave_axis, self.dtype):
-            return 0
-        # (``real``: the facets are resident as float32.  The whole-row K1 of mode 2 loads reals only for a caller who asked
-        # (``facet_dtype=float32``): without the keyword _k1_loads_reals keeps them real only when the plan's own band does
-        # not lead to mode 2, and band buffers installed from outside never get it)
-        if (self.core.axis1_first is True and self.axis1_fused and self._plan is not None and band is not None and
-                (not real or self._facet_dtype_asked is not None) and
-                self.core.supports_window_rows(band, self._facet_info[0][1][1], [cfg.off1 for cfg in self.facet_configs],
-                                               n_windows=len(self._planned_keys), real=bool(real))):
-            return 2
-        return 1
-
     def _axis1(self):
         """the axis-1-first mode of this object (``SwiftlyConfig(axis1_first=True)``, wave_axis = 1): 0 = off, 1 = row pass
         per wave, 2 = fused into K1 (decided when the facets are prepared)"""
-        mode = self._axis1_mode
-        if mode is None:
-            mode = self._choose_axis1_mode() if self.BF_Fs_persist is None else 0
-        return mode
+        if self._band is None:  # before set_band: without a band there are no window rows, so never mode 2 (a row pass per
+            # wave where the pipeline is on) -- or band buffers installed without set_band
+            return int(axis1_first_active(self.core, self.wave_axis, self.dtype)) if self.BF_Fs_persist is None else 0
+        return self._k1.axis1_mode
 
     def _placed(self):
         """the ``placed`` argument of the subgrid side: in both axis-1-first modes the blocks arrive finished along axis 1"""
@@ -785,10 +757,8 @@ class _PromotingForward(SwiftlyForward):
 
 def axis1_first_active(core, wave_axis, dtype):
     """does a forward object of this core, wave axis and dtype send blocks finished along axis 1 (axis-1-first pipeline,
-    either form)?  One rule for the senders (``_choose_axis1_mode``) and for whoever finishes their blocks (``placed``)."""
-    if not (wave_axis == 1 and bool(getattr(core, "axis1_first", False))):
-        return False
-    return dtype == _torch().complex64  # (a float32 accuracy mode: complex128 runs the default order)
+    either form)?  One rule (``k1_form.axis1_active``) for the senders and for whoever finishes their blocks (``placed``)."""
+    return axis1_active(wave_axis, getattr(core, "axis1_first", False), dtype == _torch().complex64)
 
 
 def _finish_from_columns(core, src, layout, facet_configs, sgs, window_offs, rowmap=None, band=None, placed=False):

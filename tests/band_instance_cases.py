@@ -22,7 +22,7 @@ A case is a dict:
 
 The ``call`` of a case is written by the constructor of its kind, which restates the launch site: ``try_row_pass`` (plain
 store of prepare_facet / prepare_subgrid: no window-table cache; mapped store of finish_facet_band: the handle's cache at
-32768 points, none at 65536) and ``prepare_facet_band_rows_impl`` (band store and window rows: the handle's cache).  A fresh
+32768 points, none at 65536) and ``prepare_facet_k1`` (band store and window rows: the handle's cache).  A fresh
 handle's cache always has a table to give (``table_available``), and compact twiddle sections exist at 32768 points only
 (``has_twc``).
 """
@@ -81,7 +81,7 @@ def band_half(length):
 
 
 def k1(cid, knob, want, seg_rot, core, size, off, dtype="c64", rows=7, band=None, pitch=None, base=0, fold=False):
-    """prepare_facet_band(_real): prepare_facet_band_rows_impl -- load window, band store, both conjugations, the cache"""
+    """prepare_facet_band(_real): prepare_facet_k1 -- load window, band store, both conjugations, the cache"""
     yN = CORES[core][3]
     band = band or {"c14": (5461, 5477), "c15": BAND15, "c16": (21845, 21861)}[core]
     pitch = pitch or size
@@ -231,15 +231,15 @@ finish("finish-64k-real-full", DEFAULT, ("BandGeo64k", 0, 2, 0, 0, -1, 0, 0, 1),
 
 #: instances of SWF_BAND_INSTANCES that no exported entry point reaches, each with the launch-site condition that excludes it
 #: (csrc/swiftly_abi.hip: try_row_pass sends only 32768- and 65536-point rows to the band row kernel; the one band-store call
-#: site, prepare_facet_band_rows_impl, always passes the facet window)
+#: site, prepare_facet_k1, always passes the facet window)
 NOT_REACHABLE_THROUGH_THE_ABI = {
     ("BandGeo16k", 0, 0, 0, 0, -1, 0, 0, 0): "try_row_pass runs the plain store of 16384-point rows on the lean single-workgroup kernel (launch_row_pass)",
     ("BandGeo16k", 1, 0, 0, 0, -1, 0, 0, 0): "try_row_pass runs the plain store of 16384-point rows, windowed or not, on the lean single-workgroup kernel",
     ("BandGeo16k", 0, 2, 0, 0, -1, 0, 0, 0): "try_row_pass runs the mapped store of 16384-point rows (finish_facet_band) on the lean single-workgroup kernel",
-    ("BandGeo16k", 0, 1, 0, 0, -1, 0, 0, 0): "the band store is launched by prepare_facet_band_rows_impl only, which always sets ld_win to the facet window",
-    ("BandGeo5", 0, 1, 0, 0, -1, 0, 0, 0): "the band store is launched by prepare_facet_band_rows_impl only, which always sets ld_win (here: an odd shift or pitch)",
-    ("BandGeo5", 0, 1, 1, 0, -1, 0, 0, 0): "the band store is launched by prepare_facet_band_rows_impl only, which always sets ld_win (here: adjacent-point loads)",
-    ("BandGeo64k", 0, 1, 0, 0, -1, 0, 0, 0): "the band store is launched by prepare_facet_band_rows_impl only, which always sets ld_win (here: 65536-point rows)",
+    ("BandGeo16k", 0, 1, 0, 0, -1, 0, 0, 0): "the band store is launched by prepare_facet_k1 only, which always sets ld_win to the facet window",
+    ("BandGeo5", 0, 1, 0, 0, -1, 0, 0, 0): "the band store is launched by prepare_facet_k1 only, which always sets ld_win (here: an odd shift or pitch)",
+    ("BandGeo5", 0, 1, 1, 0, -1, 0, 0, 0): "the band store is launched by prepare_facet_k1 only, which always sets ld_win (here: adjacent-point loads)",
+    ("BandGeo64k", 0, 1, 0, 0, -1, 0, 0, 0): "the band store is launched by prepare_facet_k1 only, which always sets ld_win (here: 65536-point rows)",
 }
 
 
