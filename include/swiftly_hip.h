@@ -122,9 +122,12 @@ enum {
     SWIFTLY_FEATURE_REAL_WINDOW_ROWS = 11,      /* prepare_facet_window_rows_real (dtype = the OUTPUT type), size part: the
                                                    sizes of WINDOW_ROWS that are also sizes of REAL_FACETS in complex64.  The
                                                    gate the entry point refuses through ("real window rows: ...") */
-    SWIFTLY_FEATURE_REAL_FACETS_RFFT = 12       /* prepare_facet_band_rfft / prepare_facet_band_rows_rfft (dtype = the OUTPUT
+    SWIFTLY_FEATURE_REAL_FACETS_RFFT = 12,      /* prepare_facet_band_rfft / prepare_facet_band_rows_rfft (dtype = the OUTPUT
                                                    type), size part: the sizes of REAL_FACETS with yN_size 32768.  The gate both
                                                    entry points refuse through ("real facets, half-length: ...") */
+    SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R = 13    /* finish_facet_band_c2r (dtype = the INPUT type), size part: the sizes of
+                                                   REAL_FACETS_OUT with yN_size 32768.  The gate the entry point refuses
+                                                   through ("real facets out, half-length: ...") */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -690,6 +693,20 @@ int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, i
 int swiftly_hip_finish_facet_band_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
                                        int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
                                        int64_t facet_off, int64_t facet_size, const void* mask, void* stream);
+/* finish_facet_band_real as ONE HALF-LENGTH transform per row (csrc/swiftly_rowc2r.h): only the real part of the 32768-point
+ * transform of a band row is wanted, and that is the transform of the row's Hermitian part -- one 16384-point complex
+ * transform of a recombination of the band elements k, k + yN/2 and their mirrors, in one workgroup per row, where the entry
+ * point above runs the whole complex transform in two workgroups per row and drops the imaginary half.  Same arguments, same
+ * quantity, the same error bound against the exact transform -- NOT the same bits: the rounding differs.  A kernel and a door
+ * of its own that nothing else routes to (not an instance of the band row kernel: swiftly_hip_last_band_instance does not
+ * count it).  Sizes: SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R (REAL_FACETS_OUT with yN_size 32768).  Per call, an odd facet_size, a
+ * facet at an odd position of the padded row (yN_size / 2 - facet_size / 2 + facet_off odd), an odd out_row_stride or an `out`
+ * that is not 8-byte aligned is SWIFTLY_ERR_UNSUPPORTED ("real facets out, half-length: ...") and nothing is written -- a
+ * refusal is not a copy through the entry point above; out_row_stride < facet_size is SWIFTLY_ERR_PARAM as there.  The
+ * other checks of the arguments are those of swiftly_hip_finish_facet_band. */
+int swiftly_hip_finish_facet_band_c2r(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                      int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
+                                      int64_t facet_off, int64_t facet_size, const void* mask, void* stream);
 
 /* -- point-source truths and RMSE checks on the device (handle-free; work is enqueued on `stream` of the current device).
  *    The reference checks itself with point sources: it builds facets with make_facet, and compares every subgrid with

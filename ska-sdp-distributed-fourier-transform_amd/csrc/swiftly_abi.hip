@@ -1477,25 +1477,72 @@ int swiftly_hip_prepare_facet_window_rows_real(swiftly_hip_t* h, int dtype, cons
                                      other_axis_row0, window_starts, nwindows, out_window_stride, stream);
 }
 
-// finish_facet_band and its real-output twin (`out` float32, out_row_stride in reals; real_out): one implementation
-static int finish_facet_band_impl(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+// finish_facet_band, its real-output twin (`out` float32, out_row_stride in reals) and the half-length form of the twin: one
+// implementation.  The forms differ in the capability rule they consult and, for the half-length form, the launcher.
+enum class B8Form {
+    Complex,
+    RealStore,       // the real-store instances of the row kernels: SWIFTLY_FEATURE_REAL_FACETS_OUT
+    HalfLengthReal,  // one half-length transform per row (swiftly_rowc2r.h), SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R: its own kernel
+                     // and its own refusals -- a call the kernel does not take is refused before anything is written, never
+                     // handed to the real-store form
+};
+static int finish_facet_band_impl(B8Form form, swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
                                   int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
-                                  int64_t facet_off, int64_t facet_size, const void* mask, void* stream, bool real_out) {
+                                  int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
     const int64_t in_cs = 1, out_cs = 1;
+    const bool real_out = form != B8Form::Complex, half = form == B8Form::HalfLengthReal;
+    const char* name = half ? "finish_facet_band_c2r" : "finish_facet_band_real";
     CHECK_COMMON();
-    if (real_out) {  // float32 rows out: the capability rule of SWIFTLY_FEATURE_REAL_FACETS_OUT
-        if (const std::string why = why_not_real_facets_out(*h, dtype); !why.empty())
-            return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band_real: %s", why.c_str());
+    if (real_out) {  // float32 rows out: the capability rule of the form's feature
+        if (const std::string why = half ? why_not_real_facets_out_c2r(*h, dtype) : why_not_real_facets_out(*h, dtype); !why.empty())
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "%s: %s", name, why.c_str());
     }
     CHECK_FACET_SIZE();
     if (real_out && out_row_stride < facet_size)
-        return fail(SWIFTLY_ERR_PARAM, "finish_facet_band_real: out_row_stride %lld is below facet_size %lld: the rows of the output overlap",
+        return fail(SWIFTLY_ERR_PARAM, "%s: out_row_stride %lld is below facet_size %lld: the rows of the output overlap", name,
                     (long long)out_row_stride, (long long)facet_size);
     // (the gate of swiftly_hip_supports(BACKWARD_BAND_EXPLICIT): identical to BACKWARD_BAND in complex64; complex128 rows run
     // through do_finish_facet<double>, 64 .. 32768 points)
     if (const std::string why = why_not_backward_band(*h, dtype, true); !why.empty())
         return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band: %s", why.c_str());
     CHECK_BAND();
+    if (half) {
+        // one 8-byte store per output pair (y[2n], y[2n + 1]): the pair must be one aligned pair of facet columns of every row
+        const Map facet = facet_in_padded_facet(*h, facet_size, facet_off);
+        if (facet_size & 1)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band_c2r: real facets out, half-length: odd facet size %lld", (long long)facet_size);
+        if (facet.a & 1)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band_c2r: real facets out, half-length: the facet starts at an odd index of the padded row "
+                        "(store offset %d, facet offset %lld)", facet.a, (long long)facet_off);
+        if (out_row_stride & 1)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band_c2r: real facets out, half-length: odd output row stride %lld", (long long)out_row_stride);
+        if (reinterpret_cast<uintptr_t>(out) & 7)
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "finish_facet_band_c2r: real facets out, half-length: output is not 8-byte aligned");
+        if (in_row_stride < 0) return fail(SWIFTLY_ERR_PARAM, "finish_facet_band_c2r: negative input row stride");
+        if (rows == 0) return 0;
+        const hipStream_t st = (hipStream_t)stream;
+        const Map band = band_as_load_map(*h, band_start, band_len);
+        RowPassArgs r;
+        std::memset(&r, 0, sizeof r);
+        r.in = (const cx<float>*)in; r.out = (cx<float>*)out;
+        r.in_pitch = in_row_stride; r.out_pitch = out_row_stride;
+        r.out_real = 1;  // `out` points to float32, out_pitch counts real elements
+        r.nrows = (int)rows;
+        r.ld_a = band.a; r.ld_len = band.len; r.ld_c = band.c; r.ld_mod = band.mod;
+        r.st_a = facet.a; r.st_len = facet.len; r.st_c = facet.c; r.st_mod = facet.mod;
+        // the mask and the PSWF window of finish_facet as the ONE window the mapped store of the band row kernel takes
+        r.st_win = (const float*)mask; r.st_win2 = h->invp_f + facet_lo(*h, facet_size);
+        r.scale = 1.f;
+        r.twc = compact_twiddles(h, 14, 5);
+        const cx<float>* twh = twiddles<float>(h, h->log_yN - 1);
+        const cx<float>* twf = twiddles<float>(h, h->log_yN);
+        if (!twh || !twf || !r.twc) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
+        void* tmp = nullptr;
+        if (int rc = single_store_window(r, st, &tmp)) return rc;
+        const int e = launch_row_c2r_band(r, twh, twf, st);
+        if (tmp) (void)hipFreeAsync(tmp, st);
+        return launch_status(e);
+    }
     Batch bt{1, 0, 0, nullptr, 0};
     return DISPATCH(do_finish_facet, h, in, rows, in_row_stride, in_cs, out, out_row_stride, out_cs, facet_off, facet_size,
                     mask, bt, (hipStream_t)stream, band_start, band_len, real_out);
@@ -1504,14 +1551,20 @@ static int finish_facet_band_impl(swiftly_hip_t* h, int dtype, const void* in, i
 int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
                                   int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
                                   int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
-    return finish_facet_band_impl(h, dtype, in, rows, in_row_stride, band_start, band_len, out, out_row_stride, facet_off,
-                                  facet_size, mask, stream, false);
+    return finish_facet_band_impl(B8Form::Complex, h, dtype, in, rows, in_row_stride, band_start, band_len, out, out_row_stride,
+                                  facet_off, facet_size, mask, stream);
 }
 int swiftly_hip_finish_facet_band_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
                                        int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
                                        int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
-    return finish_facet_band_impl(h, dtype, in, rows, in_row_stride, band_start, band_len, out, out_row_stride, facet_off,
-                                  facet_size, mask, stream, true);
+    return finish_facet_band_impl(B8Form::RealStore, h, dtype, in, rows, in_row_stride, band_start, band_len, out,
+                                  out_row_stride, facet_off, facet_size, mask, stream);
+}
+int swiftly_hip_finish_facet_band_c2r(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                      int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
+                                      int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
+    return finish_facet_band_impl(B8Form::HalfLengthReal, h, dtype, in, rows, in_row_stride, band_start, band_len, out,
+                                  out_row_stride, facet_off, facet_size, mask, stream);
 }
 
 

@@ -27,6 +27,7 @@
 #include "swiftly_launch.h"
 #include "swiftly_rowpass.h"
 #include "swiftly_rowreal.h"
+#include "swiftly_rowc2r.h"
 #include "swiftly_sumfinish.h"
 #include "swiftly_rows.h"
 #include "swiftly_rowslong.h"

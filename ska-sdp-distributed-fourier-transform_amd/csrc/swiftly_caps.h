@@ -278,6 +278,16 @@ inline std::string why_not_real_facets_rfft(const Sizes& s, int dtype) {
         return reason("real facets, half-length: needs yN %d; got yN %lld", 1 << kRealRfftLogYN, (long long)s.yN);
     return {};
 }
+// real-valued facets out of the backward band pass through the half-length B8 (finish_facet_band_c2r, swiftly_rowc2r.h): the
+// sizes of the real-store B8 at which the one-workgroup 16384-point form exists (the per-call conditions -- even facet size,
+// position and output row stride, an 8-byte-aligned output -- are the entry point's)
+constexpr int kRealOutC2RLogYN = 15;
+inline std::string why_not_real_facets_out_c2r(const Sizes& s, int dtype) {
+    if (std::string why = why_not_real_facets_out(s, dtype); !why.empty()) return "real facets out, half-length: " + why;
+    if (s.log_yN != kRealOutC2RLogYN)
+        return reason("real facets out, half-length: needs yN %d; got yN %lld", 1 << kRealOutC2RLogYN, (long long)s.yN);
+    return {};
+}
 // size part of prepare_facet_window_rows (the band, the facets and the windows are per call)
 inline std::string why_not_window_rows(const Sizes& s) {
     if (s.log_yN == kWindowRowsLogYN && s.log_m == kWindowRowsLogM && s.xM <= (int64_t(1) << kPlacedMaxLogXM)) return {};

@@ -18,7 +18,8 @@ ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
 # swiftly_hip_supports / swiftly_hip_limit (include/swiftly_hip.h)
 (FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
  FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE, FEATURE_REAL_FACETS,
- FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH, FEATURE_REAL_WINDOW_ROWS, FEATURE_REAL_FACETS_RFFT) = range(13)
+ FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH, FEATURE_REAL_WINDOW_ROWS, FEATURE_REAL_FACETS_RFFT,
+ FEATURE_REAL_FACETS_OUT_C2R) = range(14)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None
@@ -187,6 +188,9 @@ def _declare(lib):
     # float32 rows out of the backward finish (same arguments; `out` is real, its row stride counts reals, dtype = input type)
     lib.swiftly_hip_finish_facet_band_real.restype = c_int
     lib.swiftly_hip_finish_facet_band_real.argtypes = list(lib.swiftly_hip_finish_facet_band.argtypes)
+    # ... and its half-length form (swiftly_rowc2r.h): the same arguments
+    lib.swiftly_hip_finish_facet_band_c2r.restype = c_int
+    lib.swiftly_hip_finish_facet_band_c2r.argtypes = list(lib.swiftly_hip_finish_facet_band.argtypes)
     # point-source truths (handle-free): (dtype, sources, n_sources, image_size, size, ...
     src = [c_int, vp, i64, i64, i64]
     for name, args in [

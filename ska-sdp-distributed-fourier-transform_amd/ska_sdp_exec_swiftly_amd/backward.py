@@ -46,11 +46,21 @@ class SwiftlyBackward:
         everywhere else each facet is finished complex, its real part copied out and the complex one released before
         the next facet is finished.  A dtype that does not match the data's precision raises ``ValueError`` -- at
         construction when ``dtype`` is given, else at the first data.
+    :param half_length_finish: (``facet_dtype=torch.float32`` only, else ``ValueError``) finish the float32 facets through
+        the half-length form of the contiguous-axis kernel (``core.finish_facet_band(..., real=True, half_length=True)``):
+        one 16384-point transform per 32768-point band row.  The same facets within the same error bound, not the same
+        bits as without it.  Taken where :py:attr:`half_length_finish` says so; everywhere else the pass runs exactly
+        what it runs without the keyword.
     """
 
     # pylint: disable=too-many-arguments,too-many-instance-attributes
     def __init__(self, swiftly_config, facets_config_list, lru_backward=1, queue_size=20, client=None,
-                 subgrid_configs=None, wave_axis=None, delayed=False, dtype=None, facet_dtype=None):
+                 subgrid_configs=None, wave_axis=None, delayed=False, dtype=None, facet_dtype=None, half_length_finish=False):
+        # (before anything touches the configuration or a device)
+        self._want_half_length = bool(half_length_finish)
+        if self._want_half_length and self._parse_facet_dtype(facet_dtype) != _torch().float32:
+            raise ValueError("half_length_finish=True needs facet_dtype=float32: the half-length finish produces real facets "
+                             f"from complex64 data, got facet_dtype={facet_dtype}")
         self.delayed = bool(delayed)  # finish() hands out DeviceTask handles instead of bare device tensors
         # wave_axis=None: the reference's schedule, unless the caller hands over the plan of subgrids it will add and
         # the band kernels exist -- decided when the first subgrid shows the dtype (complex64 only)
@@ -140,6 +150,17 @@ class SwiftlyBackward:
         if not self._real_facets:
             return False
         return bool(self.wave_axis == 1 and self._facet_dtype == _torch().float32 and self.core.supports_real_facets_out())
+
+    @property
+    def half_length_finish(self):
+        """True when :py:meth:`finish` runs the half-length form of the contiguous-axis kernel: asked for
+        (``half_length_finish=True``), :py:attr:`real_finish_native` holds, ``core.supports_real_facets_out_c2r()``, and every
+        facet has an even size at an even position of the padded row (the kernel stores aligned pairs of pixels).
+        Otherwise False: the real-store form, bit for bit what the pass gives without the keyword."""
+        if not (self._want_half_length and self.real_finish_native and self.core.supports_real_facets_out_c2r()):
+            return False
+        yN = self.core.yN_size
+        return all(cfg.size % 2 == 0 and (yN // 2 - cfg.size // 2 + cfg.off1) % 2 == 0 for cfg in self.facets_config_list)
 
     def _real_part(self, facet):
         """the real part of a finished complex facet as a tensor of its own (the caller drops the complex one)"""
@@ -503,9 +524,11 @@ class SwiftlyBackward:
             return [torch.zeros((cfg.size, cfg.size), dtype=dt, device=core.device) for cfg in self.facets_config_list]
         core.band_zero_untouched(self._bands, self._touched)
         native = self.real_finish_native and self._bands.dtype == torch.complex64
+        half = bool(native and self.half_length_finish)
         for j, cfg in enumerate(self.facets_config_list):
             if native:  # float32 straight from the row kernels: no complex facet exists
-                out.append(core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1, real=True))
+                out.append(core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1, real=True,
+                                                  half_length=half))
                 continue
             facet = core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1)
             out.append(self._real_part(facet) if self._real_facets else facet)

@@ -610,6 +610,14 @@ class SwiftlyCoreHip:
         After a False ``_lib.last_error()`` says why."""
         return self._supports(_lib.FEATURE_REAL_FACETS_OUT, _torch().complex64)
 
+    def supports_real_facets_out_c2r(self):
+        """True when the half-length form of the real-output backward finish exists for these sizes
+        (``finish_facet_band(..., real=True, half_length=True)``; ``swiftly_hip_finish_facet_band_c2r``):
+        :py:meth:`supports_real_facets_out` at ``yN_size`` 32768.  Per call it also needs an even facet size, an even position
+        of the facet in the padded row, an even output row pitch and 8-byte-aligned output rows.  After a False
+        ``_lib.last_error()`` says why."""
+        return self._supports(_lib.FEATURE_REAL_FACETS_OUT_C2R, _torch().complex64)
+
     def band_for_offsets(self, subgrid_offs):
         """Smallest cyclic range ``(start, length)`` of centred indices of the padded facet axis that contains
         the ``xM_yN_size`` window of every given subgrid offset (core.py:243-253); ``(0, yN_size)`` = all."""
@@ -1105,16 +1113,24 @@ class SwiftlyCoreHip:
             )
         )
 
-    def finish_facet_band(self, band_acc, band, facet_off, facet_size, mask=None, out=None, real=False):
+    def finish_facet_band(self, band_acc, band, facet_off, facet_size, mask=None, out=None, real=False, half_length=False):
         """``finish_facet`` (core.py:481-510) along the contiguous axis for a band accumulator ``[rows, band
         length]`` (``swiftly_hip_finish_facet_band``).
 
         ``real=True`` (complex64 accumulators, :py:meth:`supports_real_facets_out`): the facet is an image -- the result is
         the float32 tensor ``[rows, facet_size]`` of the real parts, bit for bit those of the complex result, written
         by the row kernels themselves (``swiftly_hip_finish_facet_band_real``; no complex facet exists at any time).
-        ``out``: float32 rows of any pitch ``>= facet_size`` with unit column stride."""
+        ``out``: float32 rows of any pitch ``>= facet_size`` with unit column stride.
+
+        ``half_length=True`` (with ``real=True``, else ``ValueError``; :py:meth:`supports_real_facets_out_c2r`): the same
+        float32 facet through ONE half-length transform per band row (``swiftly_hip_finish_facet_band_c2r``) -- the same
+        quantity within the same bound, not the bits of the real-store form.  A call the kernel does not take (an odd facet
+        size or position, an odd pitch or 4-byte-aligned rows of ``out``, other sizes) raises ``NotImplementedError`` and
+        writes nothing: it is never handed to the real-store form."""
         torch = _torch()
         rows = band_acc.shape[0]
+        if half_length and not real:
+            raise ValueError("finish_facet_band(half_length=True) needs real=True: the half-length form produces float32 facets")
         if real and not band_acc.is_complex():
             raise ValueError(f"finish_facet_band(real=True) needs complex accumulators, got {band_acc.dtype}")
         want = torch.float32 if real else band_acc.dtype
@@ -1127,6 +1143,8 @@ class SwiftlyCoreHip:
         mvec = self._real_vec(mask, band_acc.dtype, int(facet_size)) if mask is not None else None
         cvp = ctypes.c_void_p
         entry = self._lib.swiftly_hip_finish_facet_band_real if real else self._lib.swiftly_hip_finish_facet_band
+        if half_length:
+            entry = self._lib.swiftly_hip_finish_facet_band_c2r
         _lib.check(
             entry(
                 self._handle, self._code(band_acc), cvp(band_acc.data_ptr()), rows, band_acc.stride(0), int(band[0]),
