@@ -736,7 +736,12 @@ int swiftly_hip_finish_facet_band_c2r(swiftly_hip_t* h, int dtype, const void* i
  * check_facet_from_sources: check_facet (api_helper.py:39-48): result = { sum |truth - approx|^2, sum |truth|^2 }
  *   (device double [2]), every pixel of the facet differenced on its own.  The sources of facet row r are
  *   row_sources[row_start[r] .. row_start[r + 1]) (device int32; indices into the table, ascending in their facet column;
- *   row_start has size + 1 entries), built by the caller for these offsets. */
+ *   row_start has size + 1 entries), built by the caller for these offsets.
+ * facet_from_sources_real / check_facet_from_sources_real: the same two for a real-valued image, which never becomes
+ *   complex: the arguments of their twins, but out / approx hold reals -- float for SWIFTLY_C64, double for SWIFTLY_C128
+ *   -- and the row stride counts reals.  The store writes Re(I_s) * mask0[p0] * mask1[p1] (the caller refuses a table
+ *   with a non-zero imaginary part); the check takes the truth's imaginary part as zero and sums in the order of the
+ *   complex check: for approx with zero imaginary parts both give the same bits. */
 int swiftly_hip_subgrids_from_sources(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
                                       int64_t size, const int64_t* off0s, const int64_t* off1s, int64_t n_subgrids,
                                       const double* mask0s, const double* mask1s, void* out, int64_t out_sub_stride,
@@ -754,6 +759,14 @@ int swiftly_hip_check_facet_from_sources(int dtype, const void* sources, int64_t
                                          const double* mask1, const void* approx, int64_t approx_row_stride,
                                          const int32_t* row_start, const int32_t* row_sources, double* result,
                                          void* stream);
+int swiftly_hip_facet_from_sources_real(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
+                                        int64_t size, int64_t off0, int64_t off1, const double* mask0,
+                                        const double* mask1, void* out, int64_t out_row_stride, void* stream);
+int swiftly_hip_check_facet_from_sources_real(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
+                                              int64_t size, int64_t off0, int64_t off1, const double* mask0,
+                                              const double* mask1, const void* approx, int64_t approx_row_stride,
+                                              const int32_t* row_start, const int32_t* row_sources, double* result,
+                                              void* stream);
 
 /* -- device memory helpers for callers that do not bring their own allocator
  *    (the Python mirror uses torch for device memory and never calls these) -- */

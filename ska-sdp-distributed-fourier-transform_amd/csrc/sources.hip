@@ -1,5 +1,6 @@
 // instantiations of the point-source truth kernels (swiftly_sources.h): phase tables, the rank-S subgrid update with its
 // store / check epilogues for both storage types, the fixed-order partial sums and the facet scatter / row check
+// (complex and real element types)
 #include "swiftly_sources.h"
 
 namespace swf {
@@ -36,7 +37,8 @@ static int facet_store_one(const SrcFacetArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(src_facet_store_kernel<OUT>, dim3((unsigned)((a.S + 255) / 256)), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
-int launch_src_facet_store(const SrcFacetArgs& a, bool c128, hipStream_t st) {
+int launch_src_facet_store(const SrcFacetArgs& a, bool c128, bool real, hipStream_t st) {
+    if (real) return c128 ? facet_store_one<double>(a, st) : facet_store_one<float>(a, st);
     return c128 ? facet_store_one<cx<double>>(a, st) : facet_store_one<cx<float>>(a, st);
 }
 
@@ -45,7 +47,8 @@ static int facet_check_one(const SrcFacetArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(src_facet_check_kernel<OUT>, dim3((unsigned)a.size), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
-int launch_src_facet_check(const SrcFacetArgs& a, bool c128, hipStream_t st) {
+int launch_src_facet_check(const SrcFacetArgs& a, bool c128, bool real, hipStream_t st) {
+    if (real) return c128 ? facet_check_one<double>(a, st) : facet_check_one<float>(a, st);
     return c128 ? facet_check_one<cx<double>>(a, st) : facet_check_one<cx<float>>(a, st);
 }
 

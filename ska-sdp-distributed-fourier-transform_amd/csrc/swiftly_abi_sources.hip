@@ -123,6 +123,31 @@ int facet_args(SrcFacetArgs& a, int dtype, const void* sources, int64_t n_source
     return 0;
 }
 
+// Both facet scatters (real: `out` holds float / double, row_stride counts reals) ...
+int facet_from_sources(bool real, int dtype, const void* sources, int64_t n_sources, int64_t image_size, int64_t size,
+                       int64_t off0, int64_t off1, const double* mask0, const double* mask1, void* out, int64_t row_stride,
+                       hipStream_t st) {
+    SrcFacetArgs a;
+    if (int rc = facet_args(a, dtype, sources, n_sources, image_size, size, off0, off1, mask0, mask1, out, row_stride)) return rc;
+    return launch_status(launch_src_facet_store(a, dtype == SWIFTLY_C128, real, st), "facet from sources");
+}
+
+// ... and both facet checks: one workgroup per row into per-row partial sums, then their fixed-order sum
+int check_facet_from_sources(bool real, int dtype, const void* sources, int64_t n_sources, int64_t image_size, int64_t size,
+                             int64_t off0, int64_t off1, const double* mask0, const double* mask1, const void* approx,
+                             int64_t row_stride, const int32_t* row_start, const int32_t* row_sources, double* result,
+                             hipStream_t st) {
+    SrcFacetArgs a;
+    if (int rc = facet_args(a, dtype, sources, n_sources, image_size, size, off0, off1, mask0, mask1, approx, row_stride)) return rc;
+    if (!row_start || !result || (n_sources > 0 && !row_sources)) return fail(SWIFTLY_ERR_PARAM, "null argument");
+    ScratchLease lease;
+    if (int rc = lease.acquire(nullptr, 0, (size_t)size * 2 * sizeof(double), st, "facet check partial sums")) return rc;
+    a.row_start = row_start; a.row_srcs = row_sources; a.partials = (double*)lease.p;
+    int rc = launch_status(launch_src_facet_check(a, dtype == SWIFTLY_C128, real, st), "facet check");
+    if (!rc) rc = launch_status(launch_src_sum_partials(a.partials, (long long)size, 1, result, st), "sum of partials");
+    return lease.release(rc);
+}
+
 }  // namespace
 
 extern "C" {
@@ -148,9 +173,15 @@ int swiftly_hip_check_subgrids_from_sources(int dtype, const void* sources, int6
 int swiftly_hip_facet_from_sources(int dtype, const void* sources, int64_t n_sources, int64_t image_size, int64_t size,
                                    int64_t off0, int64_t off1, const double* mask0, const double* mask1, void* out,
                                    int64_t out_row_stride, void* stream) {
-    SrcFacetArgs a;
-    if (int rc = facet_args(a, dtype, sources, n_sources, image_size, size, off0, off1, mask0, mask1, out, out_row_stride)) return rc;
-    return launch_status(launch_src_facet_store(a, dtype == SWIFTLY_C128, (hipStream_t)stream), "facet from sources");
+    return facet_from_sources(false, dtype, sources, n_sources, image_size, size, off0, off1, mask0, mask1, out, out_row_stride,
+                              (hipStream_t)stream);
+}
+
+int swiftly_hip_facet_from_sources_real(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
+                                        int64_t size, int64_t off0, int64_t off1, const double* mask0,
+                                        const double* mask1, void* out, int64_t out_row_stride, void* stream) {
+    return facet_from_sources(true, dtype, sources, n_sources, image_size, size, off0, off1, mask0, mask1, out, out_row_stride,
+                              (hipStream_t)stream);
 }
 
 int swiftly_hip_check_facet_from_sources(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
@@ -158,16 +189,17 @@ int swiftly_hip_check_facet_from_sources(int dtype, const void* sources, int64_t
                                          const double* mask1, const void* approx, int64_t approx_row_stride,
                                          const int32_t* row_start, const int32_t* row_sources, double* result,
                                          void* stream) {
-    SrcFacetArgs a;
-    if (int rc = facet_args(a, dtype, sources, n_sources, image_size, size, off0, off1, mask0, mask1, approx, approx_row_stride)) return rc;
-    if (!row_start || !result || (n_sources > 0 && !row_sources)) return fail(SWIFTLY_ERR_PARAM, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    ScratchLease lease;
-    if (int rc = lease.acquire(nullptr, 0, (size_t)size * 2 * sizeof(double), st, "facet check partial sums")) return rc;
-    a.row_start = row_start; a.row_srcs = row_sources; a.partials = (double*)lease.p;
-    int rc = launch_status(launch_src_facet_check(a, dtype == SWIFTLY_C128, st), "facet check");
-    if (!rc) rc = launch_status(launch_src_sum_partials(a.partials, (long long)size, 1, result, st), "sum of partials");
-    return lease.release(rc);
+    return check_facet_from_sources(false, dtype, sources, n_sources, image_size, size, off0, off1, mask0, mask1, approx,
+                                    approx_row_stride, row_start, row_sources, result, (hipStream_t)stream);
+}
+
+int swiftly_hip_check_facet_from_sources_real(int dtype, const void* sources, int64_t n_sources, int64_t image_size,
+                                              int64_t size, int64_t off0, int64_t off1, const double* mask0,
+                                              const double* mask1, const void* approx, int64_t approx_row_stride,
+                                              const int32_t* row_start, const int32_t* row_sources, double* result,
+                                              void* stream) {
+    return check_facet_from_sources(true, dtype, sources, n_sources, image_size, size, off0, off1, mask0, mask1, approx,
+                                    approx_row_stride, row_start, row_sources, result, (hipStream_t)stream);
 }
 
 }  // extern "C"

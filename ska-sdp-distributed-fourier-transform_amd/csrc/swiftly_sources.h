@@ -15,8 +15,14 @@
 // All arithmetic is float64 whatever the dtype of the output / the approximation; complex64 is rounded once on store
 // and widened exactly on load.  Every reduction runs in a fixed order (no floating-point atomics): results are
 // bit-reproducible from run to run.
+//
+// Real-valued images: the three facet kernels also take float / double elements.  The store writes Re(I) * mask0 * mask1,
+// the check takes the truth's imaginary part as zero and adds the squares in the order of the complex kernel, whose
+// sums for a facet with zero imaginary parts it reproduces bit for bit.
 #pragma once
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "swiftly_fft.h"  // cx<R>
 
@@ -220,6 +226,16 @@ struct SrcFacetArgs {
     double* partials;  // [size][2]
 };
 
+// element types of a facet: cx<float> / cx<double>, or float / double for a real-valued image
+template <typename OUT>
+constexpr bool kSrcReal = std::is_floating_point<OUT>::value;
+// (re, im) rounded once to OUT; a real element keeps re
+template <typename OUT>
+__device__ __forceinline__ OUT src_elem(double re, double im) {
+    if constexpr (kSrcReal<OUT>) return (OUT)re;
+    else return OUT{(decltype(OUT::x))re, (decltype(OUT::x))im};
+}
+
 // facet pixel of a source along one axis (reference fourier_algorithm.py:253-256): inside the facet when < size
 __device__ __forceinline__ long long src_pixel(long long c, long long org, long long N) { return src_pmod(c - org, N); }
 
@@ -228,7 +244,7 @@ template <typename OUT>
 __global__ void __launch_bounds__(256) src_facet_zero_kernel(SrcFacetArgs a) {
     const int per_row = (a.size + 255) / 256;
     const int c = (int)(blockIdx.x % per_row) * 256 + (int)threadIdx.x, row = (int)(blockIdx.x / per_row);
-    if (c < a.size) ((OUT*)a.data)[(size_t)row * a.row_stride + c] = OUT{0, 0};
+    if (c < a.size) ((OUT*)a.data)[(size_t)row * a.row_stride + c] = src_elem<OUT>(0.0, 0.0);
 }
 // grid (ceil(S / 256)): one source per thread; sources sit on distinct pixels, so plain stores suffice
 template <typename OUT>
@@ -240,7 +256,7 @@ __global__ void __launch_bounds__(256) src_facet_store_kernel(SrcFacetArgs a) {
     if (q0 >= a.size || q1 >= a.size) return;
     const double m0 = a.mask0 ? a.mask0[q0] : 1.0, m1 = a.mask1 ? a.mask1[q1] : 1.0;
     // (I * mask0) * mask1 per component, the order the reference multiplies in
-    ((OUT*)a.data)[(size_t)q0 * a.row_stride + q1] = OUT{(decltype(OUT::x))(r.re * m0 * m1), (decltype(OUT::x))(r.im * m0 * m1)};
+    ((OUT*)a.data)[(size_t)q0 * a.row_stride + q1] = src_elem<OUT>(r.re * m0 * m1, r.im * m0 * m1);
 }
 // grid (size): one workgroup streams one row and sums |truth - approx|^2 pixel by pixel -- never sum |approx|^2 with
 // corrections at the source pixels, which cancels completely for an approximation that is right to 1e-10
@@ -268,10 +284,20 @@ __global__ void __launch_bounds__(256) src_facet_check_kernel(SrcFacetArgs a) {
                 ti = r.im * m0 * m1;
             }
         }
-        const OUT v = p[c];
-        const double dr = tr - (double)v.x, di = ti - (double)v.y;
-        res += dr * dr + di * di;
-        tru += tr * tr + ti * ti;
+        if constexpr (kSrcReal<OUT>) {
+            // the complex kernel on zero imaginary parts adds round(dr * dr) [+ 0]: the product is rounded on its own
+            // here too, never contracted into the running sum
+#pragma clang fp contract(off)
+            const double dr = tr - (double)p[c];
+            const double d2 = dr * dr, t2 = tr * tr;
+            res += d2;
+            tru += t2;
+        } else {
+            const OUT v = p[c];
+            const double dr = tr - (double)v.x, di = ti - (double)v.y;
+            res += dr * dr + di * di;
+            tru += tr * tr + ti * ti;
+        }
     }
     src_block_sum2(res, tru, red);
     if (threadIdx.x == 0) {
@@ -284,7 +310,8 @@ __global__ void __launch_bounds__(256) src_facet_check_kernel(SrcFacetArgs a) {
 int launch_src_phase(const SrcPhaseArgs& a, int axis, int ndistinct, hipStream_t st);
 int launch_src_subgrids(const SrcSubgridArgs& a, int nsub, bool c128, bool check, hipStream_t st);
 int launch_src_sum_partials(const double* partials, long long n, int nitems, double* out, hipStream_t st);
-int launch_src_facet_store(const SrcFacetArgs& a, bool c128, hipStream_t st);
-int launch_src_facet_check(const SrcFacetArgs& a, bool c128, hipStream_t st);
+// (real: the elements of a.data are float / double instead of cx<float> / cx<double>)
+int launch_src_facet_store(const SrcFacetArgs& a, bool c128, bool real, hipStream_t st);
+int launch_src_facet_check(const SrcFacetArgs& a, bool c128, bool real, hipStream_t st);
 
 }  // namespace swf

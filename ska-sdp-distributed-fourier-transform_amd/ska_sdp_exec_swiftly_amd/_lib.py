@@ -200,6 +200,9 @@ def _declare(lib):
         # ... off0, off1, mask0, mask1, out / approx, row_stride, [row_start, row_sources, result,] stream)
         ("facet_from_sources", src + [i64, i64, vp, vp, vp, i64, vp]),
         ("check_facet_from_sources", src + [i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
+        # ... the same for a real-valued image: out / approx hold reals, the row stride counts reals
+        ("facet_from_sources_real", src + [i64, i64, vp, vp, vp, i64, vp]),
+        ("check_facet_from_sources_real", src + [i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
     ]:
         fn = getattr(lib, "swiftly_hip_" + name)
         fn.restype = c_int

@@ -97,23 +97,24 @@ class DeviceSources:
 
     # ------------------------------------------------------------------ marshalling
     @staticmethod
-    def _cdtype(dtype):
+    def _cdtype(dtype, real_ok=False):
+        """``dtype`` (torch or numpy) as a torch dtype: complex64 / complex128; ``real_ok``: float32 / float64 too"""
         torch = _torch()
-        if dtype in (torch.complex64, torch.complex128):
+        names = ("complex64", "complex128", "float32", "float64") if real_ok else ("complex64", "complex128")
+        if not isinstance(dtype, torch.dtype):
+            try:
+                dtype = getattr(torch, numpy.dtype(dtype).name, None)
+            except TypeError:
+                dtype = None
+        if dtype in [getattr(torch, name) for name in names]:
             return dtype
-        try:
-            kind = numpy.dtype(dtype)
-        except TypeError:
-            kind = None
-        if kind == numpy.complex64:
-            return torch.complex64
-        if kind == numpy.complex128:
-            return torch.complex128
-        raise ValueError(f"dtype must be complex64 or complex128, not {dtype!r}")
+        raise ValueError(f"dtype must be {' or '.join(names[:2])}{', float32 or float64' if real_ok else ''}, not {dtype!r}")
 
     @staticmethod
     def _code(dtype):
-        return _lib.C64 if dtype == _torch().complex64 else _lib.C128
+        """the library's precision code: C64 for complex64 and float32 data, C128 for complex128 and float64"""
+        torch = _torch()
+        return _lib.C64 if dtype in (torch.complex64, torch.float32) else _lib.C128
 
     def _stream(self):
         return ctypes.c_void_p(int(_torch().cuda.current_stream(self.device).cuda_stream))
@@ -139,20 +140,24 @@ class DeviceSources:
             hit = self._mask_cache[key] = _torch().from_numpy(host).to(self.device)
         return hit
 
-    def _approx(self, approx, ndim):
+    def _approx(self, approx, ndim, real_ok=False):
         """``approx`` as a complex device tensor with unit stride along the last axis: no copy for a contiguous or
-        row-strided device tensor; a host array is uploaded."""
+        row-strided device tensor; a host array is uploaded.  ``real_ok``: float32 / float64 pass as they are."""
         torch = _torch()
         if isinstance(approx, (list, tuple)):
             approx = torch.stack([self._approx(a, ndim - 1) for a in approx])
         if not isinstance(approx, torch.Tensor):
             approx = numpy.asarray(approx)
-            if not numpy.iscomplexobj(approx):
+            if real_ok and approx.dtype in (numpy.float32, numpy.float64):
+                pass
+            elif not numpy.iscomplexobj(approx):
                 raise ValueError(f"approx must be complex, not {approx.dtype}")
-            if approx.dtype not in (numpy.complex64, numpy.complex128):
+            elif approx.dtype not in (numpy.complex64, numpy.complex128):
                 approx = approx.astype(numpy.complex128)
             approx = torch.from_numpy(numpy.ascontiguousarray(approx)).to(self.device)
-        if approx.dtype not in (torch.complex64, torch.complex128):
+        if real_ok and approx.dtype in (torch.float32, torch.float64):
+            pass
+        elif approx.dtype not in (torch.complex64, torch.complex128):
             raise ValueError(f"approx must be complex64 or complex128, not {approx.dtype}")
         if approx.device != self.device:
             approx = approx.to(self.device)
@@ -164,9 +169,9 @@ class DeviceSources:
             approx = approx.contiguous()
         return approx
 
-    def _out(self, out, shape, dtype):
+    def _out(self, out, shape, dtype, real_ok=False):
         torch = _torch()
-        dtype = self._cdtype(dtype if out is None else out.dtype)
+        dtype = self._cdtype(dtype if out is None else out.dtype, real_ok)
         if out is None:
             return torch.empty(shape, dtype=dtype, device=self.device)
         if tuple(out.shape) != tuple(shape) or out.device != self.device:
@@ -248,22 +253,27 @@ class DeviceSources:
                 int(facet_config.off1), self._ptr(m0), self._ptr(m1)]
 
     def facet(self, facet_config, dtype=None, out=None):
-        """``[size, size]``: the facet holding the sources (reference ``make_facet``, api_helper.py:27-36)"""
+        """``[size, size]``: the facet holding the sources (reference ``make_facet``, api_helper.py:27-36).  ``dtype`` (or
+        ``out``) float32 / float64: the facet of a real-valued image as reals, bit for bit the real part of the complex
+        one (``swiftly_hip_facet_from_sources_real``) -- ``ValueError``, and nothing written, when an intensity has a
+        non-zero imaginary part."""
         torch = _torch()
         size = int(facet_config.size)
-        out = self._out(out, (size, size), torch.complex128 if dtype is None else dtype)
+        out = self._out(out, (size, size), torch.complex128 if dtype is None else dtype, real_ok=True)
+        entry = self._lib.swiftly_hip_facet_from_sources
+        if not out.dtype.is_complex:
+            if numpy.any(self.table["im"] != 0):
+                raise ValueError(f"a {out.dtype} facet needs real intensities: a source has a non-zero imaginary part")
+            entry = self._lib.swiftly_hip_facet_from_sources_real
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.swiftly_hip_facet_from_sources(
+            _lib.check(entry(
                 self._code(out.dtype), *self._facet_call(facet_config, size), self._ptr(out), out.stride(0), self._stream(),
             ))
         return out
 
-    def check_facet(self, facet_config, approx):
-        """RMSE between a computed facet and the one generated from the sources, as ``api_helper.check_facet``: every
-        pixel is differenced on its own (no cancellation between the facet's power and the sources')."""
+    def _facet_rows(self, facet_config, size):
+        """device ``(row_start, row_sources)`` of ``facet_row_lists`` for a facet of ``size`` pixels at these offsets (cached)"""
         torch = _torch()
-        approx = self._approx(approx, 2)
-        size = int(approx.shape[-1])
         key = (size, int(facet_config.off0), int(facet_config.off1))
         rows = self._row_cache.get(key)
         if rows is None:
@@ -272,10 +282,51 @@ class DeviceSources:
             start, srcs = facet_row_lists(self.table, self.image_size, size, key[1], key[2])
             srcs = numpy.concatenate([srcs, numpy.zeros(1, dtype=numpy.int32)])  # never an empty allocation
             rows = self._row_cache[key] = (torch.from_numpy(start).to(self.device), torch.from_numpy(srcs).to(self.device))
-        result = torch.zeros(2, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.swiftly_hip_check_facet_from_sources(
+        return rows
+
+    def _check_facet_into(self, facet_config, approx, result):
+        """enqueue the sums of one facet check into the two doubles ``result`` (complex or real ``approx``)"""
+        size = int(approx.shape[-1])
+        rows = self._facet_rows(facet_config, size)
+        entry = (self._lib.swiftly_hip_check_facet_from_sources if approx.dtype.is_complex
+                 else self._lib.swiftly_hip_check_facet_from_sources_real)
+        with _torch().cuda.device(self.device):
+            _lib.check(entry(
                 self._code(approx.dtype), *self._facet_call(facet_config, size), self._ptr(approx), approx.stride(0),
                 self._ptr(rows[0]), self._ptr(rows[1]), self._ptr(result), self._stream(),
             ))
-        return float(torch.sqrt(result[0]) / size)
+
+    def check_facet(self, facet_config, approx):
+        """RMSE between a computed facet and the one generated from the sources, as ``api_helper.check_facet``: every
+        pixel is differenced on its own (no cancellation between the facet's power and the sources')."""
+        torch = _torch()
+        approx = self._approx(approx, 2)
+        result = torch.zeros(2, dtype=torch.float64, device=self.device)
+        self._check_facet_into(facet_config, approx, result)
+        return float(torch.sqrt(result[0]) / int(approx.shape[-1]))
+
+    def check_facets(self, facet_configs, approx):
+        """float64 device tensor ``[n, 2]``: per facet the RMSE between ``approx[k]`` and the facet generated from the
+        sources, and the RMS of that truth -- the facet counterpart of :py:meth:`check_subgrids`, without a host
+        synchronisation per facet.  ``approx``: one ``[size, size]`` tensor per facet, complex64 / complex128 or, for a
+        real-valued image, float32 / float64 (the truth's imaginary part then counts as zero;
+        ``swiftly_hip_check_facet_from_sources_real``); device tensors with unit stride along their rows are read in
+        place.  For facets with zero imaginary parts the real form gives the bits of the complex one."""
+        torch = _torch()
+        facet_configs = list(facet_configs)
+        if isinstance(approx, torch.Tensor) or not isinstance(approx, (list, tuple)):
+            approx = list(approx)
+        if len(approx) != len(facet_configs):
+            raise ValueError(f"{len(facet_configs)} facet configurations for {len(approx)} facets")
+        for a in approx:  # (a facet is large: never gathered into a contiguous copy behind the caller's back)
+            if isinstance(a, torch.Tensor) and a.dim() == 2 and (a.stride(1) != 1 or a.stride(0) < a.shape[1]):
+                raise ValueError("check_facets reads facets in place: unit stride along the rows, rows that do not overlap")
+        approx = [self._approx(a, 2, real_ok=True) for a in approx]
+        result = torch.zeros((len(approx), 2), dtype=torch.float64, device=self.device)
+        for k, (cfg, a) in enumerate(zip(facet_configs, approx)):
+            if a.shape[-1]:
+                self._check_facet_into(cfg, a, result[k])
+        sizes = [max(int(a.shape[-1]), 1) for a in approx]
+        if len(set(sizes)) <= 1:
+            return torch.sqrt(result) / (sizes[0] if sizes else 1)  # sqrt(sum / size^2)
+        return torch.sqrt(result) / torch.tensor(sizes, dtype=torch.float64, device=self.device)[:, None]

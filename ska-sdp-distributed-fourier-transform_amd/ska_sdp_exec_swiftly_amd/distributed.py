@@ -310,6 +310,17 @@ def _plan_wave_keys(core, plan):
     return keys, band
 
 
+def _is_float32_facet(data):
+    """is ``data`` a facet that ``SwiftlyForward(facet_dtype=torch.float32)`` takes: a float32 host array, or a float32
+    2-D tensor with unit stride along its rows?"""
+    torch = _torch()
+    if data is None:
+        return False
+    if isinstance(data, torch.Tensor):
+        return data.dtype == torch.float32 and data.dim() == 2 and data.stride(-1) == 1
+    return numpy.asarray(data).dtype == numpy.float32
+
+
 class _CoopBands:
     """Column bookkeeping of the cooperative facets of one rank set: the band of the whole plan, the sub-band of every
     rank's wave range and where it sits inside the parity-split layout of the whole band (swiftly_rowpass.h): a band that
@@ -350,13 +361,29 @@ class DistributedForward:
     worked on cooperatively (:class:`FacetSharding`) -- every rank needs the rows ``sharding.coop_rows(size)`` of each
     of them in ``facet_data[j]`` (the whole facet is accepted too), :py:meth:`prepare_all_facets` runs K1 on them and the
     band-row exchange, and each wave's K2 / K3 of a cooperative facet runs on the rank that owns the wave.
-    ``cooperative=False`` keeps whole-facet ownership (facet ``j`` on rank ``j % world``)."""
+    ``cooperative=False`` keeps whole-facet ownership (facet ``j`` on rank ``j % world``).
+
+    **Real-valued facets** (``facet_dtype=torch.float32``, optionally ``half_length_k1=True``; parsed as in
+    :class:`SwiftlyForward`, same ``ValueError`` texts): this rank's float32 facets stay float32 -- the local object is a
+    ``SwiftlyForward`` with the same keywords, and the float32 row blocks of cooperative facets go to the device as they are
+    and through the real K1 of ``core.prepare_facet_band`` (the half-length form where it was asked for, the library has it,
+    the facet has an even size at an even position of the padded row and the block sits at an even pitch on an 8-byte-aligned
+    base; else the real-load form).  :py:attr:`facet_dtype` and :py:attr:`half_length_k1` say what happened; facets that are
+    not float32 run what they run without the keyword.  All ranks should pass the same keywords: the real-load form gives
+    the bits of the promoted facets, so a disagreement about it is harmless; the half-length form rounds differently
+    (within the same bound), so ranks that disagree about it mix roundings across the rows of a cooperative facet."""
 
     def __init__(self, swiftly_config, facet_configs, facet_data, lru_forward=1, group=None, subgrid_configs=None,
-                 wave_axis=None, dtype=None, rank_world=None, cooperative=True, whole_waves=False):
+                 wave_axis=None, dtype=None, rank_world=None, cooperative=True, whole_waves=False, facet_dtype=None,
+                 half_length_k1=False):
         from .api import SwiftlyForward, preferred_wave_axis  # pylint: disable=import-outside-toplevel
         from .forward import _PromotingForward  # pylint: disable=import-outside-toplevel
 
+        # (before anything touches the configuration or a device)
+        self._real_asked = SwiftlyForward._parse_facet_dtype(facet_dtype) is not None  # pylint: disable=protected-access
+        if half_length_k1 and not self._real_asked:
+            raise ValueError("half_length_k1=True needs facet_dtype=float32")
+        self._half_asked = bool(half_length_k1)
         torch = _torch()
         self.group = group
         # rank_world=(rank, world) overrides the process group: "virtual ranks" of one process, used with
@@ -393,13 +420,17 @@ class DistributedForward:
         local = self.sharding.local_facets
         self.local = None
         if local or not self.sharding.coop:
-            # (float32 facets are promoted here as in pack_coop: no real form in the multi-GPU classes)
-            self.local = _PromotingForward(
+            # float32 facets are promoted here as in pack_coop -- unless the caller said they are real-valued: then the local
+            # object keeps them float32 wherever its K1 form (k1_form.choose_k1) loads reals
+            keep = self._real_asked and bool(local) and all(_is_float32_facet(facet_data[j]) for j in local)
+            kw = dict(facet_dtype=torch.float32, half_length_k1=self._half_asked) if keep else {}
+            self.local = (SwiftlyForward if keep else _PromotingForward)(
                 swiftly_config,
                 [(self.facet_configs[j], facet_data[j]) for j in local],
                 lru_forward=lru_forward,
                 subgrid_configs=subgrid_configs,
                 wave_axis=wave_axis,
+                **kw,
             )
             if local and self.local.dtype != self.dtype:
                 raise ValueError(f"local facets are {self.local.dtype}, the pass was declared {self.dtype}")
@@ -437,6 +468,59 @@ class DistributedForward:
         for fwd in self._coop.values():
             fwd.set_wave_order(order)
 
+    @property
+    def facet_dtype(self):
+        """``torch.float32`` where this rank's facets -- the local ones and its row blocks of the cooperative ones -- stay
+        float32 (``facet_dtype=torch.float32`` was given, they are float32 and a K1 that loads reals exists), else the
+        complex dtype of the pass; also that on a rank that holds no facet data"""
+        forms = self._k1_forms()
+        return _torch().float32 if forms and all(real for real, _ in forms) else self.dtype
+
+    @property
+    def half_length_k1(self):
+        """does every K1 this rank runs (local facets, row blocks of cooperative facets) take the half-length form of real
+        rows?  False on a rank that runs no K1"""
+        forms = self._k1_forms()
+        return bool(forms) and all(half for _, half in forms)
+
+    def _k1_forms(self):
+        """``(stays float32, half-length)`` of every K1 this rank runs: the local object's, then one per cooperative block"""
+        forms = []
+        if self.local is not None and self.sharding.local_facets:
+            forms.append((self.local.facet_dtype == _torch().float32, bool(self.local.half_length_k1)))
+        for j in self.sharding.coop:
+            _, rows, block = self._coop_block(j)
+            if rows:
+                forms.append(self._coop_form(j, block))
+        return forms
+
+    def _coop_block(self, j):
+        """``(row0, rows, this rank's rows of cooperative facet j as the caller gave them)``"""
+        torch = _torch()
+        yB = self.facet_configs[j].size
+        row0, rows = self.sharding.coop_rows(yB)
+        data = self._coop_data[j]
+        if data is None or tuple(data.shape) not in ((yB, yB), (rows, yB)):
+            raise ValueError(f"rank {self.rank} needs the rows [{row0}, {row0 + rows}) of cooperative facet {j} "
+                             f"(shape ({rows}, {yB})) or the whole facet in facet_data[{j}]")
+        if not isinstance(data, torch.Tensor):
+            data = torch.as_tensor(data)
+        return row0, rows, data[row0 : row0 + rows] if data.shape[0] == yB and rows != yB else data
+
+    def _coop_form(self, j, block):
+        """``(stays float32, half-length)`` of K1 on a cooperative block: float32 rows stay float32 for a caller who asked
+        where the real K1 exists; the half-length form also needs the library to have it, a facet of even size at an even
+        position of the padded row and rows that load as aligned pairs (a block that is not on the device yet is uploaded
+        contiguous: its pitch is the facet size)"""
+        core, cfg = self.core, self.facet_configs[j]
+        real = bool(self._real_asked and block.dtype == _torch().float32 and self.dtype == _torch().complex64
+                    and core.supports_real_facets())
+        here = block.device == core.device and block.stride(1) == 1
+        pitch, base = (block.stride(0), block.data_ptr()) if here else (cfg.size, 0)
+        half = bool(real and self._half_asked and core.supports_real_facets_rfft() and cfg.size % 2 == 0
+                    and (int(cfg.off1) + core.yN_size // 2 - cfg.size // 2) % 2 == 0 and pitch % 2 == 0 and base % 8 == 0)
+        return real, half
+
     # -- cooperative facets: K1 on this rank's rows + the band-row exchange ----------------------------------------
     def pack_coop(self, j):
         """K1 of this rank's rows of cooperative facet ``j`` over the band of the whole plan, cut into the column
@@ -446,20 +530,19 @@ class DistributedForward:
         core, cb, sh = self.core, self._coop_bands, self.sharding
         cfg = self.facet_configs[j]
         yB = cfg.size
-        row0, rows = sh.coop_rows(yB)
-        data = self._coop_data[j]
-        if data is None or tuple(data.shape) not in ((yB, yB), (rows, yB)):
-            raise ValueError(f"rank {self.rank} needs the rows [{row0}, {row0 + rows}) of cooperative facet {j} "
-                             f"(shape ({rows}, {yB})) or the whole facet in facet_data[{j}]")
-        if not isinstance(data, torch.Tensor):
-            data = torch.as_tensor(data)
-        block = data[row0 : row0 + rows] if data.shape[0] == yB and rows != yB else data
-        block = block.to(device=core.device, dtype=self.dtype)
+        row0, rows, block = self._coop_block(j)
+        real, half = self._coop_form(j, block) if rows else (False, False)
+        if real:  # float32 to the device as it is: half the bytes of the upload and of what K1 reads
+            if block.device != core.device or block.stride(1) != 1:
+                block = block.contiguous().to(device=core.device)
+        else:
+            block = block.to(device=core.device, dtype=self.dtype)
         in_counts = [rows * 2 * cb.sub[d][1] for d in range(self.world)]
         out_counts = [sh.coop_rows(yB, s)[1] * 2 * cb.sub[self.rank][1] for s in range(self.world)]
         send = torch.empty(sum(in_counts), dtype=self.dtype, device=core.device)
         if rows:
-            part = core.prepare_facet_band(block, cfg.off1, cb.band, rows_of=(yB, row0))  # [rows, 2 * half]
+            # [rows, 2 * half columns of the band]
+            part = core.prepare_facet_band(block, cfg.off1, cb.band, rows_of=(yB, row0), half_length=half)
             pos = 0
             for d in range(self.world):
                 _, h, d2, w = cb.sub[d]
@@ -663,20 +746,39 @@ class DistributedBackward:
     accumulates them into a band accumulator over the columns of ITS waves; :py:meth:`finish` zero-fills the untouched
     columns, moves row blocks to the ranks that own them (one all-to-all: column ranges out, row blocks in, overlapping
     columns of neighbouring ranges added) and runs the contiguous-axis ``finish_facet`` on this rank's rows.  The pieces
-    are in ``coop_pieces`` = ``[(facet index, row0, tensor [rows, size])]`` after :py:meth:`finish`."""
+    are in ``coop_pieces`` = ``[(facet index, row0, tensor [rows, size])]`` after :py:meth:`finish`.
+
+    **Real-valued facets** (``facet_dtype``, ``half_length_finish``: parsed and refused as in :class:`SwiftlyBackward`): the
+    keywords go to the local ``SwiftlyBackward``, so :py:meth:`finish` returns real facets -- stored as float32 by the row
+    kernels on the band schedule (:py:attr:`real_finish_native`), the real part copied out per facet elsewhere
+    (``wave_axis=0``, this class's default).  The rows of cooperative facets are finished through
+    ``core.finish_facet_band(..., real=True)``: ``coop_pieces`` hold float32 row blocks, bit for bit the real parts -- or,
+    with ``half_length_finish=True`` where :py:attr:`half_length_finish` says so, the half-length form's values.  All
+    ranks should pass the same keywords."""
 
     MAX_IN_FLIGHT = 2
 
     # pylint: disable=too-many-arguments
     def __init__(self, swiftly_config, facet_configs, lru_backward=1, group=None, rank_world=None, wave_axis=0,
-                 subgrid_configs=None, dtype=None, cooperative=True, whole_waves=False):
+                 subgrid_configs=None, dtype=None, cooperative=True, whole_waves=False, facet_dtype=None,
+                 half_length_finish=False):
         from .api import SwiftlyBackward  # pylint: disable=import-outside-toplevel
         from .core_hip import band_range  # pylint: disable=import-outside-toplevel
 
         torch = _torch()
+        # (before anything touches the configuration or a device; the texts of SwiftlyBackward)
+        self._want_half_length = bool(half_length_finish)
+        self._facet_dtype = SwiftlyBackward._parse_facet_dtype(facet_dtype)  # pylint: disable=protected-access
+        if self._want_half_length and self._facet_dtype != torch.float32:
+            raise ValueError("half_length_finish=True needs facet_dtype=float32: the half-length finish produces real facets "
+                             f"from complex64 data, got facet_dtype={facet_dtype}")
         self.dtype = dtype if dtype is not None else torch.complex64
         if self.dtype not in (torch.complex64, torch.complex128):
             raise ValueError("dtype must be torch.complex64 or torch.complex128")
+        single = self._facet_dtype in (torch.float32, torch.complex64)
+        if self._facet_dtype is not None and single != (self.dtype == torch.complex64):
+            raise ValueError(f"DistributedBackward(facet_dtype={self._facet_dtype}) does not match {self.dtype} data: "
+                             "float32 / complex64 facets come from complex64 data, float64 / complex128 from complex128")
         self._started = []  # exchanges started and not yet finished, oldest first
         self.group = group
         self.wave_axis = int(wave_axis)
@@ -701,7 +803,8 @@ class DistributedBackward:
         if sh.local_facets or not sh.coop:
             self.local = SwiftlyBackward(
                 swiftly_config, [self.facet_configs[j] for j in sh.local_facets], lru_backward=lru_backward,
-                wave_axis=self.wave_axis, subgrid_configs=subgrid_configs,
+                wave_axis=self.wave_axis, subgrid_configs=subgrid_configs, facet_dtype=self._facet_dtype,
+                half_length_finish=self._want_half_length,
             )
             self.local.dtype = self.dtype
         # subgrid holder side: contributions to ALL facets, owner-major order (cooperative facets last)
@@ -731,6 +834,38 @@ class DistributedBackward:
                                          subgrid_configs=my_plan)
                     cb.dtype = self.dtype
                     self._coop[j] = cb
+
+    @property
+    def facet_dtype(self):
+        """dtype of the facets :py:meth:`finish` returns and of the ``coop_pieces``: the ``facet_dtype`` asked for, else
+        the complex dtype of the pass"""
+        return self._facet_dtype if self._facet_dtype is not None else self.dtype
+
+    @property
+    def real_finish_native(self):
+        """do the finishing row kernels store float32 themselves (``SwiftlyBackward.real_finish_native``; a rank without a
+        local object answers from the same rule)?  False: complex finish and a copy of the real part, or complex facets"""
+        if self.local is not None:
+            return self.local.real_finish_native
+        return self._coop_real_native()
+
+    @property
+    def half_length_finish(self):
+        """does every contiguous-axis finish this rank runs -- the local object's and that of its rows of the cooperative
+        facets -- take the half-length form (``SwiftlyBackward.half_length_finish``)?"""
+        answers = [bool(self.local.half_length_finish)] if self.local is not None else []
+        answers += [self._coop_half(self.facet_configs[j]) for j in self.sharding.coop]
+        return bool(answers) and all(answers)
+
+    def _coop_real_native(self):
+        """the rule of ``SwiftlyBackward.real_finish_native`` for the rows of cooperative facets (band schedule)"""
+        return bool(self.wave_axis == 1 and self._facet_dtype == _torch().float32 and self.core.supports_real_facets_out())
+
+    def _coop_half(self, cfg):
+        """the rule of ``SwiftlyBackward.half_length_finish`` for one cooperative facet: asked for, real store, the library
+        has the form, an even size at an even position of the padded row"""
+        return bool(self._want_half_length and self._coop_real_native() and self.core.supports_real_facets_out_c2r()
+                    and cfg.size % 2 == 0 and (self.core.yN_size // 2 - cfg.size // 2 + int(cfg.off1)) % 2 == 0)
 
     def wave_key(self, sgs):
         """key of the wave ``sgs`` (``off1`` in the band schedule, else ``off0``)"""
@@ -914,7 +1049,7 @@ class DistributedBackward:
         cfg = self.facet_configs[j]
         row0, rows = sh.coop_rows(cfg.size)
         if rows == 0:
-            return (j, row0, torch.empty((0, cfg.size), dtype=self.dtype, device=core.device))
+            return (j, row0, torch.empty((0, cfg.size), dtype=self.facet_dtype, device=core.device))
         buf = torch.zeros((rows, self._coop_band[1]), dtype=self.dtype, device=core.device)
         pos = 0
         for s in range(self.world):
@@ -922,7 +1057,14 @@ class DistributedBackward:
             if n:
                 buf[:, c0 : c0 + n] += recv[pos : pos + rows * n].view(rows, n)
             pos += rows * n
-        out = core.finish_facet_band(buf, self._coop_band, cfg.off1, cfg.size, mask=cfg.mask1)
+        if self._coop_real_native():
+            # float32 rows straight from the row kernel (a half-length call the core refuses is an error, not a fallback)
+            out = core.finish_facet_band(buf, self._coop_band, cfg.off1, cfg.size, mask=cfg.mask1, real=True,
+                                         half_length=self._coop_half(cfg))
+        else:
+            out = core.finish_facet_band(buf, self._coop_band, cfg.off1, cfg.size, mask=cfg.mask1)
+            if not self.facet_dtype.is_complex:
+                out = out.real.contiguous()
         return (j, row0, out)
 
     def finish(self):

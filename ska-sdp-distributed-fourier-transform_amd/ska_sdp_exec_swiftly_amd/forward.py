@@ -58,7 +58,8 @@ class SwiftlyForward(WavePrefetch):
         the real window-rows form of the whole-row K1, ``core.supports_window_rows(..., real=True)``), which the default
         leaves on promoted complex64 facets.  Every facet must then be float32 (``ValueError`` otherwise).  Where no real K1
         exists (``wave_axis=0``, ``yN_size`` = Q * 2^k, facets above 23552 pixels at ``yN_size`` 32768, device rows that
-        are not 8-byte aligned at an even pitch under the accurate order, the multi-GPU classes) the facets are promoted as
+        are not 8-byte aligned at an even pitch under the accurate order, the multi-GPU classes without their own
+        ``facet_dtype`` keyword) the facets are promoted as
         before and :py:attr:`facet_dtype` says complex64.  The results are those of the promoted facets bit for bit.
         Any other value: ``ValueError``
     :param half_length_k1: ``True`` (with ``facet_dtype=float32``, ``ValueError`` without): K1 of the real facets as ONE
@@ -750,7 +751,8 @@ class SwiftlyForward(WavePrefetch):
 
 
 class _PromotingForward(SwiftlyForward):
-    """``SwiftlyForward`` as the multi-GPU classes own it: float32 facets are always promoted to complex64"""
+    """``SwiftlyForward`` as the multi-GPU classes own it without ``facet_dtype=torch.float32``: float32 facets are always
+    promoted to complex64"""
 
     _keep_real_facets = False
 
