@@ -7,7 +7,8 @@ import logging
 
 import numpy
 
-from . import _lib
+from . import _lib, facet_dtype as fdt
+from .b8_form import B8Facts, choose_b8
 from .core_hip import band_range
 from .ingest import _mask_table
 from .tasks import DeviceTask, LRUCache, TaskQueue, _torch, _unwrap
@@ -58,9 +59,7 @@ class SwiftlyBackward:
                  subgrid_configs=None, wave_axis=None, delayed=False, dtype=None, facet_dtype=None, half_length_finish=False):
         # (before anything touches the configuration or a device)
         self._want_half_length = bool(half_length_finish)
-        if self._want_half_length and self._parse_facet_dtype(facet_dtype) != _torch().float32:
-            raise ValueError("half_length_finish=True needs facet_dtype=float32: the half-length finish produces real facets "
-                             f"from complex64 data, got facet_dtype={facet_dtype}")
+        self._facet_dtype = fdt.backward_keywords(facet_dtype, self._want_half_length)
         self.delayed = bool(delayed)  # finish() hands out DeviceTask handles instead of bare device tensors
         # wave_axis=None: the reference's schedule, unless the caller hands over the plan of subgrids it will add and
         # the band kernels exist -- decided when the first subgrid shows the dtype (complex64 only)
@@ -99,36 +98,11 @@ class SwiftlyBackward:
             # an explicit request for the band schedule is answered at once (complex128: the explicit gate)
             if self.wave_axis == 1 and not self._auto_axis and not self.core.supports_backward_band(dtype, explicit=True):
                 raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={dtype}): {_lib.last_error()}")
-        self._facet_dtype = self._parse_facet_dtype(facet_dtype)
-        if self._fixed_dtype is not None:
-            self._check_facet_dtype(self._fixed_dtype)
-
-    @staticmethod
-    def _parse_facet_dtype(facet_dtype):
-        """``facet_dtype`` as a torch dtype: one of float32, float64, complex64, complex128, or None"""
-        if facet_dtype is None:
-            return None
-        torch = _torch()
-        if not isinstance(facet_dtype, torch.dtype):
-            try:
-                facet_dtype = {numpy.dtype(numpy.float32): torch.float32, numpy.dtype(numpy.float64): torch.float64,
-                               numpy.dtype(numpy.complex64): torch.complex64,
-                               numpy.dtype(numpy.complex128): torch.complex128}.get(numpy.dtype(facet_dtype))
-            except TypeError:
-                facet_dtype = None
-        if facet_dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
-            raise ValueError("facet_dtype must be float32, float64, complex64, complex128 or None")
-        return facet_dtype
+            self._check_facet_dtype(dtype)
 
     def _check_facet_dtype(self, data_dtype):
         """``facet_dtype`` has the precision of the data (called wherever the data's dtype becomes known)"""
-        torch = _torch()
-        if self._facet_dtype is None:
-            return
-        single = data_dtype in (torch.complex64, torch.float32)
-        if (self._facet_dtype in (torch.float32, torch.complex64)) != single:
-            raise ValueError(f"SwiftlyBackward(facet_dtype={self._facet_dtype}) does not match {data_dtype} data: "
-                             "float32 / complex64 facets come from complex64 data, float64 / complex128 from complex128")
+        fdt.check_precision("SwiftlyBackward", self._facet_dtype, data_dtype)
 
     @property
     def facet_dtype(self):
@@ -136,20 +110,27 @@ class SwiftlyBackward:
         (``None`` while no data has shown it)"""
         return self._facet_dtype if self._facet_dtype is not None else self.dtype
 
-    @property
-    def _real_facets(self):
-        return self._facet_dtype is not None and not self._facet_dtype.is_complex
+    def _decide_b8(self, accumulators=None):
+        """The B8 form of this object: gathers the facts of ``b8_form.B8Facts`` and asks ``b8_form.choose_b8``.  Asked on every
+        read, never stored: the schedule may still be open.  ``accumulators``: the band accumulators a finish is about to
+        read (:py:meth:`_finish_bands`); the properties answer for the object."""
+        # (``reals`` / ``half``: only then does what is asked of the library and of the facets matter)
+        core = self.core
+        reals = not self._auto_axis and self.wave_axis == 1 and self._facet_dtype == _torch().float32
+        half = reals and self._want_half_length
+        return choose_b8(B8Facts(
+            resolved=not self._auto_axis, wave_axis=self.wave_axis, facet_dtype=fdt.name_of(self._facet_dtype),
+            half_length_asked=self._want_half_length, real_facets_out=reals and core.supports_real_facets_out(),
+            real_facets_out_c2r=half and core.supports_real_facets_out_c2r(),
+            pairs=half and all(fdt.loads_as_pairs(cfg.size, cfg.off1, core.yN_size) for cfg in self.facets_config_list),
+            accumulators_complex64=None if accumulators is None else accumulators.dtype == _torch().complex64))
 
     @property
     def real_finish_native(self):
         """By which path :py:meth:`finish` produces real facets: True = the finishing row kernels store float32 (band
         schedule, complex64, ``core.supports_real_facets_out()``), False = complex finish and a copy of the real part per
         facet (also: the facets are complex).  ``None`` until the schedule is resolved."""
-        if self._auto_axis:
-            return None
-        if not self._real_facets:
-            return False
-        return bool(self.wave_axis == 1 and self._facet_dtype == _torch().float32 and self.core.supports_real_facets_out())
+        return self._decide_b8().native
 
     @property
     def half_length_finish(self):
@@ -157,13 +138,13 @@ class SwiftlyBackward:
         (``half_length_finish=True``), :py:attr:`real_finish_native` holds, ``core.supports_real_facets_out_c2r()``, and every
         facet has an even size at an even position of the padded row (the kernel stores aligned pairs of pixels).
         Otherwise False: the real-store form, bit for bit what the pass gives without the keyword."""
-        if not (self._want_half_length and self.real_finish_native and self.core.supports_real_facets_out_c2r()):
-            return False
-        yN = self.core.yN_size
-        return all(cfg.size % 2 == 0 and (yN // 2 - cfg.size // 2 + cfg.off1) % 2 == 0 for cfg in self.facets_config_list)
+        return self._decide_b8().half_length
 
-    def _real_part(self, facet):
-        """the real part of a finished complex facet as a tensor of its own (the caller drops the complex one)"""
+    def _handed_out(self, facet):
+        """a facet finished complex as :py:meth:`finish` hands it out: itself, or -- real facets -- its real part as a tensor of
+        its own.  The caller keeps no name for the complex one: it is gone before the next facet is finished"""
+        if not self._decide_b8().real_facets:
+            return facet
         self._check_facet_dtype(facet.dtype)  # (contributions handed straight to accumulate_wave show their dtype only here)
         return facet.real.contiguous()
 
@@ -523,16 +504,14 @@ class SwiftlyBackward:
             dt = self.facet_dtype or torch.complex64
             return [torch.zeros((cfg.size, cfg.size), dtype=dt, device=core.device) for cfg in self.facets_config_list]
         core.band_zero_untouched(self._bands, self._touched)
-        native = self.real_finish_native and self._bands.dtype == torch.complex64
-        half = bool(native and self.half_length_finish)
+        form = self._decide_b8(self._bands)
         for j, cfg in enumerate(self.facets_config_list):
-            if native:  # float32 straight from the row kernels: no complex facet exists
+            if form.native:  # float32 straight from the row kernels: no complex facet exists
                 out.append(core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1, real=True,
-                                                  half_length=half))
-                continue
-            facet = core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1)
-            out.append(self._real_part(facet) if self._real_facets else facet)
-            del facet  # (real facets: the complex one is gone before the next is finished)
+                                                  half_length=form.half_length))
+            else:
+                out.append(self._handed_out(core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size,
+                                                                   mask=cfg.mask1)))
         self._bands = None
         self._work = None
         return out
@@ -573,8 +552,6 @@ class SwiftlyBackward:
                 dt = self.facet_dtype or torch.complex64
                 out.append(torch.zeros((cfg.size, cfg.size), dtype=dt, device=core.device))
             else:
-                facet = core.finish_facet(acc, cfg.off0, cfg.size, axis=0, mask=cfg.mask0)
-                out.append(self._real_part(facet) if self._real_facets else facet)
-                del facet  # (real facets: the complex one is gone before the next is finished)
+                out.append(self._handed_out(core.finish_facet(acc, cfg.off0, cfg.size, axis=0, mask=cfg.mask0)))
         self.task_queue.wait_all_done()
         return [DeviceTask(t) for t in out] if self.delayed else out

@@ -675,6 +675,10 @@ class SwiftlyCoreHip:
         ("window_rows", True): "prepare_facet_window_rows", ("real_window_rows", True): "prepare_facet_window_rows_real",
     }
 
+    #: the C entry point of the backward contiguous-axis finish (B8), by (real facets, half-length form)
+    _B8_ENTRY = {(False, False): "finish_facet_band", (True, False): "finish_facet_band_real",
+                 (True, True): "finish_facet_band_c2r"}
+
     def _k1_call(self, form, facet, out, out_row_stride, facet_off, band, fold_other_axis_window, rows_of, windows=()):
         """the one native K1 call: ``facet`` (float32 in the real forms, whose dtype code is that of the output) into ``out``;
         ``rows_of``: ``(size, row0)`` of the row block or None; ``windows``: the trailing arguments of the window-rows forms"""
@@ -1142,9 +1146,7 @@ class SwiftlyCoreHip:
             raise ValueError(f"finish_facet_band(real=True): `out` must be [{rows}, {int(facet_size)}] with unit column stride")
         mvec = self._real_vec(mask, band_acc.dtype, int(facet_size)) if mask is not None else None
         cvp = ctypes.c_void_p
-        entry = self._lib.swiftly_hip_finish_facet_band_real if real else self._lib.swiftly_hip_finish_facet_band
-        if half_length:
-            entry = self._lib.swiftly_hip_finish_facet_band_c2r
+        entry = getattr(self._lib, "swiftly_hip_" + self._B8_ENTRY[bool(real), bool(half_length)])
         _lib.check(
             entry(
                 self._handle, self._code(band_acc), cvp(band_acc.data_ptr()), rows, band_acc.stride(0), int(band[0]),

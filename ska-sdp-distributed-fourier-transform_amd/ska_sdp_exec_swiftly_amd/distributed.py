@@ -27,6 +27,10 @@ partitioning / ordering is covered by world_size-2/3 gloo tests on CPU
 """
 import numpy
 
+from . import facet_dtype as fdt
+from .b8_form import B8Facts, choose_b8
+from .k1_form import K1Facts, choose_k1
+
 __all__ = [
     "FacetSharding",
     "exchange_contributions",
@@ -310,15 +314,18 @@ def _plan_wave_keys(core, plan):
     return keys, band
 
 
-def _is_float32_facet(data):
-    """is ``data`` a facet that ``SwiftlyForward(facet_dtype=torch.float32)`` takes: a float32 host array, or a float32
-    2-D tensor with unit stride along its rows?"""
-    torch = _torch()
-    if data is None:
-        return False
-    if isinstance(data, torch.Tensor):
-        return data.dtype == torch.float32 and data.dim() == 2 and data.stride(-1) == 1
-    return numpy.asarray(data).dtype == numpy.float32
+def _cooperative_plan(core, cooperative, wave_axis, plan, world, facet_configs, dtype):
+    """``(wave keys in band order, band of the plan)`` when the ``len(facet_configs) % world`` leftover facets of a pass are
+    worked on cooperatively (:class:`FacetSharding`), else ``(None, None)``: the complex64 band schedule with a plan whose waves
+    have sub-bands to hand out, on more than one rank, with facets of one size"""
+    if not (cooperative and wave_axis == 1 and plan and world > 1 and len(facet_configs) % world
+            and dtype == _torch().complex64 and core.band_for_offsets([plan[0].off1]) != (0, core.yN_size)
+            and len({c.size for c in facet_configs}) == 1):
+        return None, None
+    keys, band = _plan_wave_keys(core, plan)
+    if band == (0, core.yN_size):
+        return None, None  # the plan needs the whole padded axis: no sub-bands to hand out
+    return keys, band
 
 
 class _CoopBands:
@@ -380,9 +387,7 @@ class DistributedForward:
         from .forward import _PromotingForward  # pylint: disable=import-outside-toplevel
 
         # (before anything touches the configuration or a device)
-        self._real_asked = SwiftlyForward._parse_facet_dtype(facet_dtype) is not None  # pylint: disable=protected-access
-        if half_length_k1 and not self._real_asked:
-            raise ValueError("half_length_k1=True needs facet_dtype=float32")
+        self._real_asked = fdt.forward_keywords(facet_dtype, half_length_k1) is not None
         self._half_asked = bool(half_length_k1)
         torch = _torch()
         self.group = group
@@ -407,14 +412,9 @@ class DistributedForward:
                 f"wave_axis=1 needs the fused subgrid side (complex64, <= {self.core.MAX_FUSED_FACETS} facets in total); "
                 "use wave_axis=0 (preferred_wave_axis(config, dtype, n_facets=...) says which)"
             )
-        keys = None
         self._plan = list(subgrid_configs) if subgrid_configs is not None else None
-        if (cooperative and self.wave_axis == 1 and self._plan and self.world > 1 and len(self.facet_configs) % self.world
-                and self.core.band_for_offsets([self._plan[0].off1]) != (0, self.core.yN_size)
-                and len({c.size for c in self.facet_configs}) == 1):
-            keys, band = _plan_wave_keys(self.core, self._plan)
-            if band == (0, self.core.yN_size):
-                keys = None  # the plan needs the whole padded axis: no sub-bands to hand out
+        keys, band = _cooperative_plan(self.core, cooperative, self.wave_axis, self._plan, self.world, self.facet_configs,
+                                       self.dtype)
         self.sharding = _shared_sharding(self.core, len(self.facet_configs), self.rank, self.world, keys,
                                          _wave_sizes(self._plan, self.wave_axis) if whole_waves else None)
         local = self.sharding.local_facets
@@ -422,7 +422,7 @@ class DistributedForward:
         if local or not self.sharding.coop:
             # float32 facets are promoted here as in pack_coop -- unless the caller said they are real-valued: then the local
             # object keeps them float32 wherever its K1 form (k1_form.choose_k1) loads reals
-            keep = self._real_asked and bool(local) and all(_is_float32_facet(facet_data[j]) for j in local)
+            keep = self._real_asked and bool(local) and all(fdt.is_float32_facet(facet_data[j]) for j in local)
             kw = dict(facet_dtype=torch.float32, half_length_k1=self._half_asked) if keep else {}
             self.local = (SwiftlyForward if keep else _PromotingForward)(
                 swiftly_config,
@@ -491,7 +491,8 @@ class DistributedForward:
         for j in self.sharding.coop:
             _, rows, block = self._coop_block(j)
             if rows:
-                forms.append(self._coop_form(j, block))
+                form = self._coop_form(j, block)
+                forms.append((form.facets_real, form.half_length))
         return forms
 
     def _coop_block(self, j):
@@ -508,18 +509,25 @@ class DistributedForward:
         return row0, rows, data[row0 : row0 + rows] if data.shape[0] == yB and rows != yB else data
 
     def _coop_form(self, j, block):
-        """``(stays float32, half-length)`` of K1 on a cooperative block: float32 rows stay float32 for a caller who asked
-        where the real K1 exists; the half-length form also needs the library to have it, a facet of even size at an even
-        position of the padded row and rows that load as aligned pairs (a block that is not on the device yet is uploaded
-        contiguous: its pitch is the facet size)"""
+        """The K1 form of a cooperative block (``k1_form.K1Answer``: stays float32, half-length; the mode is 0): gathers the
+        ``k1_form.K1Facts`` of the block and asks ``k1_form.choose_k1``.  The band comes from the exchange, so no axis-1-first
+        mode is open; a block that is not on the device yet is uploaded contiguous, so it counts as aligned at an even pitch
+        where the facet size is even"""
         core, cfg = self.core, self.facet_configs[j]
-        real = bool(self._real_asked and block.dtype == _torch().float32 and self.dtype == _torch().complex64
-                    and core.supports_real_facets())
+        complex64, float32 = self.dtype == _torch().complex64, block.dtype == _torch().float32
+        # (only then does what is asked of the library matter)
+        reals = self._real_asked and float32 and complex64 and core.supports_real_facets()
         here = block.device == core.device and block.stride(1) == 1
         pitch, base = (block.stride(0), block.data_ptr()) if here else (cfg.size, 0)
-        half = bool(real and self._half_asked and core.supports_real_facets_rfft() and cfg.size % 2 == 0
-                    and (int(cfg.off1) + core.yN_size // 2 - cfg.size // 2) % 2 == 0 and pitch % 2 == 0 and base % 8 == 0)
-        return real, half
+        return choose_k1(K1Facts(
+            wave_axis=1, complex64=complex64, all_float32=float32, float32_asked=self._real_asked,
+            half_length_asked=self._half_asked, keeps_real=self._real_asked, axis1_first=False, axis1_fused=False, planned=True,
+            # (the half-length form exists only where the real-load form does)
+            real_facets=reals, real_facets_rfft=reals and core.supports_real_facets_rfft(),
+            # (``core.prepare_facet_band`` promotes a block above 23552 points on the device itself: the block still travels as
+            # float32 and ``facet_dtype`` says float32)
+            rows_match_promoted=True, even=fdt.loads_as_pairs(cfg.size, cfg.off1, core.yN_size),
+            aligned=pitch % 2 == 0 and base % 8 == 0))
 
     # -- cooperative facets: K1 on this rank's rows + the band-row exchange ----------------------------------------
     def pack_coop(self, j):
@@ -531,7 +539,7 @@ class DistributedForward:
         cfg = self.facet_configs[j]
         yB = cfg.size
         row0, rows, block = self._coop_block(j)
-        real, half = self._coop_form(j, block) if rows else (False, False)
+        real, half = self._coop_form(j, block)[:2] if rows else (False, False)
         if real:  # float32 to the device as it is: half the bytes of the upload and of what K1 reads
             if block.device != core.device or block.stride(1) != 1:
                 block = block.contiguous().to(device=core.device)
@@ -766,19 +774,13 @@ class DistributedBackward:
         from .core_hip import band_range  # pylint: disable=import-outside-toplevel
 
         torch = _torch()
-        # (before anything touches the configuration or a device; the texts of SwiftlyBackward)
+        # (before anything touches the configuration or a device)
         self._want_half_length = bool(half_length_finish)
-        self._facet_dtype = SwiftlyBackward._parse_facet_dtype(facet_dtype)  # pylint: disable=protected-access
-        if self._want_half_length and self._facet_dtype != torch.float32:
-            raise ValueError("half_length_finish=True needs facet_dtype=float32: the half-length finish produces real facets "
-                             f"from complex64 data, got facet_dtype={facet_dtype}")
+        self._facet_dtype = fdt.backward_keywords(facet_dtype, self._want_half_length)
         self.dtype = dtype if dtype is not None else torch.complex64
         if self.dtype not in (torch.complex64, torch.complex128):
             raise ValueError("dtype must be torch.complex64 or torch.complex128")
-        single = self._facet_dtype in (torch.float32, torch.complex64)
-        if self._facet_dtype is not None and single != (self.dtype == torch.complex64):
-            raise ValueError(f"DistributedBackward(facet_dtype={self._facet_dtype}) does not match {self.dtype} data: "
-                             "float32 / complex64 facets come from complex64 data, float64 / complex128 from complex128")
+        fdt.check_precision("DistributedBackward", self._facet_dtype, self.dtype)
         self._started = []  # exchanges started and not yet finished, oldest first
         self.group = group
         self.wave_axis = int(wave_axis)
@@ -788,13 +790,8 @@ class DistributedBackward:
         self.core = core = swiftly_config.core
         self.facet_configs = list(facet_configs)
         plan = list(subgrid_configs) if subgrid_configs is not None else None
-        keys = None
-        if (cooperative and self.wave_axis == 1 and plan and self.world > 1 and len(self.facet_configs) % self.world
-                and self.dtype == torch.complex64 and core.band_for_offsets([plan[0].off1]) != (0, core.yN_size)
-                and len({c.size for c in self.facet_configs}) == 1):
-            keys, band = _plan_wave_keys(core, plan)  # the same wave ranges as DistributedForward
-            if band == (0, core.yN_size):
-                keys = None
+        # (the same wave ranges as DistributedForward)
+        keys, _ = _cooperative_plan(core, cooperative, self.wave_axis, plan, self.world, self.facet_configs, self.dtype)
         self.sharding = _shared_sharding(core, len(self.facet_configs), self.rank, self.world, keys,
                                          _wave_sizes(plan, self.wave_axis) if whole_waves else None)
         sh = self.sharding
@@ -847,25 +844,27 @@ class DistributedBackward:
         local object answers from the same rule)?  False: complex finish and a copy of the real part, or complex facets"""
         if self.local is not None:
             return self.local.real_finish_native
-        return self._coop_real_native()
+        return self._coop_b8().native
 
     @property
     def half_length_finish(self):
         """does every contiguous-axis finish this rank runs -- the local object's and that of its rows of the cooperative
         facets -- take the half-length form (``SwiftlyBackward.half_length_finish``)?"""
         answers = [bool(self.local.half_length_finish)] if self.local is not None else []
-        answers += [self._coop_half(self.facet_configs[j]) for j in self.sharding.coop]
+        answers += [self._coop_b8(self.facet_configs[j]).half_length for j in self.sharding.coop]
         return bool(answers) and all(answers)
 
-    def _coop_real_native(self):
-        """the rule of ``SwiftlyBackward.real_finish_native`` for the rows of cooperative facets (band schedule)"""
-        return bool(self.wave_axis == 1 and self._facet_dtype == _torch().float32 and self.core.supports_real_facets_out())
-
-    def _coop_half(self, cfg):
-        """the rule of ``SwiftlyBackward.half_length_finish`` for one cooperative facet: asked for, real store, the library
-        has the form, an even size at an even position of the padded row"""
-        return bool(self._want_half_length and self._coop_real_native() and self.core.supports_real_facets_out_c2r()
-                    and cfg.size % 2 == 0 and (self.core.yN_size // 2 - cfg.size // 2 + int(cfg.off1)) % 2 == 0)
+    def _coop_b8(self, cfg=None):
+        """The B8 form of the rows of cooperative facet ``cfg`` (``b8_form.choose_b8`` on the facts of that one facet) as the
+        class runs them: on the band schedule, from complex64 accumulators.  Without a facet: of a facet that can be stored as
+        pairs"""
+        core, asked = self.core, fdt.name_of(self._facet_dtype)
+        reals = asked == "float32" and core.supports_real_facets_out()
+        half = reals and self._want_half_length and core.supports_real_facets_out_c2r()
+        return choose_b8(B8Facts(
+            resolved=True, wave_axis=self.wave_axis, facet_dtype=asked, half_length_asked=self._want_half_length,
+            real_facets_out=reals, real_facets_out_c2r=half,
+            pairs=cfg is None or fdt.loads_as_pairs(cfg.size, cfg.off1, core.yN_size)))
 
     def wave_key(self, sgs):
         """key of the wave ``sgs`` (``off1`` in the band schedule, else ``off0``)"""
@@ -1057,14 +1056,12 @@ class DistributedBackward:
             if n:
                 buf[:, c0 : c0 + n] += recv[pos : pos + rows * n].view(rows, n)
             pos += rows * n
-        if self._coop_real_native():
-            # float32 rows straight from the row kernel (a half-length call the core refuses is an error, not a fallback)
-            out = core.finish_facet_band(buf, self._coop_band, cfg.off1, cfg.size, mask=cfg.mask1, real=True,
-                                         half_length=self._coop_half(cfg))
-        else:
-            out = core.finish_facet_band(buf, self._coop_band, cfg.off1, cfg.size, mask=cfg.mask1)
-            if not self.facet_dtype.is_complex:
-                out = out.real.contiguous()
+        # native: float32 rows straight from the row kernel (a half-length call the core refuses is an error, not a fallback)
+        form = self._coop_b8(cfg)
+        out = core.finish_facet_band(buf, self._coop_band, cfg.off1, cfg.size, mask=cfg.mask1, real=bool(form.native),
+                                     half_length=form.half_length)
+        if form.real_facets and not form.native:
+            out = out.real.contiguous()
         return (j, row0, out)
 
     def finish(self):

@@ -7,10 +7,9 @@ import logging
 import os
 from functools import cached_property
 
-import numpy
-
 from . import _lib, slabs
 from .core_hip import band_range
+from .facet_dtype import forward_keywords, loads_as_pairs
 from .ingest import _FacetIngest, _mask_table
 from .k1_form import K1Facts, axis1_active, choose_k1, may_fuse
 from .prefetch import WavePrefetch, _knobs
@@ -76,9 +75,7 @@ class SwiftlyForward(WavePrefetch):
         self, swiftly_config, facet_tasks, lru_forward=1, queue_size=20, client=None, subgrid_configs=None,
         wave_axis=None, delayed=False, facet_dtype=None, half_length_k1=False,
     ):
-        self._facet_dtype_asked = self._parse_facet_dtype(facet_dtype)
-        if half_length_k1 and self._facet_dtype_asked is None:
-            raise ValueError("half_length_k1=True needs facet_dtype=float32")
+        self._facet_dtype_asked = forward_keywords(facet_dtype, half_length_k1)
         self._half_length_asked, self._k1 = bool(half_length_k1), None  # (the K1 form: _decide_k1)
         WavePrefetch.__init__(self)
         self.delayed = bool(delayed)  # hand out DeviceTask handles instead of bare device tensors
@@ -159,22 +156,6 @@ class SwiftlyForward(WavePrefetch):
         exists and every facet can be loaded as pairs)?"""
         return self._k1.half_length
 
-    @staticmethod
-    def _parse_facet_dtype(facet_dtype):
-        """``facet_dtype`` as given to the constructor: ``None``, or float32 (torch dtype, or anything ``numpy.dtype`` reads
-        as float32, parsed as in ``SwiftlyBackward._parse_facet_dtype``) -> ``torch.float32``; ``ValueError`` otherwise"""
-        if facet_dtype is None:
-            return None
-        torch = _torch()
-        if not isinstance(facet_dtype, torch.dtype):
-            try:
-                facet_dtype = torch.float32 if numpy.dtype(facet_dtype) == numpy.dtype(numpy.float32) else None
-            except TypeError:
-                facet_dtype = None
-        if facet_dtype != torch.float32:
-            raise ValueError("facet_dtype must be float32 or None")
-        return facet_dtype
-
     def _own_band(self):
         """the band this object's own K1 stores: the plan's (complex128, or no plan: the whole padded axis, plain band layout)"""
         planned = self._plan is not None and self.dtype == _torch().complex64
@@ -195,7 +176,7 @@ class SwiftlyForward(WavePrefetch):
             planned=self._plan is not None, real_facets=reals and core.supports_real_facets(),
             real_facets_rfft=reals and core.supports_real_facets_rfft(),
             rows_match_promoted=all(core._real_rows_match_promoted(n) for n in sizes),  # pylint: disable=protected-access
-            even=all(n % 2 == 0 and (off1 + core.yN_size // 2 - n // 2) % 2 == 0 for n, off1 in zip(sizes, off1s)),
+            even=all(loads_as_pairs(n, off1, core.yN_size) for n, off1 in zip(sizes, off1s)),
             # (device facets are read in place: two adjacent reals must be one aligned 8-byte load; uploads are contiguous)
             aligned=reals and all(t is None or t.device != core.device or (t.stride(0) % 2 == 0 and t.data_ptr() % 8 == 0)
                                   for t in ingest.tensors), settled=self._k1)

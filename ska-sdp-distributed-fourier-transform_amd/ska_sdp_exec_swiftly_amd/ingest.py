@@ -4,6 +4,7 @@ uploads host facets one ahead of the kernels that use them (SURVEY section 8f ro
 """
 import numpy
 
+from .facet_dtype import is_float32_facet
 from .tasks import _torch
 
 _MASK_CACHE = {}
@@ -79,16 +80,14 @@ class _FacetIngest:
         torch = _torch()
         if self._settled:
             raise RuntimeError("facets must be registered before settle()")
-        is_float32 = False
+        is_float32 = is_float32_facet(data)
         if isinstance(data, torch.Tensor):
             # (a float32 tensor K1 could not read in place -- not 2-D row-major -- is promoted at once, as it always was)
-            is_float32 = data.dtype == torch.float32 and data.dim() == 2 and data.stride(-1) == 1
             ten = data if is_float32 else self.core._as_device(data)[0]  # pylint: disable=protected-access
             self.host.append(None)
             self.tensors.append(ten)
         else:
             arr = numpy.asarray(data)
-            is_float32 = arr.dtype == numpy.float32
             if is_float32:
                 pass
             elif not numpy.iscomplexobj(arr):

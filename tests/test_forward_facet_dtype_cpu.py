@@ -7,7 +7,8 @@ import numpy
 import pytest
 import torch
 
-from ska_sdp_exec_swiftly_amd import SwiftlyBackward, SwiftlyForward
+from ska_sdp_exec_swiftly_amd import SwiftlyForward
+from ska_sdp_exec_swiftly_amd.facet_dtype import BACKWARD, FORWARD, parse_facet_dtype
 
 BAD = (torch.float64, torch.complex64, torch.complex128, torch.float16, "float64", "complex64", numpy.complex64, numpy.float64,
        "real", 32, object(), True)
@@ -22,12 +23,11 @@ def test_constructor_refuses_other_values_before_it_touches_anything(value):
 
 
 def test_accepted_values():
-    parse = SwiftlyForward._parse_facet_dtype  # pylint: disable=protected-access
-    assert parse(None) is None
+    assert parse_facet_dtype(None, FORWARD) is None and parse_facet_dtype(None, BACKWARD) is None
     for value in (torch.float32, "float32", numpy.float32, numpy.dtype("float32"), "f4"):
-        assert parse(value) is torch.float32, value
+        assert parse_facet_dtype(value, FORWARD) is torch.float32, value
         # ... and they are what the backward class reads as float32 too
-        assert SwiftlyBackward._parse_facet_dtype(value) is torch.float32  # pylint: disable=protected-access
+        assert parse_facet_dtype(value, BACKWARD) is torch.float32
     # an accepted value gets past the parsing: the constructor then fails on the missing configuration, not on the keyword
     with pytest.raises(AttributeError):
         SwiftlyForward(None, [], facet_dtype="float32")
