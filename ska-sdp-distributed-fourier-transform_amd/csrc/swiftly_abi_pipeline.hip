@@ -192,6 +192,7 @@ static int prepare_facet_columns_mixed(swiftly_hip_t* h, const void* in, int64_t
                 c.out_bs = out_facet_stride;
                 c.scale = (float)(1.0 / yN);
                 c.conj_ld = 0; c.conj_st = 1;
+                c.f64 = h->col_f64;  // (the sub-transforms only: the radix-Q pass is float32; as accumulate_facet_columns)
                 c.st_rowmap = rowmaps ? rowmaps + w * rowmap_stride : nullptr;
                 c.st_rowmap_bs = 0;
                 const int r2 = col_transform(h, logM, c, plain_colz(), m, nf, st, part.sub(lease.p), part.sub_bytes, Q, j, yN);

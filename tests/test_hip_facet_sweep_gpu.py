@@ -111,12 +111,13 @@ def vector_peak(got, want, axis):
     return float((err[ref > 0] / ref[ref > 0]).max())
 
 
-def _record(what, L, bits, value, bound, note=""):
-    print(f"FACETSWEEP {what:<26s} L={L:<3d} f{bits:<3d} {value:.3e} (bound {bound:.2e}) {note}")
+def _record(what, L, bits, value, bound, note="", label=None):
+    print(f"{label or f'FACETSWEEP {what:<26s} L={L:<3d}'} f{bits:<3d} {value:.3e} (bound {bound:.2e}) {note}")
 
 
-def check(what, L, bits, got, want, axis, f64=False, stages=None, note=""):
-    """all elements of ``got`` against ``want``; returns the relative RMSE"""
+def check(what, L, bits, got, want, axis, f64=False, stages=None, note="", label=None):
+    """all elements of ``got`` against ``want``; returns the relative RMSE.  ``label``: the head of the record line of
+    another sweep (tests/test_hip_mixed_sweep_gpu.py), whose ``L`` is the stage count of its bound"""
     assert got.shape == want.shape, (what, got.shape, want.shape)
     assert got.dtype == numpy.complex64, (what, got.dtype)
     assert numpy.isfinite(got).all(), what  # (``got`` may be a gathered, non-contiguous selection)
@@ -126,7 +127,7 @@ def check(what, L, bits, got, want, axis, f64=False, stages=None, note=""):
     else:
         bound = f32_bound(L if stages is None else stages)
     peak = vector_peak(got, want, axis)
-    _record(what, L, bits, err, bound, f"peak {peak:.2e} {note}")
+    _record(what, L, bits, err, bound, f"peak {peak:.2e} {note}", label)
     assert err < bound, (what, L, bits, note, err, bound)
     assert peak <= 2e-5, (what, L, bits, note, peak)
     return err
@@ -343,9 +344,10 @@ def test_prepare_facet_columns_workspace_of_one_facet(L):
 
 
 # ------------------------------------------------------------------------------------ (b) accumulate_facet_columns
-def facet_size(L, odd=False):
-    """a facet size near 0.69 yN (0.6875 yN: even, and a whole number of load segments of the long-row kernels)"""
-    yB = (11 << L) // 16
+def facet_size(L, odd=False, yN=None):
+    """a facet size near 0.69 yN (0.6875 yN: even, and a whole number of load segments of the long-row kernels);
+    ``yN`` = ``2^L`` unless given"""
+    yB = 11 * ((1 << L) if yN is None else yN) // 16
     return yB + 1 if odd else yB
 
 
@@ -358,15 +360,20 @@ def acc_problem(L, F=2, n_waves=2, seed=0):
 
     ``want[F, yB, columns]`` holds every touched band column (``cols``: their logical column numbers)."""
     key = (L, F, n_waves, seed)
-    if key in _ACC:
-        return _ACC[key]
+    if key not in _ACC:
+        _ACC[key] = acc_problem_at(params(L), facet_size(L, odd=(L == 9)), numpy.random.default_rng(3200 + 16 * L + seed),
+                                   L >= 10, F, n_waves)
+    return _ACC[key]
+
+
+def acc_problem_at(p, yB, rng, pruned_band, F=2, n_waves=2):
+    """:py:func:`acc_problem` for the parameter set ``p`` (N, xM, yN) and facet size ``yB`` (not cached); ``pruned_band``:
+    the smallest band that holds the windows, else the whole axis"""
     from ska_sdp_exec_swiftly_amd.core_hip import band_range
 
-    core, ref = cores(params(L))
+    core, ref = cores(p)
     N, yN, m = core.N, core.yN_size, core.xM_yN_size
     fstep, sstep = core.facet_off_step, core.subgrid_off_step
-    yB = facet_size(L, odd=(L == 9))
-    rng = numpy.random.default_rng(3200 + 16 * L + seed)
     facet_off0s = [5 * fstep, -24 * fstep] if F == 2 else [((7 * f) % 61 - 30) * fstep for f in range(F)]
     assert len(set(facet_off0s)) == F
     masks = (rng.random((F, yB)) > 0.1).astype(numpy.float32)
@@ -374,7 +381,7 @@ def acc_problem(L, F=2, n_waves=2, seed=0):
     s1 = [yN // 8, yN // 8 + m - m // 4][:n_waves]
     s0 = [[-m, -(m // 4), m // 2], [m // 8, m // 8 + m // 2]][:n_waves]
     waves = [(a * sstep, [b * sstep for b in bs]) for a, bs in zip(s1, s0)]
-    band = band_range(N, yN, m, [w[0] for w in waves] + [(s1[-1] + m + m // 2) * sstep]) if L >= 10 else (0, yN)
+    band = band_range(N, yN, m, [w[0] for w in waves] + [(s1[-1] + m + m // 2) * sstep]) if pruned_band else (0, yN)
     cols = sorted({int(c) for a in s1 for c in (yN // 2 - m // 2 + numpy.arange(m) + a) % yN})
     pos = numpy.full(yN, -1)
     pos[cols] = numpy.arange(len(cols))
@@ -391,10 +398,8 @@ def acc_problem(L, F=2, n_waves=2, seed=0):
                 acc = ref.add_to_facet(pw[f, b].astype(complex), o0, axis=0, out=acc)
             fin = ref.finish_facet(acc, facet_off0s[f], yB, axis=0) * masks[f][:, None]
             want[f][:, pos[big]] += fin[:, (i + a) % m]
-    prob = dict(yB=yB, facet_off0s=facet_off0s, masks=masks, waves=waves, band=band, cols=numpy.array(cols), want=want,
+    return dict(yB=yB, facet_off0s=facet_off0s, masks=masks, waves=waves, band=band, cols=numpy.array(cols), want=want,
                 parts=parts)
-    _ACC[key] = prob
-    return prob
 
 
 def acc_run(L, bits, prob, workspace_facets=None):
@@ -403,24 +408,52 @@ def acc_run(L, bits, prob, workspace_facets=None):
     import torch
 
     core, _ = cores(params(L))
+    F = len(prob["facet_off0s"])
+    work = torch.empty((F if workspace_facets is None else workspace_facets, core.yN_size, core.xM_yN_size),
+                       dtype=torch.complex64, device="cuda")
+    got = acc_run_at(params(L), bits, prob, work)
+    return check("accumulate_facet_columns", L, bits, got, prob["want"], 1, acc_has_f64(L), note=f"F {F}")
+
+
+def acc_run_at(p, bits, prob, workspace, two_chunks=False):
+    """:py:func:`acc_run` for the parameter set ``p`` up to the comparison of the touched columns: returns them,
+    ``got[F, yB, columns]``.  ``workspace``: a device tensor, or None (the library allocates its own).  ``two_chunks``: the
+    last subgrid of every wave in a source chunk of its own that lies BELOW the first chunk in memory (offsets are
+    relative to the lowest address), both chunks inside one allocation, the row table naming both."""
+    import torch
+
+    core, _ = cores(p)
     yN, m = core.yN_size, core.xM_yN_size
     yB, band, cols = prob["yB"], prob["band"], prob["cols"]
     F = len(prob["facet_off0s"])
     start, length = band
     bands = torch.full((F, yB, length), float("nan"), dtype=torch.complex64, device="cuda")  # uninitialised on purpose
     touched = torch.zeros((length,), dtype=torch.uint8, device="cuda")
-    work = torch.empty((F if workspace_facets is None else workspace_facets, yN, m), dtype=torch.complex64, device="cuda")
     mask_t = torch.from_numpy(prob["masks"]).cuda()
     two_sources = False
     with precision(core, bits):
         for (off1, off0s), pw in zip(prob["waves"], prob["parts"]):
-            pt = torch.from_numpy(pw).cuda()
-            groups = core.column_row_sources(off0s)
+            S = len(off0s)
+            if two_chunks:
+                pt = torch.empty((F * S * m * m + 64,), dtype=torch.complex64, device="cuda")
+                low = pt[: F * m * m].view(F, 1, m, m)
+                high = pt[F * m * m + 64:].view(F, S - 1, m, m)
+                high.copy_(torch.from_numpy(pw[:, : S - 1]).cuda())
+                low.copy_(torch.from_numpy(pw[:, S - 1:]).cuda())
+                assert high.data_ptr() > low.data_ptr()
+                offs, fstr = [F * m * m + 64, 0], [(S - 1) * m * m, m * m]
+                locs = [(0, b) for b in range(S - 1)] + [(1, 0)]
+            else:
+                pt = torch.from_numpy(pw).cuda()
+                offs, fstr, locs = [0], [pt.stride(0)], None
+            groups = core.column_row_sources(off0s, locs)
             assert len(groups) == 1 or yN < 4 * m  # (short rings: three windows overlap in some rows, two tables)
             for _, table in groups:
                 two_sources |= bool((table[1] >= 0).any())
-                core.accumulate_facet_columns(pt, m, [0], [pt.stride(0)], table, prob["facet_off0s"], yB, mask_t, off1, bands,
-                                              band, workspace=work, touched=touched)
+                if two_chunks:
+                    assert sorted(set((table[table >= 0] >> 20).cpu().tolist())) == [0, 1]
+                core.accumulate_facet_columns(pt, m, offs, fstr, table, prob["facet_off0s"], yB, mask_t, off1, bands,
+                                              band, workspace=workspace, touched=touched)
         core.band_zero_untouched(bands, touched)
     assert two_sources
     tch = touched.cpu().numpy()
@@ -429,8 +462,7 @@ def acc_run(L, bits, prob, workspace_facets=None):
     if m < yN:  # (m = yN at L = 6, 7: every column is in every window)
         assert (tch == 0).any()
     assert not bool((bands[:, :, torch.from_numpy(tch == 0).cuda()] != 0).any()), "an untouched band column is not zero"
-    got = bands[:, :, torch.from_numpy(d).cuda()].cpu().numpy()
-    return check("accumulate_facet_columns", L, bits, got, prob["want"], 1, acc_has_f64(L), note=f"F {F}")
+    return bands[:, :, torch.from_numpy(d).cuda()].cpu().numpy()
 
 
 @pytest.mark.parametrize("L", LENGTHS)
@@ -470,7 +502,7 @@ def data_segments(yN, size, off, seglen):
     return sum(valid)
 
 
-def k1_run(core, ref, L, x, xt, off, band, fold, rows_of=None, note=""):
+def k1_run(core, ref, L, x, xt, off, band, fold, rows_of=None, note="", label=None):
     import torch
 
     yN = core.yN_size
@@ -491,7 +523,7 @@ def k1_run(core, ref, L, x, xt, off, band, fold, rows_of=None, note=""):
         pc = band_cols(yN, band)
         keep = pc >= 0
         got, want = got[:, pc[keep]], want[:, keep]
-    return check("prepare_facet_band", L, 32, got, want, 1, note=note)
+    return check("prepare_facet_band", L, 32, got, want, 1, note=note, label=label)
 
 
 @pytest.mark.parametrize("L", K1_LENGTHS)

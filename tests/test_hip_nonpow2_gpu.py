@@ -16,6 +16,9 @@ pytestmark = pytest.mark.gpu
 # catalogue entries (ska_sdp_exec_swiftly_amd.swift_configs): all of yN, xM, m non-power-of-two / only yN
 CFG_ALL = dict(W=10.875, N=1792, yB_size=608, yN_size=896, xA_size=392, xM_size=448)     # "1792[1]-n896-448": m = 224
 CFG_YN = dict(W=11.0, N=1536, yB_size=528, yN_size=768, xA_size=448, xM_size=512)        # "1536[1]-n768-512": m = 256
+# all three lengths Q = 5 (640, 320, 160) / Q = 3 (768, 384, 192): the xM = 320 / 384 and m = 160 / 192 of twelve entries
+CFG_Q5 = dict(W=11.125, N=1280, yB_size=448, yN_size=640, xA_size=280, xM_size=320)      # "1280[1]-n640-320": m = 160
+CFG_Q3 = dict(W=10.75, N=1536, yB_size=512, yN_size=768, xA_size=345, xM_size=384)       # "1536[1]-n768-384": m = 192
 
 
 def relrms(a, b):
@@ -29,7 +32,7 @@ def cores(p):
             orc.OracleCore(p["W"], p["N"], p["xM_size"], p["yN_size"]))
 
 
-@pytest.mark.parametrize("p", [CFG_ALL, CFG_YN])
+@pytest.mark.parametrize("p", [CFG_ALL, CFG_YN, CFG_Q5, CFG_Q3])
 @pytest.mark.parametrize("dtype", [numpy.complex128, numpy.complex64])
 @pytest.mark.parametrize("path", ["mixed", "bluestein"])
 def test_primitives_nonpow2(p, dtype, path, monkeypatch):
