@@ -1,7 +1,9 @@
 """
 ``SwiftlyBackward``: the subgrid -> facet direction of the streaming API (reference src/ska_sdp_exec_swiftly/api.py:327-463,
 task bodies api_helper.py:115-197) on one MI355X, with the reference's schedule (``wave_axis=0``) and the band schedule
-(``wave_axis=1``).
+(``wave_axis=1``).  The class is the front -- keywords, schedule and dtype rules, staging of partial
+waves, ``finish()`` -- of three roles: ``splitter.SubgridSplitter`` (a wave's contributions to every facet) and the facet
+owner's accumulators of either schedule, ``ColumnAccumulators`` and ``BandAccumulators``.
 """
 import logging
 
@@ -11,9 +13,190 @@ from . import _lib, facet_dtype as fdt
 from .b8_form import B8Facts, choose_b8
 from .core_hip import band_range
 from .ingest import _mask_table
+from .splitter import SubgridSplitter
 from .tasks import DeviceTask, LRUCache, TaskQueue, _torch, _unwrap
 
 log = logging.getLogger("fourier-logger")
+
+
+class ColumnAccumulators:
+    """The reference's schedule (``wave_axis=0``) for the facets ``facet_configs``: partial sums ``NAF_MNAF [F, m, yN]`` per
+    subgrid ``off0`` column in an LRU of ``lru_backward`` columns (reference api.py:402-438), evicted columns folded into the
+    facet accumulators ``MNAF_BMNAFs_persist [yN, yB]``, strided-axis transform at the end."""
+
+    def __init__(self, core, facet_configs, lru_backward=1):
+        self.core, self.facet_configs = core, facet_configs
+        self.lru = LRUCache(lru_backward)
+        self.MNAF_BMNAFs_persist = [None for _ in facet_configs]
+
+    def accumulate_wave(self, sgs, parts):
+        """:py:meth:`accumulate` of the one chunk ``parts[F, S, m, m]`` of subgrids ``sgs`` that share ``off0``"""
+        off0 = sgs[0].off0
+        if any(int(sg.off0) != int(off0) for sg in sgs):
+            raise ValueError(f"reference schedule (wave_axis=0): all subgrids of a wave must share off0={off0}")
+        return self.accumulate(off0, [(sgs, parts)])
+
+    def accumulate(self, off0, chunks):
+        """``accumulate_column`` (reference api_helper.py:142-152): add ``chunks = [(subgrid configs, parts[F, S_c, m, m]),
+        ...]`` into the partial sums of column ``off0``; the column this evicts goes to the facet accumulators"""
+        core = self.core
+        m, yN = core.xM_yN_size, core.yN_size
+        F = len(self.facet_configs)
+        col = self.lru.get(off0)
+        for sgs, parts in chunks:
+            if col is None:
+                col = _torch().zeros((F, m, yN), dtype=parts.dtype, device=core.device)
+            # one launch per subgrid (batched over facets): launches are ordered on the stream, so subgrids whose
+            # windows overlap never update the same element concurrently
+            for b, sg in enumerate(sgs):
+                core.launch("add_to_facet", parts[:, b], m, m, 1, col, yN, 1, sg.off1,
+                            nbatch=F, in_bs=parts.stride(0), out_bs=m * yN)
+        if col is None:
+            return None
+        old_off0, old_col = self.lru.set(off0, col)
+        if old_off0 is not None and old_col is not None:
+            self.update_MNAF_BMNAFs(old_off0, old_col)
+        return col
+
+    def update_MNAF_BMNAFs(self, off0, NAF_MNAFs):
+        """accumulate_facet for every facet (reference api.py:440-463,
+        api_helper.py:155-179): finish axis 1 (+mask1), add along axis 0."""
+        torch = _torch()
+        core = self.core
+        yN = core.yN_size
+        dev, dt = core.device, NAF_MNAFs.dtype
+        for j, cfg in enumerate(self.facet_configs):
+            yB = cfg.size
+            t = core.finish_facet(NAF_MNAFs[j], cfg.off1, yB, axis=1, mask=cfg.mask1)
+            if self.MNAF_BMNAFs_persist[j] is None:
+                self.MNAF_BMNAFs_persist[j] = torch.zeros((yN, yB), dtype=dt, device=dev)
+            core.launch("add_to_facet", t, yB, 1, yB, self.MNAF_BMNAFs_persist[j], 1, yB, off0)
+        return self.MNAF_BMNAFs_persist
+
+    def finish(self, empty_dtype, handed_out):
+        """flush the column cache and finish every facet along axis 0 (reference api_helper.py:182-197): ``handed_out(facet)``
+        per facet as it is finished, zeros of ``empty_dtype`` for a facet without contributions"""
+        core = self.core
+        for old_off0, old_col in self.lru.pop_all():
+            self.update_MNAF_BMNAFs(old_off0, old_col)
+        out = []
+        for cfg, acc in zip(self.facet_configs, self.MNAF_BMNAFs_persist):
+            if acc is None:
+                out.append(_torch().zeros((cfg.size, cfg.size), dtype=empty_dtype, device=core.device))
+            else:
+                out.append(handed_out(core.finish_facet(acc, cfg.off0, cfg.size, axis=0, mask=cfg.mask0)))
+        return out
+
+
+class BandAccumulators:
+    """The band schedule (``wave_axis=1``) for the facets ``facet_configs``: accumulators
+    ``bands [F, yB, band length]`` over the columns ``band`` that the waves of ``plan`` touch (no plan: the whole padded axis),
+    first-write flags ``touched`` per column, the facet mask table and the scratch of ``accumulate_facet_columns`` -- all
+    created by the first wave.  ``fixed_dtype``: the dtype a ``SwiftlyBackward`` was constructed with (the explicit gate)."""
+
+    def __init__(self, core, facet_configs, plan=None, fixed_dtype=None):
+        self.core, self.facet_configs, self._plan, self._fixed_dtype = core, facet_configs, plan, fixed_dtype
+        self.band = self.bands = self.touched = self.masks0 = self.work = None
+        self._planned = {sg.off1 for sg in plan} if plan else None
+        self._facet_off0s = [cfg.off0 for cfg in facet_configs]
+
+    def _create(self, dtype):
+        torch = _torch()
+        core = self.core
+        if self._fixed_dtype is not None:
+            # explicit dtype: complex128 runs through the explicit gate (complex64: the same answer as without)
+            if dtype != self._fixed_dtype:
+                raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={self._fixed_dtype}) got {dtype} contributions")
+            if not core.supports_backward_band(dtype, explicit=True):
+                raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={dtype}): {_lib.last_error()}")
+        elif dtype != torch.complex64 or not core.supports_backward_band(dtype):
+            raise ValueError("SwiftlyBackward(wave_axis=1) needs complex64 data and power-of-two yN_size / xM_yN_size")
+        sizes = {cfg.size for cfg in self.facet_configs}
+        if len(sizes) != 1:
+            raise ValueError("SwiftlyBackward(wave_axis=1) needs facets of one size")
+        yB = sizes.pop()
+        # (the backward accumulators are plain-order bands for every yN: band_range, not the forward layout rule)
+        self.band = (
+            band_range(core.N, core.yN_size, core.xM_yN_size, [sg.off1 for sg in self._plan])
+            if self._plan else (0, core.yN_size)
+        )
+        F = len(self.facet_configs)
+        # uninitialised: first-write flags per band column replace the zero fill
+        self.bands = torch.empty((F, yB, self.band[1]), dtype=dtype, device=core.device)
+        self.touched = torch.zeros((self.band[1],), dtype=torch.uint8, device=core.device)
+        self.masks0 = _mask_table(core, self.facet_configs, "mask0", yB, dtype)
+        # four-step scratch of accumulate_facet_columns (+ the radix-Q pass's output when yN = Q * 2^k)
+        esz = 16 if dtype == torch.complex128 else 8
+        self.work = torch.empty((core._k2_scratch_bytes(F, element_size=esz) // esz,), dtype=dtype, device=core.device)
+
+    def accumulate(self, off1, chunks, first=None):
+        """accumulate_column + accumulate_facet (reference api_helper.py:142-179) with the axes swapped, for the
+        contributions ``chunks = [(subgrid configs, parts[F, S_c, m, m]), ...]`` of subgrids sharing ``off1``.
+        ``first(dtype)``: called with the contributions' dtype once the wave has passed its key check, before anything is
+        created (the owner's first-data rules)."""
+        core = self.core
+        m = core.xM_yN_size
+        chunks = [(sgs, parts) for sgs, parts in chunks if len(sgs)]
+        if not chunks:
+            return None
+        for sgs, _parts in chunks:
+            # (r4 advice) the band schedule folds a wave under ONE off1: a caller that follows the reference's per-off0
+            # flow (accumulate_column, api_helper.py:142-152) on an object whose schedule resolved to wave_axis=1 must
+            # hear about it instead of getting every subgrid placed at the first one's off1
+            bad = [sg for sg in sgs if int(sg.off1) != int(off1)]
+            if bad:
+                raise ValueError(
+                    f"band schedule (wave_axis=1): all subgrids of a wave must share off1={off1}, got off1={bad[0].off1}; "
+                    "group the subgrids by off1, or construct SwiftlyBackward(wave_axis=0) for the reference's per-off0 flow"
+                )
+        if first is not None:
+            first(chunks[0][1].dtype)
+        if self.bands is None:
+            self._create(chunks[0][1].dtype)
+        bands = self.bands
+        for _sgs, parts in chunks:
+            # on EVERY call, not only the one that creates the accumulators: the native side reads `parts` with the
+            # accumulators' element size
+            if parts.dtype != bands.dtype:
+                raise ValueError(f"band accumulators are {bands.dtype}, got {parts.dtype} contributions")
+        if self._planned is not None and off1 not in self._planned:
+            raise ValueError(f"subgrid off1={off1} is not in the subgrid_configs this SwiftlyBackward was planned for")
+        F = len(self.facet_configs)
+        dt0 = chunks[0][1].dtype
+        fstr, off0s, locs = [], [], []
+        fixed = []
+        for c, (sgs, parts) in enumerate(chunks):
+            if parts.shape[0] != F or parts.dtype != dt0:
+                raise ValueError("contribution chunk does not match the facet list / dtype")
+            if parts.stride(3) != 1 or parts.stride(2) != m or (parts.shape[1] > 1 and parts.stride(1) != m * m):
+                parts = parts.contiguous()
+            fixed.append(parts)  # keeps a contiguous copy alive until the launch is queued
+            fstr.append(parts.stride(0) if F > 1 else 0)
+            for b, sg in enumerate(sgs):
+                off0s.append(sg.off0)
+                locs.append((c, b))
+        # chunk offsets are relative to the LOWEST chunk address: the gather-sum kernel reads a negative 64-bit offset
+        # as "no source row", so a chunk allocated below the base (a contiguous copy, a separately allocated chunk
+        # handed to accumulate_chunks) would otherwise be dropped silently
+        base = min(fixed, key=lambda t: t.data_ptr())
+        offs = [(t.data_ptr() - base.data_ptr()) // base.element_size() for t in fixed]
+        if len(chunks) > core.GS_MAX_CHUNKS:
+            raise ValueError(f"at most {core.GS_MAX_CHUNKS} contribution chunks per wave")
+        for _members, table in core.column_row_sources(off0s, locs):
+            core.accumulate_facet_columns(base, m, offs, fstr, table, self._facet_off0s, bands.shape[1], self.masks0,
+                                          off1, bands, self.band, workspace=self.work, touched=self.touched)
+        return bands
+
+    def hand_out(self):
+        """the accumulators ``[F, yB, band length]`` with the columns no wave touched zero-filled, ready for the
+        contiguous-axis finish; ``None`` when no wave arrived"""
+        if self.bands is not None:
+            self.core.band_zero_untouched(self.bands, self.touched)
+        return self.bands
+
+    def release(self):
+        """drop the accumulators and the scratch (the finished facets replace them)"""
+        self.bands = self.work = None
 
 
 class SwiftlyBackward:
@@ -69,22 +252,14 @@ class SwiftlyBackward:
             raise ValueError("wave_axis must be 0 or 1")
         self._plan = list(subgrid_configs) if subgrid_configs is not None else None
         self._plan_counts = None
-        self._wsbuf = {}
-        self._ring = 0
-        self._band = None
-        self._bands = None
-        self._work = None
         self.config = swiftly_config
         self.core = swiftly_config.core
         self.facets_config_list = facets_config_list
         self.queue_size = queue_size
         self.task_queue = TaskQueue(queue_size)
         self._client = client
-        self.lru = LRUCache(lru_backward)
-        self.MNAF_BMNAFs_persist = [None for _ in facets_config_list]
+        self.lru = LRUCache(lru_backward)  # the staged partial waves of the band schedule (wave_axis=0: unused, see columns.lru)
         self.dtype = None
-        self._off0s = sorted({cfg.off0 for cfg in facets_config_list})
-        self._off0_of = [self._off0s.index(cfg.off0) for cfg in facets_config_list]
         self._fixed_dtype = None
         if dtype is not None:
             torch = _torch()
@@ -99,6 +274,27 @@ class SwiftlyBackward:
             if self.wave_axis == 1 and not self._auto_axis and not self.core.supports_backward_band(dtype, explicit=True):
                 raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={dtype}): {_lib.last_error()}")
             self._check_facet_dtype(dtype)
+        # the three roles: the subgrid holder's half, and the facet owner's half in either schedule
+        self.splitter = SubgridSplitter(self.core, facets_config_list)  # (the dtype goes with each call)
+        self.columns = ColumnAccumulators(self.core, facets_config_list, lru_backward)
+        self.bands = BandAccumulators(self.core, facets_config_list, self._plan, self._fixed_dtype)
+
+    def __getattr__(self, name):
+        """the band state (``_band``, ``_bands``, ``_work``, ``_masks0``) and the splitter's workspaces (``_wsbuf``) read under
+        the names they had on this class"""
+        role = {"_band": "bands", "_bands": "bands", "_work": "bands", "_masks0": "bands", "_wsbuf": "splitter"}.get(name)
+        if role not in self.__dict__:
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}'")
+        return getattr(self.__dict__[role], name if role == "splitter" else name[1:])
+
+    @property
+    def MNAF_BMNAFs_persist(self):
+        """the reference schedule's facet accumulators (reference api.py:341)"""
+        return self.columns.MNAF_BMNAFs_persist
+
+    def update_MNAF_BMNAFs(self, off0, NAF_MNAFs):
+        """:py:meth:`ColumnAccumulators.update_MNAF_BMNAFs` (reference api.py:440-463)"""
+        return self.columns.update_MNAF_BMNAFs(off0, NAF_MNAFs)
 
     def _check_facet_dtype(self, data_dtype):
         """``facet_dtype`` has the precision of the data (called wherever the data's dtype becomes known)"""
@@ -250,23 +446,17 @@ class SwiftlyBackward:
         old_key, old = self.lru.set(key, staged)
         if old_key is not None and old is not None:
             self._flush_staged(old)
-        return self._bands
+        return self.bands.bands
 
     def _flush_staged(self, staged):
         n = len(staged["cfgs"])
         return self._add_wave(staged["cfgs"], [staged["buf"][k] for k in range(n)])
 
-    def _ws(self, name, shape, dtype):
-        """Grow-only persistent workspace (per-wave allocations of changing size are kept away from the caching
-        allocator: its misses are synchronous hipMallocs)."""
-        torch = _torch()
-        n = 1
-        for d in shape:
-            n *= int(d)
-        buf = self._wsbuf.get(name)
-        if buf is None or buf.numel() < n or buf.dtype != dtype:
-            buf = self._wsbuf[name] = torch.empty((n,), dtype=dtype, device=self.core.device)
-        return buf[:n].view(*shape)
+    def _first_dtype(self, dtype):
+        """the first data shows the dtype, where none was fixed: ``facet_dtype`` has its precision"""
+        if self.dtype is None:
+            self.dtype = dtype
+            self._check_facet_dtype(dtype)
 
     def wave_contributions(self, sgs, subgrids):
         """``prepare_and_split_subgrid`` (reference api_helper.py:115-139) for a
@@ -276,69 +466,11 @@ class SwiftlyBackward:
         workspaces of this object: it stays valid until the second-next call."""
         if self._auto_axis and len(subgrids):
             self._resolve_axis(_unwrap(subgrids[0]))
-        torch = _torch()
-        core = self.core
-        m, xM = core.xM_yN_size, core.xM_size
-        F, S, D = len(self.facets_config_list), len(sgs), len(self._off0s)
-        xA = sgs[0].size
-        subs = []
-        for data in subgrids:
-            ten, _ = core._as_device(data)  # pylint: disable=protected-access
-            if self.dtype is None:
-                self.dtype = ten.dtype
-                self._check_facet_dtype(ten.dtype)
-            elif ten.dtype != self.dtype:
-                if self.wave_axis == 1 and self._fixed_dtype is not None:  # no silent conversion on the explicit band schedule
-                    raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={self.dtype}) got {ten.dtype} data")
-                ten = ten.to(self.dtype)
-            if tuple(ten.shape) != (xA, xA):
-                raise ValueError(f"subgrid has shape {tuple(ten.shape)}, expected {(xA, xA)}")
-            subs.append(ten)
-        dev, dt = core.device, self.dtype
-        # complex128 takes the split kernel only on the explicitly requested band schedule: every path that existed before
-        # keeps its launch sequence (and its rounding)
-        explicit128 = self.wave_axis == 1 and self._fixed_dtype is not None and dt == torch.complex128
-        if core.supports_fused_subgrid(dt, n_facets=F) or (explicit128 and core.supports_split_prepare(dt, n_facets=F)):
-            # prepare_subgrid along axis 0 on the xA columns, then ONE kernel per padded row for the contiguous-axis
-            # half (prepare axis 1 + extract axis 1 for every facet, on chip) and one column pass for the rest
-            step = xA * xA * subs[0].element_size()
-            base = subs[0].untyped_storage().data_ptr()
-            if all(
-                t.is_contiguous() and t.data_ptr() == subs[0].data_ptr() + i * step
-                and t.untyped_storage().data_ptr() == base  # views of ONE allocation, not neighbours by chance
-                for i, t in enumerate(subs)
-            ):
-                # the subgrids already sit back to back (slices of one wave tensor, e.g. what get_wave returned)
-                sub = torch.as_strided(subs[0], (S, xA, xA), (xA * xA, xA, 1))
-            else:
-                sub = self._ws("stack", (S, xA, xA), dt)
-                torch.stack(subs, out=sub)
-            work = self._ws("work", (2 * S * xM * xA,), dt)
-            self._ring ^= 1
-            parts = self._ws(f"parts{self._ring}", (F, S, m, m), dt)
-            return core.wave_split_subgrids(sub, [sg.off0 for sg in sgs], [sg.off1 for sg in sgs],
-                                            [c.off0 for c in self.facets_config_list],
-                                            [c.off1 for c in self.facets_config_list], work, parts)
-        sub = subs[0].unsqueeze(0) if S == 1 else torch.stack(subs)
-        sub = sub.contiguous()
-        # prepare_subgrid (core.py:328-368): axis 1 on the xA rows, then axis 0 on all xM columns
-        tmp = torch.empty((S, xA, xM), dtype=dt, device=dev)
-        core.launch("prepare_subgrid", sub, xA, xA, 1, tmp, xM, 1, 0, size=xA,
-                    nbatch=S, in_bs=xA * xA, out_bs=xA * xM, offs=[sg.off1 for sg in sgs])
-        prepared = torch.empty((S, xM, xM), dtype=dt, device=dev)
-        core.launch("prepare_subgrid", tmp, xM, 1, xM, prepared, 1, xM, 0, size=xA,
-                    nbatch=S, in_bs=xA * xM, out_bs=xM * xM, offs=[sg.off0 for sg in sgs])
-        # extract_from_subgrid along axis 0 once per distinct facet off0 (api_helper.py:125-131) ...
-        e0 = torch.empty((D, S, m, xM), dtype=dt, device=dev)
-        for d, off0_f in enumerate(self._off0s):
-            core.launch("extract_from_subgrid", prepared, xM, 1, xM, e0[d], 1, xM, off0_f,
-                        nbatch=S, in_bs=xM * xM, out_bs=m * xM)
-        # ... and along axis 1 per facet (api_helper.py:133-138)
-        parts = torch.empty((F, S, m, m), dtype=dt, device=dev)
-        for j, cfg in enumerate(self.facets_config_list):
-            core.launch("extract_from_subgrid", e0[self._off0_of[j]], m, xM, 1, parts[j], m, 1, cfg.off1,
-                        nbatch=S, in_bs=m * xM, out_bs=m * m)
-        return parts
+        if self.dtype is None and len(subgrids):
+            first, _ = self.core._as_device(subgrids[0])  # pylint: disable=protected-access
+            self._first_dtype(first.dtype)
+            subgrids = [first, *subgrids[1:]]  # (uploaded once)
+        return self.splitter.contributions(sgs, subgrids, self.wave_axis == 1 and self._fixed_dtype is not None, self.dtype)
 
     def accumulate_wave(self, sgs, parts):
         """``accumulate_column`` (reference api_helper.py:142-152) for a wave:
@@ -349,27 +481,9 @@ class SwiftlyBackward:
         ``wave_axis=None`` the schedule is fixed by the first data this object sees (:py:meth:`_resolve_axis`); a wave
         whose subgrids do not share the key of the resolved schedule raises ``ValueError``."""
         self._resolve_axis(parts)
-        torch = _torch()
-        core = self.core
-        m, yN = core.xM_yN_size, core.yN_size
-        F = len(self.facets_config_list)
         if self.wave_axis == 1:
-            return self._accumulate_band(sgs[0].off1, [(sgs, parts)])
-        off0 = sgs[0].off0
-        if any(int(sg.off0) != int(off0) for sg in sgs):
-            raise ValueError(f"reference schedule (wave_axis=0): all subgrids of a wave must share off0={off0}")
-        col = self.lru.get(off0)
-        if col is None:
-            col = torch.zeros((F, m, yN), dtype=parts.dtype, device=core.device)
-        # one launch per subgrid (batched over facets): launches are ordered on the stream, so subgrids whose
-        # windows overlap never update the same element concurrently
-        for b, sg in enumerate(sgs):
-            core.launch("add_to_facet", parts[:, b], m, m, 1, col, yN, 1, sg.off1,
-                        nbatch=F, in_bs=parts.stride(0), out_bs=m * yN)
-        old_off0, old_col = self.lru.set(off0, col)
-        if old_off0 is not None and old_col is not None:
-            self.update_MNAF_BMNAFs(old_off0, old_col)
-        return col
+            return self.bands.accumulate(sgs[0].off1, [(sgs, parts)], self._first_dtype)
+        return self.columns.accumulate_wave(sgs, parts)
 
     def accumulate_chunks(self, off0, chunks):
         """:py:meth:`accumulate_wave` for contributions that arrive in several pieces (one per source rank of
@@ -377,28 +491,11 @@ class SwiftlyBackward:
         the wave KEY: the subgrids' ``off0`` with ``wave_axis=0``, their ``off1`` with ``wave_axis=1`` (checked)."""
         if self._auto_axis and len(chunks):
             self._resolve_axis(chunks[0][1])
-        torch = _torch()
-        core = self.core
-        m, yN = core.xM_yN_size, core.yN_size
-        F = len(self.facets_config_list)
         if self.wave_axis == 1:  # ``off0`` is the wave key: the subgrids' off1
-            return self._accumulate_band(off0, chunks)
-        col = self.lru.get(off0)
-        for sgs, parts in chunks:
-            if self.dtype is None:
-                self.dtype = parts.dtype
-                self._check_facet_dtype(parts.dtype)
-            if col is None:
-                col = torch.zeros((F, m, yN), dtype=parts.dtype, device=core.device)
-            for b, sg in enumerate(sgs):
-                core.launch("add_to_facet", parts[:, b], m, m, 1, col, yN, 1, sg.off1,
-                            nbatch=F, in_bs=parts.stride(0), out_bs=m * yN)
-        if col is None:
-            return None
-        old_off0, old_col = self.lru.set(off0, col)
-        if old_off0 is not None and old_col is not None:
-            self.update_MNAF_BMNAFs(old_off0, old_col)
-        return col
+            return self.bands.accumulate(off0, chunks, self._first_dtype)
+        if len(chunks):
+            self._first_dtype(chunks[0][1].dtype)
+        return self.columns.accumulate(off0, chunks)
 
     def _add_wave(self, sgs, subgrids):
         parts = self.wave_contributions(sgs, subgrids)
@@ -406,152 +503,35 @@ class SwiftlyBackward:
         self.task_queue.process([col])
         return col
 
-    # ---- wave_axis = 1: band accumulators
-    def _band_state(self, dtype):
-        """Band, accumulators ``[F, yB, band length]`` (zeros) and the facet mask table, created at first use."""
-        torch = _torch()
-        core = self.core
-        if self._bands is None:
-            if self._fixed_dtype is not None:
-                # explicit dtype: complex128 runs through the explicit gate (complex64: the same answer as without)
-                if dtype != self._fixed_dtype:
-                    raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={self._fixed_dtype}) got {dtype} contributions")
-                if not core.supports_backward_band(dtype, explicit=True):
-                    raise ValueError(f"SwiftlyBackward(wave_axis=1, dtype={dtype}): {_lib.last_error()}")
-            elif dtype != torch.complex64 or not core.supports_backward_band(dtype):
-                raise ValueError("SwiftlyBackward(wave_axis=1) needs complex64 data and power-of-two yN_size / xM_yN_size")
-            sizes = {cfg.size for cfg in self.facets_config_list}
-            if len(sizes) != 1:
-                raise ValueError("SwiftlyBackward(wave_axis=1) needs facets of one size")
-            yB = sizes.pop()
-            # (the backward accumulators are plain-order bands for every yN: band_range, not the forward layout rule)
-            self._band = (
-                band_range(core.N, core.yN_size, core.xM_yN_size, [sg.off1 for sg in self._plan])
-                if self._plan else (0, core.yN_size)
-            )
-            self._planned = {sg.off1 for sg in self._plan} if self._plan else None
-            F = len(self.facets_config_list)
-            # uninitialised: first-write flags per band column replace the zero fill
-            self._bands = torch.empty((F, yB, self._band[1]), dtype=dtype, device=core.device)
-            self._touched = torch.zeros((self._band[1],), dtype=torch.uint8, device=core.device)
-            self._masks0 = _mask_table(core, self.facets_config_list, "mask0", yB, dtype)
-            self._facet_off0s = [cfg.off0 for cfg in self.facets_config_list]
-            # four-step scratch of accumulate_facet_columns (+ the radix-Q pass's output when yN = Q * 2^k)
-            esz = 16 if dtype == torch.complex128 else 8
-            self._work = torch.empty((core._k2_scratch_bytes(F, element_size=esz) // esz,), dtype=dtype, device=core.device)
-        return self._bands
-
-    def _accumulate_band(self, off1, chunks):
-        """accumulate_column + accumulate_facet (reference api_helper.py:142-179) with the axes swapped, for the
-        contributions ``chunks = [(subgrid configs, parts[F, S_c, m, m]), ...]`` of subgrids sharing ``off1``."""
-        core = self.core
-        m = core.xM_yN_size
-        chunks = [(sgs, parts) for sgs, parts in chunks if len(sgs)]
-        if not chunks:
-            return None
-        for sgs, _parts in chunks:
-            # (r4 advice) the band schedule folds a wave under ONE off1: a caller that follows the reference's per-off0
-            # flow (accumulate_column, api_helper.py:142-152) on an object whose schedule resolved to wave_axis=1 must
-            # hear about it instead of getting every subgrid placed at the first one's off1
-            bad = [sg for sg in sgs if int(sg.off1) != int(off1)]
-            if bad:
-                raise ValueError(
-                    f"band schedule (wave_axis=1): all subgrids of a wave must share off1={off1}, got off1={bad[0].off1}; "
-                    "group the subgrids by off1, or construct SwiftlyBackward(wave_axis=0) for the reference's per-off0 flow"
-                )
-        if self.dtype is None:
-            self.dtype = chunks[0][1].dtype
-            self._check_facet_dtype(self.dtype)
-        bands = self._band_state(chunks[0][1].dtype)
-        for _sgs, parts in chunks:
-            # on EVERY call, not only the one that creates the accumulators: the native side reads `parts` with the
-            # accumulators' element size
-            if parts.dtype != bands.dtype:
-                raise ValueError(f"band accumulators are {bands.dtype}, got {parts.dtype} contributions")
-        if self._planned is not None and off1 not in self._planned:
-            raise ValueError(f"subgrid off1={off1} is not in the subgrid_configs this SwiftlyBackward was planned for")
-        F = len(self.facets_config_list)
-        dt0 = chunks[0][1].dtype
-        fstr, off0s, locs = [], [], []
-        fixed = []
-        for c, (sgs, parts) in enumerate(chunks):
-            if parts.shape[0] != F or parts.dtype != dt0:
-                raise ValueError("contribution chunk does not match the facet list / dtype")
-            if parts.stride(3) != 1 or parts.stride(2) != m or (parts.shape[1] > 1 and parts.stride(1) != m * m):
-                parts = parts.contiguous()
-            fixed.append(parts)  # keeps a contiguous copy alive until the launch is queued
-            fstr.append(parts.stride(0) if F > 1 else 0)
-            for b, sg in enumerate(sgs):
-                off0s.append(sg.off0)
-                locs.append((c, b))
-        # chunk offsets are relative to the LOWEST chunk address: the gather-sum kernel reads a negative 64-bit offset
-        # as "no source row", so a chunk allocated below the base (a contiguous copy, a separately allocated chunk
-        # handed to accumulate_chunks) would otherwise be dropped silently
-        base = min(fixed, key=lambda t: t.data_ptr())
-        offs = [(t.data_ptr() - base.data_ptr()) // base.element_size() for t in fixed]
-        if len(chunks) > core.GS_MAX_CHUNKS:
-            raise ValueError(f"at most {core.GS_MAX_CHUNKS} contribution chunks per wave")
-        for _members, table in core.column_row_sources(off0s, locs):
-            core.accumulate_facet_columns(base, m, offs, fstr, table, self._facet_off0s, bands.shape[1], self._masks0,
-                                          off1, bands, self._band, workspace=self._work, touched=self._touched)
-        return bands
-
     def _finish_bands(self):
         torch = _torch()
         core = self.core
         out = []
-        if self._bands is None:
+        bands = self.bands.hand_out()
+        if bands is None:
             dt = self.facet_dtype or torch.complex64
             return [torch.zeros((cfg.size, cfg.size), dtype=dt, device=core.device) for cfg in self.facets_config_list]
-        core.band_zero_untouched(self._bands, self._touched)
-        form = self._decide_b8(self._bands)
+        form = self._decide_b8(bands)
         for j, cfg in enumerate(self.facets_config_list):
             if form.native:  # float32 straight from the row kernels: no complex facet exists
-                out.append(core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size, mask=cfg.mask1, real=True,
+                out.append(core.finish_facet_band(bands[j], self.bands.band, cfg.off1, cfg.size, mask=cfg.mask1, real=True,
                                                   half_length=form.half_length))
             else:
-                out.append(self._handed_out(core.finish_facet_band(self._bands[j], self._band, cfg.off1, cfg.size,
+                out.append(self._handed_out(core.finish_facet_band(bands[j], self.bands.band, cfg.off1, cfg.size,
                                                                    mask=cfg.mask1)))
-        self._bands = None
-        self._work = None
+        self.bands.release()
         return out
-
-    def update_MNAF_BMNAFs(self, off0, NAF_MNAFs):
-        """accumulate_facet for every facet (reference api.py:440-463,
-        api_helper.py:155-179): finish axis 1 (+mask1), add along axis 0."""
-        torch = _torch()
-        core = self.core
-        yN = core.yN_size
-        dev, dt = core.device, NAF_MNAFs.dtype
-        for j, cfg in enumerate(self.facets_config_list):
-            yB = cfg.size
-            t = core.finish_facet(NAF_MNAFs[j], cfg.off1, yB, axis=1, mask=cfg.mask1)
-            if self.MNAF_BMNAFs_persist[j] is None:
-                self.MNAF_BMNAFs_persist[j] = torch.zeros((yN, yB), dtype=dt, device=dev)
-            core.launch("add_to_facet", t, yB, 1, yB, self.MNAF_BMNAFs_persist[j], 1, yB, off0)
-        return self.MNAF_BMNAFs_persist
 
     def finish(self):
         """Flush the column cache and finish all facets (reference
         api.py:374-400, api_helper.py:182-197).  A facet that never received a
         contribution is all zeros (the reference raises AttributeError there,
         api_helper.py:184-187)."""
-        torch = _torch()
-        core = self.core
         if self.wave_axis == 1:
             for _key, staged in self.lru.pop_all():
                 self._flush_staged(staged)
             out = self._finish_bands()
-            self.task_queue.wait_all_done()
-            return [DeviceTask(t) for t in out] if self.delayed else out
-        for old_off0, old_col in self.lru.pop_all():
-            self.update_MNAF_BMNAFs(old_off0, old_col)
-        out = []
-        for cfg, acc in zip(self.facets_config_list, self.MNAF_BMNAFs_persist):
-            if acc is None:
-                dt = self.facet_dtype or torch.complex64
-                out.append(torch.zeros((cfg.size, cfg.size), dtype=dt, device=core.device))
-            else:
-                out.append(self._handed_out(core.finish_facet(acc, cfg.off0, cfg.size, axis=0, mask=cfg.mask0)))
+        else:
+            out = self.columns.finish(self.facet_dtype or _torch().complex64, self._handed_out)
         self.task_queue.wait_all_done()
         return [DeviceTask(t) for t in out] if self.delayed else out

@@ -30,6 +30,7 @@ import numpy
 from . import facet_dtype as fdt
 from .b8_form import B8Facts, choose_b8
 from .k1_form import K1Facts, choose_k1
+from .splitter import SubgridSplitter
 
 __all__ = [
     "FacetSharding",
@@ -770,7 +771,7 @@ class DistributedBackward:
     def __init__(self, swiftly_config, facet_configs, lru_backward=1, group=None, rank_world=None, wave_axis=0,
                  subgrid_configs=None, dtype=None, cooperative=True, whole_waves=False, facet_dtype=None,
                  half_length_finish=False):
-        from .api import SwiftlyBackward  # pylint: disable=import-outside-toplevel
+        from .backward import BandAccumulators, SwiftlyBackward  # pylint: disable=import-outside-toplevel
         from .core_hip import band_range  # pylint: disable=import-outside-toplevel
 
         torch = _torch()
@@ -806,11 +807,8 @@ class DistributedBackward:
             self.local.dtype = self.dtype
         # subgrid holder side: contributions to ALL facets, owner-major order (cooperative facets last)
         self._base_order = sh.arrival_order + sh.coop
-        self.splitter = SwiftlyBackward(
-            swiftly_config, [self.facet_configs[j] for j in self._base_order], lru_backward=1
-        )
-        self.splitter.dtype = self.dtype
-        self._splitters = {tuple(self._base_order): self.splitter}
+        self._splitters = {}  # by facet order: each has its own workspaces
+        self.splitter = self._splitter_of(tuple(self._base_order))
         self._coop, self.coop_pieces = {}, []
         self._coop_band = None
         if sh.coop:
@@ -827,10 +825,14 @@ class DistributedBackward:
             my_plan = [sg for sg in plan if int(sg.off1) in mine]
             if my_plan:
                 for j in sh.coop:
-                    cb = SwiftlyBackward(swiftly_config, [self.facet_configs[j]], lru_backward=lru_backward, wave_axis=1,
-                                         subgrid_configs=my_plan)
-                    cb.dtype = self.dtype
-                    self._coop[j] = cb
+                    self._coop[j] = BandAccumulators(core, [self.facet_configs[j]], my_plan)
+
+    def _splitter_of(self, order):
+        """the splitter whose contributions come out in the facet order ``order``"""
+        splitter = self._splitters.get(order)
+        if splitter is None:
+            splitter = self._splitters[order] = SubgridSplitter(self.core, [self.facet_configs[j] for j in order], self.dtype)
+        return splitter
 
     @property
     def facet_dtype(self):
@@ -894,18 +896,8 @@ class DistributedBackward:
         if mine:
             # the contributions come out in the facet order of the splitter = the arrival order of this wave: with
             # cooperative facets that order depends on the rank that owns the wave, so there is one splitter per owner
-            order = tuple(sh.arrival(key))
-            splitter = self._splitters.get(order)
-            if splitter is None:
-                from .api import SwiftlyBackward  # pylint: disable=import-outside-toplevel
-
-                splitter = self._splitters[order] = SwiftlyBackward(
-                    self.config, [self.facet_configs[j] for j in order], lru_backward=1)
-                splitter.dtype = self.dtype
-            parts = splitter.wave_contributions([sgs[i] for i in mine], subgrids_mine)
-            if parts.dtype != self.dtype:
-                raise ValueError(f"subgrids are {parts.dtype}, the pass was declared {self.dtype}")
-            send = parts.reshape(-1)
+            splitter = self._splitter_of(tuple(sh.arrival(key)))
+            send = splitter.contributions([sgs[i] for i in mine], subgrids_mine).reshape(-1)
         else:
             send = torch.empty(0, dtype=self.dtype, device=core.device)
         return send, in_counts, out_counts
@@ -932,28 +924,34 @@ class DistributedBackward:
             if cnt:
                 chunks.append(([sgs[i] for i in idx], recv[pos : pos + cnt].view(F_local, len(idx), m, m)))
             pos += cnt
-        wave_key = sgs[0].off1 if self.wave_axis == 1 else sgs[0].off0
         if F_whole:
-            self.local.accumulate_chunks(wave_key, [(c, t[:F_whole]) for c, t in chunks])
+            self.local.accumulate_chunks(key, [(c, t[:F_whole]) for c, t in chunks])
         for n, j in enumerate(items[F_whole:]):
-            self._coop[j].accumulate_chunks(wave_key, [(c, t[F_whole + n : F_whole + n + 1]) for c, t in chunks])
+            self._coop[j].accumulate(key, [(c, t[F_whole + n : F_whole + n + 1]) for c, t in chunks])
 
-    def start_wave(self, sgs, subgrids_mine):
-        """:py:meth:`pack_wave` + start of the mirror all-to-all; returns a handle for :py:meth:`finish_wave`."""
+    def _start(self, pack, what, subgrids_mine):
+        """``pack(what, subgrids_mine)`` + start of its all-to-all: ``(what, the pending exchange)``"""
         # the send buffer about to be written may still be read by the exchange started MAX_IN_FLIGHT waves ago
         while len(self._started) >= self.MAX_IN_FLIGHT:
             self._started.pop(0).wait()  # stream-side wait on the collective (no host block for RCCL)
-        send, in_counts, out_counts = self.pack_wave(sgs, subgrids_mine)
-        pending = exchange_blocks(send, in_counts, out_counts, self.group)
+        pending = exchange_blocks(*pack(what, subgrids_mine), self.group)
         self._started.append(pending)
-        return sgs, pending
+        return what, pending
+
+    def _finished(self, handle):
+        """wait for a started exchange: ``(what was started, the receive buffer)``"""
+        what, pending = handle
+        recv = pending.wait()
+        self._started = [q for q in self._started if q is not pending]
+        return what, recv
+
+    def start_wave(self, sgs, subgrids_mine):
+        """:py:meth:`pack_wave` + start of the mirror all-to-all; returns a handle for :py:meth:`finish_wave`."""
+        return self._start(self.pack_wave, sgs, subgrids_mine)
 
     def finish_wave(self, handle):
         """Wait for the exchange and :py:meth:`unpack_wave`."""
-        sgs, pending = handle
-        recv = pending.wait()
-        self._started = [q for q in self._started if q is not pending]
-        self.unpack_wave(sgs, recv)
+        self.unpack_wave(*self._finished(handle))
 
     def add_wave(self, sgs, subgrids_mine):
         """start_wave + finish_wave"""
@@ -1002,19 +1000,11 @@ class DistributedBackward:
 
     def start_group(self, waves, subgrids_mine):
         """:py:meth:`pack_group` + start of the group's all-to-all; handle for :py:meth:`finish_group`"""
-        while len(self._started) >= self.MAX_IN_FLIGHT:
-            self._started.pop(0).wait()
-        send, in_counts, out_counts = self.pack_group(waves, subgrids_mine)
-        pending = exchange_blocks(send, in_counts, out_counts, self.group)
-        self._started.append(pending)
-        return waves, pending
+        return self._start(self.pack_group, waves, subgrids_mine)
 
     def finish_group(self, handle):
         """wait for the exchange of a started group and :py:meth:`unpack_group`"""
-        waves, pending = handle
-        recv = pending.wait()
-        self._started = [q for q in self._started if q is not pending]
-        self.unpack_group(waves, recv)
+        self.unpack_group(*self._finished(handle))
 
     # -- cooperative facets: column ranges out, row blocks in, contiguous-axis finish on this rank's rows -------------
     def pack_coop_finish(self, j):
@@ -1025,14 +1015,13 @@ class DistributedBackward:
         core, sh = self.core, self.sharding
         yB = self.facet_configs[j].size
         ncol = self._coop_sub[self.rank][1]
-        cb = self._coop.get(j)
+        bands = self._coop[j].hand_out() if ncol and j in self._coop else None
         if ncol == 0:
             acc = torch.empty(0, dtype=self.dtype, device=core.device)
-        elif cb is None or cb._bands is None:  # pylint: disable=protected-access
+        elif bands is None:
             acc = torch.zeros((yB, ncol), dtype=self.dtype, device=core.device)
         else:
-            core.band_zero_untouched(cb._bands, cb._touched)  # pylint: disable=protected-access
-            acc = cb._bands[0]  # pylint: disable=protected-access
+            acc = bands[0]
             if tuple(acc.shape) != (yB, ncol):
                 raise ValueError("internal: cooperative accumulator does not match the wave range's band")
         in_counts = [sh.coop_rows(yB, d)[1] * ncol for d in range(self.world)]

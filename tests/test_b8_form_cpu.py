@@ -72,14 +72,15 @@ def configs(cover):
 
 def backward_of(case, cover, core=None, auto_axis=None, accumulators=None):
     """a ``SwiftlyBackward`` as its constructor leaves it (and, with ``accumulators``, as the first wave does), without a device"""
-    from ska_sdp_exec_swiftly_amd.backward import SwiftlyBackward
+    from ska_sdp_exec_swiftly_amd.backward import BandAccumulators, SwiftlyBackward
 
     bwd = object.__new__(SwiftlyBackward)
     bwd.core = core or _Core(case)
     bwd._auto_axis, bwd.wave_axis = bool(auto_axis), case.wave_axis
     bwd._facet_dtype, bwd._want_half_length = torch_dtype(case.facet_dtype), case.half_length_asked
     bwd.facets_config_list = configs(cover)
-    bwd._bands = None if accumulators is None else torch.empty((len(cover), 2, 4), dtype=torch_dtype(accumulators))
+    bwd.bands = BandAccumulators(bwd.core, bwd.facets_config_list)
+    bwd.bands.bands = None if accumulators is None else torch.empty((len(cover), 2, 4), dtype=torch_dtype(accumulators))
     return bwd
 
 
@@ -189,10 +190,10 @@ def test_decide_b8_gathers_what_the_recorded_methods_read(tables):
             bwd = backward_of(case, bc.COVERS[case.cover], auto_axis=case.auto_axis, accumulators=case.accumulators)
             got = native_char(bwd.real_finish_native) + "01"[bwd.half_length_finish]
             assert bwd.real_finish_native in (None, False, True) and bwd.half_length_finish in (False, True)
-            if bwd._bands is None:  # pylint: disable=protected-access
+            if bwd.bands.bands is None:
                 got += "--"
             else:
-                fin = bwd._decide_b8(bwd._bands)  # pylint: disable=protected-access
+                fin = bwd._decide_b8(bwd.bands.bands)  # pylint: disable=protected-access
                 got += "01"[bool(fin.native)] + "01"[bool(fin.half_length)]
         if got != want:
             wrong.append((case, got, want))
@@ -209,12 +210,12 @@ def test_finish_bands_runs_the_form_it_decided():
             continue
         bwd = backward_of(case, bc.COVERS[case.cover], accumulators=case.accumulators)
         bwd.core.band_zero_untouched = lambda bands, touched: None
-        bwd._band, bwd._touched, bwd._work = (0, 4), None, None  # pylint: disable=protected-access
-        want = bwd._decide_b8(bwd._bands)  # pylint: disable=protected-access
+        bwd.bands.band, bwd.bands.touched, bwd.bands.work = (0, 4), None, None
+        want = bwd._decide_b8(bwd.bands.bands)  # pylint: disable=protected-access
         out = bwd._finish_bands()  # pylint: disable=protected-access
         assert bwd.core.finished == [(bool(want.native), want.half_length)] * len(out), case
         assert all(t.dtype == (bwd._facet_dtype or torch_dtype(case.accumulators)) for t in out), case  # pylint: disable=protected-access
-        assert bwd._bands is None  # pylint: disable=protected-access
+        assert bwd.bands.bands is None
 
 
 def test_distributed_backward_gives_the_recorded_answers(tables):

@@ -130,7 +130,7 @@ def test_backward_band_sparse_plan_and_overlaps():
     by1 = sorted(range(len(keep)), key=lambda i: keep[i].off1)
     b0.add_new_subgrid_tasks(keep, data)
     b1.add_new_subgrid_tasks([keep[i] for i in by1], [data[i] for i in by1])
-    assert b1._band[1] < cfg.core.yN_size  # pylint: disable=protected-access
+    assert b1.bands.band[1] < cfg.core.yN_size
     # truth: the reference schedule in complex128; both complex64 schedules must sit at the float32 level
     b64 = sw.SwiftlyBackward(cfg, facet_cfgs, wave_axis=0)
     b64.add_new_subgrid_tasks(keep, [d.to(torch.complex128) for d in data])

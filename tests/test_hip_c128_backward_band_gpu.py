@@ -447,8 +447,8 @@ def whole_waves_result(P):
     inner = bwd._add_wave
     bwd._add_wave = lambda sgs, subs: (folds.append(len(sgs)), inner(sgs, subs))[1]
     bwd.add_new_subgrid_tasks([sg[i] for i in by1], [data[i] for i in by1])
-    assert bwd._bands.dtype == torch.complex128 and bwd._work.dtype == torch.complex128
-    assert bwd._masks0 is not None and bwd._masks0.dtype == torch.float64
+    assert bwd.bands.bands.dtype == torch.complex128 and bwd.bands.work.dtype == torch.complex128
+    assert bwd.bands.masks0 is not None and bwd.bands.masks0.dtype == torch.float64
     n1 = len({c.off1 for c in sg})
     assert folds == [len(sg) // n1] * n1  # whole waves: no staging copy
     P["got_plan"] = finished(bwd)
@@ -488,7 +488,7 @@ def test_backward_small_without_a_plan_delayed_and_in_chunks():
     # no plan: the band is the whole padded axis
     bwd = band_backward(P)
     bwd.add_new_subgrid_tasks([sg[i] for i in by1], [data[i] for i in by1])
-    assert bwd._band == (0, yN)
+    assert bwd.bands.band == (0, yN)
     pass_rule("no plan (whole-axis band)", finished(bwd), P["want"], P["e_ref"])
     # delayed=True: DeviceTask handles
     bwd = band_backward(P, subgrid_configs=sg, delayed=True)
@@ -528,7 +528,7 @@ def test_backward_small_sparse_plan_with_duplicates():
     b1 = band_backward(P, subgrid_configs=keep)
     by1 = sorted(range(len(keep)), key=lambda i: keep[i].off1)
     b1.add_new_subgrid_tasks([keep[i] for i in by1], [data[i] for i in by1])
-    assert b1._band[1] < cfg.core.yN_size
+    assert b1.bands.band[1] < cfg.core.yN_size
     pass_rule("sparse plan with duplicates", finished(b1), want, e_ref)
 
 
@@ -556,7 +556,7 @@ def test_backward_band_without_a_split_instance():
     e_ref = relrms(finished(b0), want)
     b1 = sw.SwiftlyBackward(cfg, facet_cfgs, wave_axis=1, subgrid_configs=sg_cfgs, dtype=torch.complex128)
     b1.add_new_subgrid_tasks(sg_cfgs, data)
-    assert "work" not in b1._wsbuf  # the general launch sequence, not wave_split_subgrids
+    assert "work" not in b1.splitter._wsbuf  # the general launch sequence, not wave_split_subgrids
     pass_rule("(64, 256): no split instance", finished(b1), want, e_ref)
 
 
@@ -582,7 +582,7 @@ def test_backward_64k_n16k_1k():
     want = numpy.array([oracle.facet_rows(j, rows[j]) for j in range(2)])
     b1 = sw.SwiftlyBackward(cfg, facet_cfgs, wave_axis=1, subgrid_configs=sg_cfgs, dtype=torch.complex128)
     b1.add_new_subgrid_tasks(sg_cfgs, data)
-    assert b1._band[1] < core.yN_size and b1._bands.dtype == torch.complex128
+    assert b1.bands.band[1] < core.yN_size and b1.bands.bands.dtype == torch.complex128
     out1 = b1.finish()
     del b1
     b0 = sw.SwiftlyBackward(cfg, facet_cfgs, wave_axis=0)
@@ -639,9 +639,9 @@ def test_defaults_and_refusals():
     # ... and not only at the first data: complex64 contributions after a complex128 wave has created the accumulators
     bwd = sw.SwiftlyBackward(cfg, facet_cfgs, wave_axis=1, dtype=torch.complex128)
     p128 = bwd.wave_contributions([sg], [d128])
-    assert p128.dtype == torch.complex128 and "work" in bwd._wsbuf  # (the split kernel, on the explicit schedule only)
+    assert p128.dtype == torch.complex128 and "work" in bwd.splitter._wsbuf  # (the split kernel, on the explicit schedule only)
     bwd.accumulate_wave([sg], p128)
-    assert bwd._bands is not None
+    assert bwd.bands.bands is not None
     for call in (lambda: bwd.accumulate_wave([sg], p128.to(torch.complex64)),
                  lambda: bwd.accumulate_chunks(sg.off1, [([sg], p128), ([sg], p128.to(torch.complex64))]),
                  lambda: bwd.add_new_subgrid_tasks([sg, sg], [d64, d64]),
@@ -651,12 +651,12 @@ def test_defaults_and_refusals():
     core = cfg.core
     with pytest.raises(ValueError, match="complex64"):
         core.accumulate_facet_columns(p128.to(torch.complex64), core.xM_yN_size, [0], [0], core.column_row_sources([0])[0][1],
-                                      [0, 0], yB, None, 0, bwd._bands, bwd._band)
+                                      [0, 0], yB, None, 0, bwd.bands.bands, bwd.bands.band)
     assert all(t.dtype == torch.complex128 for t in bwd.finish())
     # every complex128 path that existed before keeps the general launch sequence for its contributions
     for kw in (dict(wave_axis=0), dict(subgrid_configs=[sg]), dict(wave_axis=0, dtype=torch.complex128)):
         old = sw.SwiftlyBackward(cfg, facet_cfgs, **kw)
-        assert old.wave_contributions([sg], [d128]).dtype == torch.complex128 and "work" not in old._wsbuf, kw
+        assert old.wave_contributions([sg], [d128]).dtype == torch.complex128 and "work" not in old.splitter._wsbuf, kw
     with pytest.raises(ValueError):
         sw.SwiftlyBackward(cfg, facet_cfgs, wave_axis=1, dtype=torch.float64)
     # facets of two sizes

@@ -7,7 +7,7 @@ import numpy
 import pytest
 
 from oracle import swiftly_oracle as orc
-from ska_sdp_exec_swiftly_amd import api, api_helper, prefetch
+from ska_sdp_exec_swiftly_amd import api, api_helper, backward, prefetch
 from ska_sdp_exec_swiftly_amd.core_hip import calculate_pswf
 from ska_sdp_exec_swiftly_amd.swift_configs import SWIFT_CONFIGS
 
@@ -421,6 +421,8 @@ def test_backward_wave_entry_points_check_the_wave_key():
     bwd.wave_axis = 1
     bwd.core = types.SimpleNamespace(xM_yN_size=4, yN_size=16)
     bwd.facets_config_list = [api.FacetConfig(0, 0, 8)]
+    bwd.bands = backward.BandAccumulators(bwd.core, bwd.facets_config_list)
+    bwd.columns = backward.ColumnAccumulators(bwd.core, bwd.facets_config_list)
     same_off0 = [api.SubgridConfig(0, 0, 8), api.SubgridConfig(0, 8, 8)]  # the reference's accumulate_column grouping
     with pytest.raises(ValueError, match="share off1"):
         bwd.accumulate_wave(same_off0, numpy.zeros((1, 2, 4, 4), dtype=numpy.complex64))

@@ -79,7 +79,7 @@ def one_pass(sw, torch, cfg, facet_cfgs, plan, data, axis):
     for a, b, kind in zip(marks, marks[1:], kinds):
         stage[kind] += a.elapsed_time(b)
     total = marks[0].elapsed_time(marks[-1])
-    band_len = bwd._band[1] if axis and bwd._band else 0  # pylint: disable=protected-access
+    band_len = bwd.bands.band[1] if axis and bwd.bands.band else 0
     del bwd, out
     return total, stage, band_len
 
