@@ -125,9 +125,17 @@ enum {
     SWIFTLY_FEATURE_REAL_FACETS_RFFT = 12,      /* prepare_facet_band_rfft / prepare_facet_band_rows_rfft (dtype = the OUTPUT
                                                    type), size part: the sizes of REAL_FACETS with yN_size 32768.  The gate both
                                                    entry points refuse through ("real facets, half-length: ...") */
-    SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R = 13    /* finish_facet_band_c2r (dtype = the INPUT type), size part: the sizes of
+    SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R = 13,   /* finish_facet_band_c2r (dtype = the INPUT type), size part: the sizes of
                                                    REAL_FACETS_OUT with yN_size 32768.  The gate the entry point refuses
                                                    through ("real facets out, half-length: ...") */
+    SWIFTLY_FEATURE_REAL_FACETS_F64 = 14,       /* prepare_facet_band_real64 (dtype = the OUTPUT type): FLOAT64 facets into the
+                                                   complex128 K1 -- the sizes of BAND_PIPELINE_EXPLICIT in complex128 (n_facets
+                                                   not counted); complex64 is answered no (float32 facets: REAL_FACETS).  The
+                                                   gate the entry point refuses through ("real facets, float64: ...") */
+    SWIFTLY_FEATURE_REAL_FACETS_OUT_F64 = 15    /* finish_facet_band_real64 (dtype = the INPUT type): FLOAT64 facets out of the
+                                                   complex128 backward band -- the sizes of BACKWARD_BAND_EXPLICIT in
+                                                   complex128; complex64 is answered no (float32 facets: REAL_FACETS_OUT).  The
+                                                   gate the entry point refuses through ("real facet output, float64: ...") */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -393,6 +401,19 @@ int swiftly_hip_prepare_facet_band_rows_real(swiftly_hip_t* h, int dtype, const 
                                              int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                              int64_t band_start, int64_t band_len, int64_t other_axis_size,
                                              int64_t other_axis_row0, void* stream);
+/* K1 of a real-valued FLOAT64 facet in complex128: the argument list of swiftly_hip_prepare_facet_band_real with `in`
+ * pointing to FLOAT64, in_row_stride counting real elements, and `dtype` the type of the OUTPUT, which must be SWIFTLY_C128.
+ * The complex128 row kernels (one workgroup per row up to 8192 points; pass A of the two-kernel long-row form at 16384 /
+ * 32768) load the reals -- 8 bytes per pixel where the promoted facet holds 16 -- and set the imaginary parts to zero in
+ * registers.  Value contract: `out` holds, bit for bit, what swiftly_hip_prepare_facet_band gives for the same facet promoted
+ * to complex128 (the instances and their code after the load are the same, and every operation on a zero imaginary part is
+ * exact), whatever in_row_stride; no instance is exempt.  The band must be (0, yN_size) as for every complex128 K1; there is
+ * no _rows form (complex128 has no row blocks).  Sizes: SWIFTLY_FEATURE_REAL_FACETS_F64; a refusal is
+ * SWIFTLY_ERR_UNSUPPORTED ("real facets, float64: ...") and nothing is written.  The _real, _rfft entry points above keep
+ * refusing SWIFTLY_C128: this is a door of its own. */
+int swiftly_hip_prepare_facet_band_real64(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                          int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                          int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream);
 /* K1 of a real-valued facet as a HALF-LENGTH transform: the argument lists and the stored quantity of the two _real entry
  * points above (`in` float32, in_row_stride in reals, `dtype` the OUTPUT type; inverse-transform convention of prepare_facet,
  * 1 / yN_size, the folded window of the other axis; parity-split band), computed by ONE workgroup per row from one
@@ -693,6 +714,18 @@ int swiftly_hip_finish_facet_band(swiftly_hip_t* h, int dtype, const void* in, i
 int swiftly_hip_finish_facet_band_real(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
                                        int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
                                        int64_t facet_off, int64_t facet_size, const void* mask, void* stream);
+/* finish_facet_band for a real-valued FLOAT64 facet in complex128: the argument list of swiftly_hip_finish_facet_band_real
+ * with `in` a COMPLEX128 band accumulator (`dtype` = SWIFTLY_C128, the type of the input) over any band the complex128
+ * swiftly_hip_finish_facet_band takes, `out` pointing to FLOAT64, and out_row_stride counting real elements.  The complex128
+ * row kernels (one workgroup per row up to 8192 points; pass B of the long-row form at 16384 / 32768) store the real part
+ * only: 8 bytes per pixel, and no complex128 facet exists at any time.  Value contract: `out` holds, bit for bit, the real
+ * parts of what swiftly_hip_finish_facet_band stores for the same band rows, whatever out_row_stride; no instance is exempt.
+ * out_row_stride < facet_size (overlapping rows) is SWIFTLY_ERR_PARAM.  Sizes: SWIFTLY_FEATURE_REAL_FACETS_OUT_F64; a
+ * refusal is SWIFTLY_ERR_UNSUPPORTED ("real facet output, float64: ...") and nothing is written.  The _real and _c2r entry
+ * points keep refusing SWIFTLY_C128: this is a door of its own. */
+int swiftly_hip_finish_facet_band_real64(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                         int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
+                                         int64_t facet_off, int64_t facet_size, const void* mask, void* stream);
 /* finish_facet_band_real as ONE HALF-LENGTH transform per row (csrc/swiftly_rowc2r.h): only the real part of the 32768-point
  * transform of a band row is wanted, and that is the transform of the row's Hermitian part -- one 16384-point complex
  * transform of a recombination of the band elements k, k + yN/2 and their mirrors, in one workgroup per row, where the entry

@@ -7,6 +7,7 @@ int launch_fft_long_a(const RowsArgs<double>& a, const OffTab& tab, const LongAr
     const int tiles = (1 << L.log_n2) / G::RB;
     if (L.nrows <= 0) return 0;
     const dim3 grid((unsigned)((long long)L.nrows * tiles), a.nbatch > 0 ? a.nbatch : 1);
+    if (a.real_in) return launch_lds<fft_long_a_kernel<G, double, true>, kLongALds>(grid, dim3(G::NT), s, a, tab, L);
     return launch_lds<fft_long_a_kernel<G, double>, kLongALds>(grid, dim3(G::NT), s, a, tab, L);
 }
 }  // namespace swf

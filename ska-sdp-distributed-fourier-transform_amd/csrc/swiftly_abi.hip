@@ -578,7 +578,8 @@ static int run_rows_long(swiftly_hip* h, int logn, RowsArgs<double>& a, const Of
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)a.nrows, budget / row_bytes));
     void* scratch = nullptr;
     HIP_TRY(hipMallocAsync(&scratch, (size_t)chunk * row_bytes, st));
-    RowsArgs<double> A = a;
+    RowsArgs<double> A = a;  // (real_in, float64 rows, is pass A's alone: pass B reads the complex scratch)
+    A.real_out = 0;
     A.tw = tw1;
     A.full_logn = logn;
     A.full_n = 0;
@@ -589,7 +590,8 @@ static int run_rows_long(swiftly_hip* h, int logn, RowsArgs<double>& a, const Of
     L.tw_full = tw_full;
     // pass B: rows of the chunk x outer index k1 = n1 sub-transforms of length n2 per row; the n1 workgroups of a row block
     // are enumerated next to each other on one XCD (outer_group), whose L2 merges their interleaved output elements
-    RowsArgs<double> B = a;
+    RowsArgs<double> B = a;  // (real_out, float64 rows, is pass B's alone: pass A writes the complex scratch)
+    B.real_in = 0;
     B.tw = tw2;
     B.in = (const cx<double>*)scratch;
     B.raw_ld = 1;
@@ -620,7 +622,8 @@ static int run_rows_long(swiftly_hip* h, int logn, RowsArgs<double>& a, const Of
         rc = launch_status(launch_fft_long_a(A, tab, L, st), "long-row pass A");
         if (rc) break;
         B.nrows = rows;
-        B.out = a.out + (long long)row0 * a.out_rs;
+        // (out_rs counts reals when the rows are float64)
+        B.out = a.real_out ? (cx<double>*)((double*)a.out + (long long)row0 * a.out_rs) : a.out + (long long)row0 * a.out_rs;
         B.row_win = a.row_win ? a.row_win + row0 : nullptr;
         rc = launch_checked(l2, B, tab, st);
     }
@@ -674,6 +677,12 @@ static int run_rows_chunk(swiftly_hip* h, int logn, RowsArgs<R>& a, const OffTab
         return fail(SWIFTLY_ERR_UNSUPPORTED, "transform length 65536 is only supported for complex64 prepare_* / finish_* "
                     "calls with unit stride along the transform axis or along a strided axis of contiguous rows");
     if constexpr (sizeof(R) == 8) {
+        // float64 rows: the single-workgroup instances of the generic kernel (launch_fft_rows refuses lengths without one) and
+        // the long-row pair below, which hands real_in to its pass A and real_out to its pass B
+        if (a.real_in && (sub || a.rowfast || a.raw_ld))
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: float64 input reaches a decomposed transform of 2^%d points", logn);
+        if (a.real_out && (sub || a.rowfast || a.raw_st || a.st_rowmap || a.accumulate))
+            return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: float64 output reaches a transform of 2^%d points without a real store", logn);
         if (!a.rowfast && logn > kMaxLogNDouble) {  // 16384 / 32768 complex128 points along the contiguous axis
             if (sub || a.raw_ld)
                 return fail(SWIFTLY_ERR_UNSUPPORTED, "complex128 transform length %d along the contiguous axis: only the "
@@ -1281,7 +1290,7 @@ int swiftly_hip_finish_facet(swiftly_hip_t* h, int dtype, const void* in, int64_
                                           mask, 1, 0, 0, nullptr, 0, stream);
 }
 
-// The seven K1 entry points below are one implementation: prepare_facet_band for the rows [other_axis_row0,
+// The eight K1 entry points below are one implementation: prepare_facet_band for the rows [other_axis_row0,
 // other_axis_row0 + rows) of a facet whose other axis has other_axis_size pixels -- the folded window of the other axis is
 // that facet's, not the one of a `rows`-pixel facet (cooperative facets of the multi-GPU pass: every rank transforms a block
 // of rows of the same facet); other_axis_size = 0: no window of the other axis.  The forms differ in the capability rule they
@@ -1295,6 +1304,8 @@ enum class K1Form {
                      // never handed to the band row kernel
     WindowRows,      // the whole-row kernel storing complete window rows (swiftly_rowwhole.h)
     RealWindowRows,  // ... loading float32 rows: SWIFTLY_FEATURE_REAL_WINDOW_ROWS
+    RealBand64,      // Band in complex128 loading FLOAT64 rows: SWIFTLY_FEATURE_REAL_FACETS_F64 (a door of its own: the float32
+                     // forms above keep refusing complex128)
 };
 static int prepare_facet_k1(K1Form form, swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                             int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off, int64_t band_start,
@@ -1310,12 +1321,14 @@ static int prepare_facet_k1(K1Form form, swiftly_hip_t* h, int dtype, const void
                     (long long)rows, (long long)other_axis_size);
     DeviceGuard device_guard_(h->device);
     CHECK_DTYPE();
-    if (real_in) {  // float32 rows: the capability rule of the form's feature
+    if (real_in) {  // float32 (RealBand64: float64) rows: the capability rule of the form's feature
         const std::string why = form == K1Form::RealWindowRows ? why_not_real_window_rows(*h, dtype)
+                                : form == K1Form::RealBand64   ? why_not_real_facets_f64(*h, dtype)
                                 : half                         ? why_not_real_facets_rfft(*h, dtype)
                                                                : why_not_real_facets(*h, dtype);
         if (!why.empty())
             return fail(SWIFTLY_ERR_UNSUPPORTED, "%s: %s", form == K1Form::RealWindowRows ? "prepare_facet_window_rows_real"
+                        : form == K1Form::RealBand64 ? "prepare_facet_band_real64"
                         : half ? "prepare_facet_band_rfft" : "prepare_facet_band_real", why.c_str());
     }
     CHECK_FACET_SIZE();
@@ -1333,7 +1346,8 @@ static int prepare_facet_k1(K1Form form, swiftly_hip_t* h, int dtype, const void
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rows: complex128 has no row blocks");
         if (rows == 0) return 0;
         return do_prepare_facet<double>(h, in, rows, facet_size, in_row_stride, 1, out, out_row_stride, 1, facet_off, INT64_MIN,
-                                        nullptr, nullptr, fold_other_axis_window, 0, (hipStream_t)stream);
+                                        nullptr, nullptr, fold_other_axis_window, 0, (hipStream_t)stream,
+                                        /*real_in=*/form == K1Form::RealBand64);  // (the only real form its rule lets through)
     }
     const bool mixed_yN = h->log_yN < 0 && h->mixed.count(h->yN) && h->mixed.at(h->yN).tw_f;
     if (!mixed_yN && (h->log_yN < kMinLogN || h->log_yN > kBandMaxLogYN))
@@ -1426,6 +1440,12 @@ int swiftly_hip_prepare_facet_band_real(swiftly_hip_t* h, int dtype, const void*
     return swiftly_hip_prepare_facet_band_rows_real(h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
                                                     band_start, band_len, fold_other_axis_window ? rows : 0, 0, stream);
 }
+int swiftly_hip_prepare_facet_band_real64(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
+                                          int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
+                                          int64_t band_start, int64_t band_len, int fold_other_axis_window, void* stream) {
+    return prepare_facet_k1(K1Form::RealBand64, h, dtype, in, rows, facet_size, in_row_stride, out, out_row_stride, facet_off,
+                            band_start, band_len, fold_other_axis_window ? rows : 0, 0, stream);
+}
 int swiftly_hip_prepare_facet_band_rows_rfft(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t facet_size,
                                              int64_t in_row_stride, void* out, int64_t out_row_stride, int64_t facet_off,
                                              int64_t band_start, int64_t band_len, int64_t other_axis_size,
@@ -1485,17 +1505,21 @@ enum class B8Form {
     HalfLengthReal,  // one half-length transform per row (swiftly_rowc2r.h), SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R: its own kernel
                      // and its own refusals -- a call the kernel does not take is refused before anything is written, never
                      // handed to the real-store form
+    RealStore64,     // complex128 band rows in, FLOAT64 rows out: SWIFTLY_FEATURE_REAL_FACETS_OUT_F64 (a door of its own: the
+                     // float32 forms above keep refusing complex128)
 };
 static int finish_facet_band_impl(B8Form form, swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
                                   int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
                                   int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
     const int64_t in_cs = 1, out_cs = 1;
     const bool real_out = form != B8Form::Complex, half = form == B8Form::HalfLengthReal;
-    const char* name = half ? "finish_facet_band_c2r" : "finish_facet_band_real";
+    const char* name = half ? "finish_facet_band_c2r" : form == B8Form::RealStore64 ? "finish_facet_band_real64" : "finish_facet_band_real";
     CHECK_COMMON();
-    if (real_out) {  // float32 rows out: the capability rule of the form's feature
-        if (const std::string why = half ? why_not_real_facets_out_c2r(*h, dtype) : why_not_real_facets_out(*h, dtype); !why.empty())
-            return fail(SWIFTLY_ERR_UNSUPPORTED, "%s: %s", name, why.c_str());
+    if (real_out) {  // float32 (RealStore64: float64) rows out: the capability rule of the form's feature
+        const std::string why = half                          ? why_not_real_facets_out_c2r(*h, dtype)
+                                : form == B8Form::RealStore64 ? why_not_real_facets_out_f64(*h, dtype)
+                                                              : why_not_real_facets_out(*h, dtype);
+        if (!why.empty()) return fail(SWIFTLY_ERR_UNSUPPORTED, "%s: %s", name, why.c_str());
     }
     CHECK_FACET_SIZE();
     if (real_out && out_row_stride < facet_size)
@@ -1558,6 +1582,12 @@ int swiftly_hip_finish_facet_band_real(swiftly_hip_t* h, int dtype, const void* 
                                        int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
                                        int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
     return finish_facet_band_impl(B8Form::RealStore, h, dtype, in, rows, in_row_stride, band_start, band_len, out,
+                                  out_row_stride, facet_off, facet_size, mask, stream);
+}
+int swiftly_hip_finish_facet_band_real64(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,
+                                         int64_t band_start, int64_t band_len, void* out, int64_t out_row_stride,
+                                         int64_t facet_off, int64_t facet_size, const void* mask, void* stream) {
+    return finish_facet_band_impl(B8Form::RealStore64, h, dtype, in, rows, in_row_stride, band_start, band_len, out,
                                   out_row_stride, facet_off, facet_size, mask, stream);
 }
 int swiftly_hip_finish_facet_band_c2r(swiftly_hip_t* h, int dtype, const void* in, int64_t rows, int64_t in_row_stride,

@@ -77,6 +77,8 @@ int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int
             case SWIFTLY_FEATURE_REAL_WINDOW_ROWS: why = why_not_real_window_rows(s, dtype); break;
             case SWIFTLY_FEATURE_REAL_FACETS_RFFT: why = why_not_real_facets_rfft(s, dtype); break;
             case SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R: why = why_not_real_facets_out_c2r(s, dtype); break;
+            case SWIFTLY_FEATURE_REAL_FACETS_F64: why = why_not_real_facets_f64(s, dtype); break;
+            case SWIFTLY_FEATURE_REAL_FACETS_OUT_F64: why = why_not_real_facets_out_f64(s, dtype); break;
             default: why = reason("unknown feature %d", feature);
         }
     }

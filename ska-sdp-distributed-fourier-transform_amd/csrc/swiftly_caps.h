@@ -249,7 +249,7 @@ inline std::string why_not_split_band(const Sizes& s) {
 }
 // real-valued (float32) facets into the forward K1 (prepare_facet_band_real / prepare_facet_band_rows_real): the complex64 band
 // pipeline with a power-of-two yN -- the row kernels of both band layouts have a real-load form, the radix-Q pass in front of
-// the Q * 2^k lengths has none, and there is no float64 -> complex128 form
+// the Q * 2^k lengths has none; float64 facets into complex128 are a feature of their own (why_not_real_facets_f64)
 inline std::string why_not_real_facets(const Sizes& s, int dtype) {
     if (dtype == SWIFTLY_C128) return "real facets: complex64 output only (no float64 -> complex128 load in the complex128 row kernels)";
     if (dtype != SWIFTLY_C64) return reason("real facets: unknown dtype %d", dtype);
@@ -259,13 +259,34 @@ inline std::string why_not_real_facets(const Sizes& s, int dtype) {
 }
 // real-valued (float32) facets out of the backward band pass (finish_facet_band_real): the complex64 backward band with a
 // power-of-two yN -- the row kernels behind finish_facet_band have a real-store form, the radix-Q pass behind Q * 2^k and
-// the Bluestein kernel have none, and there is no complex128 -> float64 store
+// the Bluestein kernel have none; float64 facets out of complex128 are a feature of their own (why_not_real_facets_out_f64)
 inline std::string why_not_real_facets_out(const Sizes& s, int dtype) {
     if (dtype == SWIFTLY_C128)
         return "real facet output: complex64 input only (no complex128 -> float64 store in the complex128 row kernels)";
     if (dtype != SWIFTLY_C64) return reason("real facet output: unknown dtype %d", dtype);
     if (std::string why = why_not_backward_band(s, SWIFTLY_C64); !why.empty()) return "real facet output: " + why;
     if (s.log_yN < 0) return reason("real facet output: yN %lld is Q * 2^k: the radix-Q pass has no real store", (long long)s.yN);
+    return {};
+}
+// real-valued FLOAT64 facets into the complex128 forward K1 (prepare_facet_band_real64): the sizes of the complex128 band
+// pipeline -- its row kernels (swiftly_rows.h up to 8192 points, pass A of swiftly_rowslong.h above) have a float64-load form
+inline std::string why_not_real_facets_f64(const Sizes& s, int dtype) {
+    if (dtype == SWIFTLY_C64)
+        return "real facets, float64: complex128 output only (float32 facets into complex64: features 8 / 9, "
+               "SWIFTLY_FEATURE_REAL_FACETS / SWIFTLY_FEATURE_REAL_FACETS_OUT)";
+    if (dtype != SWIFTLY_C128) return reason("real facets, float64: unknown dtype %d", dtype);
+    if (std::string why = why_not_band_pipeline(s, SWIFTLY_C128, 0, true); !why.empty()) return "real facets, float64: " + why;
+    return {};
+}
+// real-valued FLOAT64 facets out of the complex128 backward band (finish_facet_band_real64): the sizes of the complex128
+// backward band -- the row kernels behind its finish_facet_band (swiftly_rows.h, also as pass B of the long rows) have a
+// float64-store form
+inline std::string why_not_real_facets_out_f64(const Sizes& s, int dtype) {
+    if (dtype == SWIFTLY_C64)
+        return "real facet output, float64: complex128 input only (float32 facets out of complex64: features 8 / 9, "
+               "SWIFTLY_FEATURE_REAL_FACETS / SWIFTLY_FEATURE_REAL_FACETS_OUT)";
+    if (dtype != SWIFTLY_C128) return reason("real facet output, float64: unknown dtype %d", dtype);
+    if (std::string why = why_not_backward_band(s, SWIFTLY_C128, true); !why.empty()) return "real facet output, float64: " + why;
     return {};
 }
 // real-valued facets through the half-length K1 (prepare_facet_band_rfft / prepare_facet_band_rows_rfft, swiftly_rowreal.h):

@@ -35,7 +35,10 @@ struct LongArgs {
     const cx<R>* tw_full;    // exp(-2 pi i k / n), k < n
 };
 
-template <class G, typename R>
+// REAL_IN (RowsArgs::real_in, float64 facet rows into the complex128 K1): `A.in` points to R, in_rs / in_cs / in_bs count
+// reals; the imaginary part is zero in registers as in load_in of fft_rows_kernel, so everything after the load sees the
+// values of the promoted row.
+template <class G, typename R, bool REAL_IN = false>
 __global__ __launch_bounds__(G::NT) void fft_long_a_kernel(const RowsArgs<R> A, const OffTab tab, const LongArgs<R> L) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int P = G::P, T = G::T, RB = G::RB;
@@ -60,7 +63,15 @@ __global__ __launch_bounds__(G::NT) void fft_long_a_kernel(const RowsArgs<R> A, 
     const bool absent = in_row < 0;  // row absent from a compacted input: reads as zeros
     if (absent) in_row = 0;
     const int b = blockIdx.y;
-    const cx<R>* __restrict__ in = A.in + in_row * A.in_rs + (long long)b * A.in_bs;
+    const long long in_base = in_row * A.in_rs + (long long)b * A.in_bs;
+    const cx<R>* __restrict__ in = A.in + (REAL_IN ? 0ll : in_base);
+    const R* __restrict__ rin = reinterpret_cast<const R*>(A.in) + (REAL_IN ? in_base : 0ll);
+    auto load_in = [&](size_t e) -> cx<R> {
+        if constexpr (REAL_IN)
+            return cx<R>{rin[e], (R)0};
+        else
+            return in[e];
+    };
     const int ld_a = (tab.use & 1) ? tab.ld_a[b] : A.ld.a;
     const int ld_c = (tab.use & 2) ? tab.ld_c[b] : A.ld.c;
     const R csign_ld = A.conj_ld ? (R)-1 : (R)1;
@@ -80,7 +91,7 @@ __global__ __launch_bounds__(G::NT) void fft_long_a_kernel(const RowsArgs<R> A, 
         const int qs = ok ? q : 0;
         int idx = qs + ld_c;
         if (idx >= A.ld.mod) idx -= A.ld.mod;
-        cx<R> val = in[(size_t)((unsigned)idx * A.in_cs)];
+        cx<R> val = load_in((size_t)((unsigned)idx * A.in_cs));
         R w = win1[qs * w1s] * win2[qs * w2s];
         w = ok ? w * live_f : (R)0;
         val.x *= w;

@@ -19,7 +19,7 @@ ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
 (FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
  FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE, FEATURE_REAL_FACETS,
  FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH, FEATURE_REAL_WINDOW_ROWS, FEATURE_REAL_FACETS_RFFT,
- FEATURE_REAL_FACETS_OUT_C2R) = range(14)
+ FEATURE_REAL_FACETS_OUT_C2R, FEATURE_REAL_FACETS_F64, FEATURE_REAL_FACETS_OUT_F64) = range(16)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None
@@ -117,6 +117,9 @@ def _declare(lib):
     lib.swiftly_hip_prepare_facet_band_real.argtypes = list(lib.swiftly_hip_prepare_facet_band.argtypes)
     lib.swiftly_hip_prepare_facet_band_rows_real.restype = c_int
     lib.swiftly_hip_prepare_facet_band_rows_real.argtypes = list(lib.swiftly_hip_prepare_facet_band_rows.argtypes)
+    # float64 rows into the complex128 K1 (same arguments; `in` is float64, the row stride counts reals, dtype = C128)
+    lib.swiftly_hip_prepare_facet_band_real64.restype = c_int
+    lib.swiftly_hip_prepare_facet_band_real64.argtypes = list(lib.swiftly_hip_prepare_facet_band.argtypes)
     # ... as ONE half-length transform per row (same arguments; a door of its own: rounds differently, refuses odd layouts)
     lib.swiftly_hip_prepare_facet_band_rfft.restype = c_int
     lib.swiftly_hip_prepare_facet_band_rfft.argtypes = list(lib.swiftly_hip_prepare_facet_band.argtypes)
@@ -188,6 +191,9 @@ def _declare(lib):
     # float32 rows out of the backward finish (same arguments; `out` is real, its row stride counts reals, dtype = input type)
     lib.swiftly_hip_finish_facet_band_real.restype = c_int
     lib.swiftly_hip_finish_facet_band_real.argtypes = list(lib.swiftly_hip_finish_facet_band.argtypes)
+    # float64 rows out of the complex128 finish (same arguments; `out` is float64, its row stride counts reals, dtype = C128)
+    lib.swiftly_hip_finish_facet_band_real64.restype = c_int
+    lib.swiftly_hip_finish_facet_band_real64.argtypes = list(lib.swiftly_hip_finish_facet_band.argtypes)
     # ... and its half-length form (swiftly_rowc2r.h): the same arguments
     lib.swiftly_hip_finish_facet_band_c2r.restype = c_int
     lib.swiftly_hip_finish_facet_band_c2r.argtypes = list(lib.swiftly_hip_finish_facet_band.argtypes)

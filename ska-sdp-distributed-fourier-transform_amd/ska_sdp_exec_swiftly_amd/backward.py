@@ -226,7 +226,8 @@ class SwiftlyBackward:
         ``torch.float32`` (complex64 data) / ``torch.float64`` (complex128 data): the facets are images and
         :py:meth:`finish` returns their real parts, ``[size, size]`` in that dtype -- bit for bit the ``.real`` of the complex
         result.  On the band schedule in complex64, where ``core.supports_real_facets_out()`` holds, the finishing row
-        kernels store float32 themselves and no complex facet is ever allocated (:py:attr:`real_finish_native`);
+        kernels store float32 themselves and no complex facet is ever allocated (:py:attr:`real_finish_native`); likewise
+        float64 from complex128 accumulators where ``core.supports_real_facets_out_f64()`` holds;
         everywhere else each facet is finished complex, its real part copied out and the complex one released before
         the next facet is finished.  A dtype that does not match the data's precision raises ``ValueError`` -- at
         construction when ``dtype`` is given, else at the first data.
@@ -314,17 +315,21 @@ class SwiftlyBackward:
         core = self.core
         reals = not self._auto_axis and self.wave_axis == 1 and self._facet_dtype == _torch().float32
         half = reals and self._want_half_length
+        reals64 = not self._auto_axis and self.wave_axis == 1 and self._facet_dtype == _torch().float64
+        f64 = getattr(core, "supports_real_facets_out_f64", None)  # (a core without the method has no such form)
         return choose_b8(B8Facts(
             resolved=not self._auto_axis, wave_axis=self.wave_axis, facet_dtype=fdt.name_of(self._facet_dtype),
             half_length_asked=self._want_half_length, real_facets_out=reals and core.supports_real_facets_out(),
             real_facets_out_c2r=half and core.supports_real_facets_out_c2r(),
             pairs=half and all(fdt.loads_as_pairs(cfg.size, cfg.off1, core.yN_size) for cfg in self.facets_config_list),
-            accumulators_complex64=None if accumulators is None else accumulators.dtype == _torch().complex64))
+            accumulators_complex64=None if accumulators is None else accumulators.dtype == _torch().complex64,
+            real_facets_out_f64=bool(reals64 and f64 is not None and f64())))
 
     @property
     def real_finish_native(self):
         """By which path :py:meth:`finish` produces real facets: True = the finishing row kernels store float32 (band
-        schedule, complex64, ``core.supports_real_facets_out()``), False = complex finish and a copy of the real part per
+        schedule, complex64, ``core.supports_real_facets_out()``) or float64 (band schedule, complex128,
+        ``core.supports_real_facets_out_f64()``), False = complex finish and a copy of the real part per
         facet (also: the facets are complex).  ``None`` until the schedule is resolved."""
         return self._decide_b8().native
 
@@ -513,7 +518,9 @@ class SwiftlyBackward:
             return [torch.zeros((cfg.size, cfg.size), dtype=dt, device=core.device) for cfg in self.facets_config_list]
         form = self._decide_b8(bands)
         for j, cfg in enumerate(self.facets_config_list):
-            if form.native:  # float32 straight from the row kernels: no complex facet exists
+            if form.native and self._facet_dtype == torch.float64:  # float64 straight from the complex128 row kernels
+                out.append(core.finish_facet_band_float64(bands[j], self.bands.band, cfg.off1, cfg.size, mask=cfg.mask1))
+            elif form.native:  # float32 straight from the row kernels: no complex facet exists
                 out.append(core.finish_facet_band(bands[j], self.bands.band, cfg.off1, cfg.size, mask=cfg.mask1, real=True,
                                                   half_length=form.half_length))
             else:

@@ -618,6 +618,18 @@ class SwiftlyCoreHip:
         ``_lib.last_error()`` says why."""
         return self._supports(_lib.FEATURE_REAL_FACETS_OUT_C2R, _torch().complex64)
 
+    def supports_real_facets_f64(self):
+        """True when the complex128 forward K1 takes real-valued float64 facets as they are
+        (:py:meth:`prepare_facet_band_float64`; ``swiftly_hip_prepare_facet_band_real64``): the sizes of the complex128 band
+        pipeline (``supports_band_pipeline(torch.complex128, explicit=True)``).  After a False ``_lib.last_error()`` says why."""
+        return self._supports(_lib.FEATURE_REAL_FACETS_F64, _torch().complex128)
+
+    def supports_real_facets_out_f64(self):
+        """True when the complex128 backward finish stores real-valued float64 facets as they are
+        (:py:meth:`finish_facet_band_float64`; ``swiftly_hip_finish_facet_band_real64``): the sizes of the complex128 backward
+        band (``supports_backward_band(torch.complex128, explicit=True)``).  After a False ``_lib.last_error()`` says why."""
+        return self._supports(_lib.FEATURE_REAL_FACETS_OUT_F64, _torch().complex128)
+
     def band_for_offsets(self, subgrid_offs):
         """Smallest cyclic range ``(start, length)`` of centred indices of the padded facet axis that contains
         the ``xM_yN_size`` window of every given subgrid offset (core.py:243-253); ``(0, yN_size)`` = all."""
@@ -666,6 +678,27 @@ class SwiftlyCoreHip:
         form = "half_length_band" if half_length else "real_band" if real else "band"
         return self._k1_call(form, facet, out, out.stride(0), facet_off, band, fold_other_axis_window, rows_of)
 
+    def prepare_facet_band_float64(self, facet, facet_off, band, out=None, fold_other_axis_window=True):
+        """K1 in complex128 for a real-valued facet held as float64 (:py:meth:`supports_real_facets_f64`;
+        ``swiftly_hip_prepare_facet_band_real64``): the row kernels load 8 bytes per pixel and the complex128 ``out`` holds,
+        bit for bit, what :py:meth:`prepare_facet_band` gives for ``facet.to(torch.complex128)``.  ``facet``: a float64
+        row-major 2-D device tensor (any row pitch); ``band`` must be ``(0, yN_size)`` as for every complex128 K1.
+        ``ValueError`` for other dtypes or strides, ``NotImplementedError`` with the library's reason where the feature says
+        no.  (``prepare_facet_band`` itself keeps refusing float64 tensors: this is a door of its own.)"""
+        torch = _torch()
+        if facet.dtype != torch.float64:
+            raise ValueError(f"prepare_facet_band_float64 takes float64 facets, not {facet.dtype}")
+        if facet.dim() != 2 or facet.stride(1) != 1:
+            raise ValueError("prepare_facet_band_float64 needs a row-major 2-D device tensor")
+        ncols = self.band_columns(band)
+        if out is None:
+            out = torch.empty((facet.shape[0], ncols), dtype=torch.complex128, device=self._device)
+        elif out.dtype != torch.complex128:
+            raise ValueError(f"Output array is {out.dtype}, a float64 facet needs {torch.complex128}!")
+        elif out.dim() != 2 or tuple(out.shape) != (facet.shape[0], ncols) or out.stride(1) != 1:
+            raise ValueError(f"Output array has shape {tuple(out.shape)}, expected {(facet.shape[0], ncols)}!")
+        return self._k1_call("real_band_f64", facet, out, out.stride(0), facet_off, band, fold_other_axis_window, None)
+
     #: the C entry point (``swiftly_hip_`` + name) of every K1 form, by (form, a row block was given); the window-rows
     #: forms always take one
     _K1_ENTRY = {
@@ -673,6 +706,7 @@ class SwiftlyCoreHip:
         ("real_band", False): "prepare_facet_band_real", ("real_band", True): "prepare_facet_band_rows_real",
         ("half_length_band", False): "prepare_facet_band_rfft", ("half_length_band", True): "prepare_facet_band_rows_rfft",
         ("window_rows", True): "prepare_facet_window_rows", ("real_window_rows", True): "prepare_facet_window_rows_real",
+        ("real_band_f64", False): "prepare_facet_band_real64",
     }
 
     #: the C entry point of the backward contiguous-axis finish (B8), by (real facets, half-length form)
@@ -680,7 +714,8 @@ class SwiftlyCoreHip:
                  (True, True): "finish_facet_band_c2r"}
 
     def _k1_call(self, form, facet, out, out_row_stride, facet_off, band, fold_other_axis_window, rows_of, windows=()):
-        """the one native K1 call: ``facet`` (float32 in the real forms, whose dtype code is that of the output) into ``out``;
+        """the one native K1 call: ``facet`` (float32, or float64 for ``real_band_f64``, in the real forms, whose dtype code is
+        that of the output) into ``out``;
         ``rows_of``: ``(size, row0)`` of the row block or None; ``windows``: the trailing arguments of the window-rows forms"""
         entry = getattr(self._lib, "swiftly_hip_" + self._K1_ENTRY[form, rows_of is not None])
         fold = (int(bool(fold_other_axis_window)),) if rows_of is None else (
@@ -1151,6 +1186,36 @@ class SwiftlyCoreHip:
             entry(
                 self._handle, self._code(band_acc), cvp(band_acc.data_ptr()), rows, band_acc.stride(0), int(band[0]),
                 int(band[1]), cvp(out.data_ptr()), out.stride(0), int(facet_off), int(facet_size),
+                cvp(mvec.data_ptr()) if mvec is not None else None, self._stream(),
+            )
+        )
+        return out
+
+    def finish_facet_band_float64(self, band_acc, band, facet_off, facet_size, mask=None, out=None):
+        """:py:meth:`finish_facet_band` of complex128 band accumulators for a facet that is an image
+        (:py:meth:`supports_real_facets_out_f64`; ``swiftly_hip_finish_facet_band_real64``): the result is the float64 tensor
+        ``[rows, facet_size]`` of the real parts, bit for bit those of the complex128 result, stored by the row kernels
+        themselves -- no complex128 facet exists at any time.  ``out``: float64 rows of any pitch ``>= facet_size`` with unit
+        column stride.  ``ValueError`` for other dtypes or strides, ``NotImplementedError`` with the library's reason where
+        the feature says no.  (``finish_facet_band(complex128, real=True)`` keeps refusing: this is a door of its own.)"""
+        torch = _torch()
+        if band_acc.dtype != torch.complex128:
+            raise ValueError(f"finish_facet_band_float64 needs complex128 accumulators, got {band_acc.dtype}")
+        if band_acc.dim() != 2 or band_acc.stride(1) != 1:
+            raise ValueError("finish_facet_band_float64 needs row-major 2-D band accumulators")
+        rows = band_acc.shape[0]
+        if out is None:
+            out = torch.empty((rows, int(facet_size)), dtype=torch.float64, device=self._device)
+        elif out.dtype != torch.float64:
+            raise ValueError(f"finish_facet_band_float64 writes {torch.float64}, got an `out` of {out.dtype}")
+        elif out.dim() != 2 or tuple(out.shape) != (rows, int(facet_size)) or out.stride(1) != 1:
+            raise ValueError(f"finish_facet_band_float64: `out` must be [{rows}, {int(facet_size)}] with unit column stride")
+        mvec = self._real_vec(mask, band_acc.dtype, int(facet_size)) if mask is not None else None
+        cvp = ctypes.c_void_p
+        _lib.check(
+            self._lib.swiftly_hip_finish_facet_band_real64(
+                self._handle, _lib.C128, cvp(band_acc.data_ptr()), rows, band_acc.stride(0), int(band[0]), int(band[1]),
+                cvp(out.data_ptr()), out.stride(0), int(facet_off), int(facet_size),
                 cvp(mvec.data_ptr()) if mvec is not None else None, self._stream(),
             )
         )

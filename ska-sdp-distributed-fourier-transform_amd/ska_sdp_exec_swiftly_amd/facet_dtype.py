@@ -10,11 +10,15 @@ from .tasks import _torch
 
 #: the ``facet_dtype`` the forward classes take (their facets are inputs) and the backward ones (outputs)
 FORWARD, BACKWARD = ("float32",), ("float32", "float64", "complex64", "complex128")
+#: ... and ``SwiftlyForward`` alone: float64 facets stay float64 through a complex128 band pipeline (the multi-GPU classes
+#: have no such form and keep ``FORWARD``)
+FORWARD_SINGLE = FORWARD + ("float64",)
 
 
-def parse_facet_dtype(facet_dtype, accepted):
+def parse_facet_dtype(facet_dtype, accepted, named=None, note=""):
     """``facet_dtype`` as given to a constructor -> ``None`` or the torch dtype: a torch dtype or anything ``numpy.dtype``
-    reads as one of the names in ``accepted``; ``ValueError`` otherwise"""
+    reads as one of the names in ``accepted``; ``ValueError`` otherwise -- its sentence lists ``named`` (default: ``accepted``)
+    and ends with ``note``"""
     if facet_dtype is None:
         return None
     torch = _torch()
@@ -24,7 +28,7 @@ def parse_facet_dtype(facet_dtype, accepted):
         except TypeError:
             facet_dtype = None
     if facet_dtype not in [getattr(torch, name) for name in accepted]:
-        raise ValueError(f"facet_dtype must be {', '.join(accepted)} or None")
+        raise ValueError(f"facet_dtype must be {', '.join(named or accepted)} or None{note}")
     return facet_dtype
 
 
@@ -33,6 +37,27 @@ def forward_keywords(facet_dtype, half_length_k1):
     parsed = parse_facet_dtype(facet_dtype, FORWARD)
     if half_length_k1 and parsed is None:
         raise ValueError("half_length_k1=True needs facet_dtype=float32")
+    return parsed
+
+
+#: what the refusals of ``SwiftlyForward`` add to the sentence every forward class says
+_FLOAT64_NOTE = ("; SwiftlyForward also takes float64, for float64 facets kept real through the complex128 band pipeline "
+                 "(wave_axis=1)")
+
+
+def single_forward_keywords(facet_dtype, half_length_k1, facet_data):
+    """the keywords of ``SwiftlyForward``, before anything touches a configuration or a device: those of the forward classes,
+    and ``float64`` -- which is a statement about the data, so it is held against the data here: every facet must be one
+    ``is_float64_facet`` accepts (then the pass is complex128), and the half-length K1 is a float32 form"""
+    parsed = parse_facet_dtype(facet_dtype, FORWARD_SINGLE, named=FORWARD, note=_FLOAT64_NOTE)
+    if parsed != _torch().float64:
+        return forward_keywords(parsed, half_length_k1)
+    if half_length_k1:
+        raise ValueError("half_length_k1=True needs facet_dtype=float32")
+    facet_data = list(facet_data)
+    if not facet_data or not all(is_float64_facet(data) for data in facet_data):
+        raise ValueError(f"facet_dtype must be {', '.join(FORWARD)} or None{_FLOAT64_NOTE}: facet_dtype=float64 needs every "
+                         "facet as a row-major float64 array (and at least one)")
     return parsed
 
 
@@ -72,6 +97,17 @@ def is_float32_facet(data):
     if isinstance(data, torch.Tensor):
         return data.dtype == torch.float32 and data.dim() == 2 and data.stride(-1) == 1
     return numpy.asarray(data).dtype == numpy.float32
+
+
+def is_float64_facet(data):
+    """is ``data`` a facet that can stay float64: a float64 host array, or a float64 tensor K1 could read in place (2-D, unit
+    stride along its rows)?"""
+    torch = _torch()
+    if data is None:
+        return False
+    if isinstance(data, torch.Tensor):
+        return data.dtype == torch.float64 and data.dim() == 2 and data.stride(-1) == 1
+    return numpy.asarray(data).dtype == numpy.float64
 
 
 def loads_as_pairs(size, off1, yN_size):

@@ -9,7 +9,7 @@ from functools import cached_property
 
 from . import _lib, slabs
 from .core_hip import band_range
-from .facet_dtype import forward_keywords, loads_as_pairs
+from .facet_dtype import loads_as_pairs, single_forward_keywords
 from .ingest import _FacetIngest, _mask_table
 from .k1_form import K1Facts, axis1_active, choose_k1, may_fuse
 from .prefetch import WavePrefetch, _knobs
@@ -60,6 +60,13 @@ class SwiftlyForward(WavePrefetch):
         are not 8-byte aligned at an even pitch under the accurate order, the multi-GPU classes without their own
         ``facet_dtype`` keyword) the facets are promoted as
         before and :py:attr:`facet_dtype` says complex64.  The results are those of the promoted facets bit for bit.
+        ``torch.float64`` / ``"float64"``: "my facets are real-valued float64 images, keep them float64 through the
+        complex128 band pipeline" (``wave_axis=1``; ``core.supports_band_pipeline(torch.complex128, n, explicit=True)`` and
+        ``core.supports_real_facets_f64()``): every facet must be a float64 host array or a row-major 2-D float64 tensor
+        (``ValueError`` otherwise); they stay float64 on the host, on the wire and in HBM -- 8 bytes per pixel where the
+        promoted facet holds 16 -- and K1 is ``core.prepare_facet_band_float64``.  The subgrids are those of the promoted
+        facets bit for bit.  Where no float64 K1 exists (``wave_axis=0``, other sizes) the facets are promoted as before and
+        :py:attr:`facet_dtype` says complex128; without the keyword float64 facets are always promoted.
         Any other value: ``ValueError``
     :param half_length_k1: ``True`` (with ``facet_dtype=float32``, ``ValueError`` without): K1 of the real facets as ONE
         half-length transform per row (``core.prepare_facet_band(..., half_length=True)``) where that form exists
@@ -75,7 +82,8 @@ class SwiftlyForward(WavePrefetch):
         self, swiftly_config, facet_tasks, lru_forward=1, queue_size=20, client=None, subgrid_configs=None,
         wave_axis=None, delayed=False, facet_dtype=None, half_length_k1=False,
     ):
-        self._facet_dtype_asked = forward_keywords(facet_dtype, half_length_k1)
+        facet_tasks = list(facet_tasks)
+        self._facet_dtype_asked = single_forward_keywords(facet_dtype, half_length_k1, (_unwrap(t[1]) for t in facet_tasks))
         self._half_length_asked, self._k1 = bool(half_length_k1), None  # (the K1 form: _decide_k1)
         WavePrefetch.__init__(self)
         self.delayed = bool(delayed)  # hand out DeviceTask handles instead of bare device tensors
@@ -107,14 +115,16 @@ class SwiftlyForward(WavePrefetch):
         # uploaded on a dedicated copy stream through a small ring of pinned staging buffers, and the compute
         # stream waits per facet only when a kernel first needs it -- the PCIe transfer of facet j+1 overlaps
         # the full-facet transform of facet j
-        self._ingest = _FacetIngest(self.core)
+        self._ingest = _FacetIngest(self.core, float64=self._facet_dtype_asked == torch.float64)
         self._facet_info = [self._ingest.add(data) for _, data in facet_tasks]
         dtypes = {info[0] for info in self._facet_info}
         if len(dtypes) > 1:
             raise ValueError("all facets must have the same dtype")
         self.dtype = dtypes.pop() if dtypes else torch.complex64
-        if self._facet_dtype_asked is not None and not self._ingest.all_float32:
+        if self._facet_dtype_asked == torch.float32 and not self._ingest.all_float32:
             raise ValueError("facet_dtype=float32 needs every facet as a row-major float32 array")
+        if self._facet_dtype_asked == torch.float64 and (self.dtype != torch.complex128 or not self._ingest.all_float64):
+            raise ValueError(f"facet_dtype=float64 needs float64 facets in a complex128 pass, got a {self.dtype} pass")
         if wave_axis is None:
             # default: the reference's schedule (waves keyed by off0) -- unless the caller hands over the plan of
             # subgrids it is going to request AND the contiguous-axis-first kernels exist for this configuration:
@@ -139,16 +149,19 @@ class SwiftlyForward(WavePrefetch):
         self._results = {}
         self._result_bytes = 0
         self._result_budget = int(float(os.environ.get("SWIFTLY_RESULT_CACHE_GB", "16")) * 2**30)
-        # float32 facets: kept as they are when this object's K1 loads reals, promoted to complex64 otherwise -- decided
-        # before the first upload, for the band its own K1 will get
+        # float32 facets: kept as they are when this object's K1 loads reals, promoted to complex64 otherwise (float64 facets
+        # of a caller who asked: float64 or complex128) -- decided before the first upload, for the band its own K1 will get
         self._ingest.settle(self._decide_k1(own=True).facets_real)
         self._ingest.prefetch(0)
 
     @property
     def facet_dtype(self):
-        """dtype of the facets as they are resident: ``torch.float32`` when real-valued facets were kept real, else
-        :py:attr:`dtype` (the complex dtype everything downstream of K1 computes in)"""
-        return _torch().float32 if self._ingest.real else self.dtype
+        """dtype of the facets as they are resident: ``torch.float32`` (in a complex128 pass ``torch.float64``) when
+        real-valued facets were kept real, else :py:attr:`dtype` (the complex dtype everything downstream of K1 computes in)"""
+        torch = _torch()
+        if not self._ingest.real:
+            return self.dtype
+        return torch.float64 if self.dtype == torch.complex128 else torch.float32
 
     @property
     def half_length_k1(self):
@@ -168,10 +181,12 @@ class SwiftlyForward(WavePrefetch):
         the axis-1-first mode."""
         # (``reals``: only then does what is asked of the library and of the tensors matter)
         core, ingest, reals = self.core, self._ingest, self._ingest.all_float32 and self.wave_axis == 1
+        torch = _torch()
+        reals64 = getattr(ingest, "all_float64", False) and self.wave_axis == 1
         sizes, off1s = [info[1][-1] for info in self._facet_info], [int(cfg.off1) for cfg in self.facet_configs]
         facts = K1Facts(
-            wave_axis=self.wave_axis, complex64=self.dtype == _torch().complex64, all_float32=ingest.all_float32,
-            float32_asked=self._facet_dtype_asked is not None, half_length_asked=self._half_length_asked,
+            wave_axis=self.wave_axis, complex64=self.dtype == torch.complex64, all_float32=ingest.all_float32,
+            float32_asked=self._facet_dtype_asked == torch.float32, half_length_asked=self._half_length_asked,
             keeps_real=self._keep_real_facets, axis1_first=getattr(core, "axis1_first", False), axis1_fused=self.axis1_fused,
             planned=self._plan is not None, real_facets=reals and core.supports_real_facets(),
             real_facets_rfft=reals and core.supports_real_facets_rfft(),
@@ -179,7 +194,9 @@ class SwiftlyForward(WavePrefetch):
             even=all(loads_as_pairs(n, off1, core.yN_size) for n, off1 in zip(sizes, off1s)),
             # (device facets are read in place: two adjacent reals must be one aligned 8-byte load; uploads are contiguous)
             aligned=reals and all(t is None or t.device != core.device or (t.stride(0) % 2 == 0 and t.data_ptr() % 8 == 0)
-                                  for t in ingest.tensors), settled=self._k1)
+                                  for t in ingest.tensors), settled=self._k1,
+            all_float64=getattr(ingest, "all_float64", False), float64_asked=self._facet_dtype_asked == torch.float64,
+            real_facets_f64=bool(reals64 and core.supports_real_facets_f64()))
         # (only then are the window rows asked about: they need the plan's waves and a facet -- a rank may own none)
         if (own or band is not None) and sizes and may_fuse(facts):
             band = self._own_band() if own else band
@@ -516,6 +533,8 @@ class SwiftlyForward(WavePrefetch):
                 t0 = timer.start() if timer is not None else None
                 if mode == 2:
                     core.prepare_facet_window_rows(data, cfg.off1, self._band, starts, bands[j])
+                elif data.dtype == torch.float64:  # (float64 facets kept real: the float64-load K1 of complex128)
+                    core.prepare_facet_band_float64(data, cfg.off1, self._band, out=bands[j])
                 else:
                     core.prepare_facet_band(data, cfg.off1, self._band, out=bands[j], half_length=self._k1.half_length)
                 if timer is not None:

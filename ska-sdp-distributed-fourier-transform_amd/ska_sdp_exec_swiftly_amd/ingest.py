@@ -4,7 +4,7 @@ uploads host facets one ahead of the kernels that use them (SURVEY section 8f ro
 """
 import numpy
 
-from .facet_dtype import is_float32_facet
+from .facet_dtype import is_float32_facet, is_float64_facet
 from .tasks import _torch
 
 _MASK_CACHE = {}
@@ -61,16 +61,20 @@ class _FacetIngest:
     Real-valued facets: a float32 facet (host array or device tensor) is registered as it is and reported with the complex
     dtype it computes in; ``settle(keep_real)`` -- called by the owner once all facets are registered, before the first upload
     -- either keeps all of them float32 (the owner's K1 loads reals: half the resident bytes and half the upload) or promotes
-    them to complex64 the way every other real input is."""
+    them to complex64 the way every other real input is.  ``float64=True`` (an owner whose caller asked for float64 facets):
+    the same for float64 facets, which compute in complex128 -- kept float64 or promoted to complex128; without it a float64
+    facet is promoted when it is registered, as ever."""
 
     SLAB = 128 << 20
 
-    def __init__(self, core):
+    def __init__(self, core, float64=False):
         self.core = core
         self.host, self.tensors, self.events = [], [], []
         self._float32 = []    # per facet: registered as float32 (promotion pending until settle)
+        self._float64 = []    # per facet: registered as float64 (only an owner that asked: promotion pending until settle)
+        self._keep_float64 = bool(float64)
         self._settled = False
-        self.real = False     # the facets stay float32 (settle(True))
+        self.real = False     # the facets stay float32 / float64 (settle(True))
         self._stream = None
         self._staging = None
         self._staging_free = None
@@ -81,27 +85,30 @@ class _FacetIngest:
         if self._settled:
             raise RuntimeError("facets must be registered before settle()")
         is_float32 = is_float32_facet(data)
+        is_float64 = self._keep_float64 and is_float64_facet(data)
+        is_real = is_float32 or is_float64
         if isinstance(data, torch.Tensor):
             # (a float32 tensor K1 could not read in place -- not 2-D row-major -- is promoted at once, as it always was)
-            ten = data if is_float32 else self.core._as_device(data)[0]  # pylint: disable=protected-access
+            ten = data if is_real else self.core._as_device(data)[0]  # pylint: disable=protected-access
             self.host.append(None)
             self.tensors.append(ten)
         else:
             arr = numpy.asarray(data)
-            if is_float32:
+            if is_real:
                 pass
             elif not numpy.iscomplexobj(arr):
                 arr = arr.astype(numpy.complex128)
             elif arr.dtype not in (numpy.complex64, numpy.complex128):
                 arr = arr.astype(numpy.complex128)
-            self.host.append(arr if is_float32 else numpy.ascontiguousarray(arr))
+            self.host.append(arr if is_real else numpy.ascontiguousarray(arr))
             self.tensors.append(None)
         self.events.append(None)
         self._float32.append(is_float32)
+        self._float64.append(is_float64)
         j = len(self.tensors) - 1
         src = self.tensors[j] if self.tensors[j] is not None else self.host[j]
-        if is_float32:
-            tdt = torch.complex64  # the dtype it computes in, kept real or not
+        if is_real:
+            tdt = torch.complex64 if is_float32 else torch.complex128  # the dtype it computes in, kept real or not
         else:
             tdt = src.dtype if self.tensors[j] is not None else (
                 torch.complex64 if src.dtype == numpy.complex64 else torch.complex128
@@ -114,16 +121,22 @@ class _FacetIngest:
         """every registered facet is float32 (and there is one)"""
         return bool(self._float32) and all(self._float32)
 
+    @property
+    def all_float64(self):
+        """every registered facet is float64, registered by an owner that asked (and there is one)"""
+        return bool(self._float64) and all(self._float64)
+
     def settle(self, keep_real):
         """Decide what the float32 facets become: with ``keep_real`` (all of them must be float32) they stay float32 -- a
         device tensor in place, a host array staged and uploaded as float32; otherwise each is promoted to complex64 exactly as
-        a real input always was.  Idempotent; the first upload settles with ``False`` when the owner never asked."""
+        a real input always was.  Float64 facets of an owner that asked: the same, float64 or complex128.  Idempotent; the
+        first upload settles with ``False`` when the owner never asked."""
         if self._settled:
             return
         self._settled = True
-        self.real = bool(keep_real) and self.all_float32
-        for j, is_float32 in enumerate(self._float32):
-            if not is_float32:
+        self.real = bool(keep_real) and (self.all_float32 or self.all_float64)
+        for j, (is_float32, is_float64) in enumerate(zip(self._float32, self._float64)):
+            if not (is_float32 or is_float64):
                 continue
             if self.tensors[j] is not None:
                 ten = self.tensors[j]
@@ -132,7 +145,7 @@ class _FacetIngest:
                 else:
                     self.tensors[j] = self.core._as_device(ten)[0]  # pylint: disable=protected-access
             else:
-                arr = self.host[j] if self.real else self.host[j].astype(numpy.complex64)
+                arr = self.host[j] if self.real else self.host[j].astype(numpy.complex64 if is_float32 else numpy.complex128)
                 self.host[j] = numpy.ascontiguousarray(arr)
 
     def prefetch(self, j):
@@ -143,9 +156,8 @@ class _FacetIngest:
             return
         core = self.core
         arr = self.host[j]
-        tdt = {numpy.dtype(numpy.float32): torch.float32, numpy.dtype(numpy.complex64): torch.complex64}.get(
-            arr.dtype, torch.complex128
-        )
+        tdt = {numpy.dtype(numpy.float32): torch.float32, numpy.dtype(numpy.float64): torch.float64,
+               numpy.dtype(numpy.complex64): torch.complex64}.get(arr.dtype, torch.complex128)
         dev = torch.empty(arr.shape, dtype=tdt, device=core.device)
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=core.device)
