@@ -75,8 +75,7 @@ static int launch_mode(const ColPassArgs& a, const ColZ& cz, int outer, int nbat
     return launch_lds<col_pass_kernel<G, (MODE == 2 ? 0 : MODE), false>, G::LDS_BYTES>(
         grid, dim3(G::NT), s, a, a.in, a.out, a.ld_win, a.ld_win2, a.st_win, a.st_win2, a.st_rowmap, a.tw, a.tw_full, cz);
 }
-// float64 arithmetic (ColPassArgs::f64): lengths 32 .. 512
-constexpr int kColF64MinLog = 5;
+// float64 arithmetic (ColPassArgs::f64): lengths 32 .. 512 (kColF64MinLog .. kColPassMaxLogF64, swiftly_rowroute.h)
 template <int LOGN, int MODE>
 static int launch_mode_f64(const ColPassArgs& a, const ColZ& cz, int outer, int nbatch, hipStream_t s) {
     if constexpr (LOGN < kColF64MinLog || LOGN > kColPassMaxLogF64) {
@@ -178,6 +177,6 @@ int launch_col_pass(int logn, int mode, const ColPassArgs& a, const ColZ& cz, in
                     const ColPassSrc2* src2) {
     return CDispatch<kColPassMinLog, kColPassMaxLog>::launch(logn, mode, a, cz, outer, nbatch, s, src2);
 }
-bool col_pass_f64_supported(int logn) { return logn >= kColF64MinLog && logn <= kColPassMaxLogF64; }
+bool col_pass_f64_supported(int logn) { return col_f64_instance(logn); }
 
 }  // namespace swf

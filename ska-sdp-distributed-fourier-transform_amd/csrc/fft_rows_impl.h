@@ -19,23 +19,15 @@ static int launch_one(const RowsArgs<R>& a, const OffTab& tab, hipStream_t s) {
         grid = (unsigned)(((rowblocks + 7) / 8) * 8 * a.outer);
     }
     if (a.real_in) {
-        // real input: complex64 prepare_facet of the plain band layout (swiftly_caps.h, why_not_real_facets), 64 .. 4096 points
-        // (8192: the lean row kernel, row_pass.hip)
-        // complex128 prepare_facet (why_not_real_facets_f64): float64 rows, 64 .. 8192 points in one workgroup (16384 / 32768:
-        // pass A of swiftly_rowslong.h)
-        if constexpr ((sizeof(R) == 4 && LOGN >= kBandMinLog && LOGN < 13) ||
-                      (sizeof(R) == 8 && LOGN >= kBandMinLog && LOGN <= kMaxLogNDouble))
+        // real input: the lengths of generic_has_real_load (swiftly_rowroute.h; choose_row_route refuses the others)
+        if constexpr (generic_has_real_load(sizeof(R) == 8, LOGN))
             return launch_lds<fft_rows_kernel<G, R, true>, G::LDS_BYTES>(dim3(grid, a.nbatch > 0 ? a.nbatch : 1), dim3(G::NT), s, a, tab);
         else
             return -1;
     }
     if (a.real_out) {
-        // real output: complex64 finish_facet of the plain band layout (swiftly_caps.h, why_not_real_facets_out), 64 .. 4096
-        // points (8192 and longer: the lean row kernels, row_pass.hip); the mapped store only
-        // complex128 finish_facet (why_not_real_facets_out_f64): float64 rows, 64 .. 8192 points, and pass B of the long rows
-        // (128 / 256 points behind n1 = 128, swiftly_rowslong.h)
-        if constexpr ((sizeof(R) == 4 && LOGN >= kBackwardBandMinLogYN && LOGN < 13) ||
-                      (sizeof(R) == 8 && LOGN >= kBackwardBandMinLogYN && LOGN <= kMaxLogNDouble)) {
+        // real output: the lengths of generic_has_real_store (swiftly_rowroute.h); the mapped store only
+        if constexpr (generic_has_real_store(sizeof(R) == 8, LOGN)) {
             if (a.raw_st || a.st_rowmap || a.accumulate) return -1;
             return launch_lds<fft_rows_kernel<G, R, false, true>, G::LDS_BYTES>(dim3(grid, a.nbatch > 0 ? a.nbatch : 1), dim3(G::NT), s, a, tab);
         } else {

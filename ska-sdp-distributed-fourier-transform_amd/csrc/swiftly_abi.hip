@@ -397,16 +397,9 @@ static int launch_checked(int logn, const RowsArgs<R>& a, const OffTab& tab, hip
     return launch_status(launch_fft_rows(logn, a, tab, st));
 }
 
-// Lean path for complex64 transforms along the strided axis of row-major
-// arrays (columns contiguous): swiftly_colpass.h.  Returns false when the call
-// does not fit its constraints (the generic kernel handles it then).
-static bool try_col_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, const OffTab& tab, hipStream_t st,
-                         int* rc_out) {
-    if (!a.rowfast || a.in_rs != 1 || a.out_rs != 1 || (tab.use & 8) || a.rm_mod > 0 || a.in_rowmap) return false;
-    const uint64_t n = uint64_t(1) << logn, lim = uint64_t(1) << 32;
-    const uint64_t W = (uint64_t)a.nrows;
-    // all element offsets inside one batch item are 32 bit
-    if (n * (uint64_t)a.in_cs + W >= lim || n * (uint64_t)a.out_cs + W >= lim || n * W >= lim) return false;
+// Route ColPass (complex64 transforms along the strided axis of row-major arrays, columns contiguous: swiftly_colpass.h):
+// the argument block of the call and, in `cz`, its per-item tables.
+static ColPassArgs col_pass_of(int logn, const RowsArgs<float>& a, const OffTab& tab, ColZ& cz) {
     const int nb = a.nbatch > 0 ? a.nbatch : 1;
     ColPassArgs c = col_pass_args(Map{a.ld.a, a.ld.len, a.ld.c, a.ld.mod}, Map{a.st.a, a.st.len, a.st.c, a.st.mod});
     c.ncols = a.nrows;
@@ -422,7 +415,7 @@ static bool try_col_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
     c.scale = a.scale;
     c.conj_ld = a.conj_ld; c.conj_st = a.conj_st; c.accumulate = a.accumulate;
     // per-item map offsets (OffTab) -> per-subgrid tables of the column pass (batch item z = b)
-    ColZ cz = plain_colz();
+    cz = plain_colz();
     if (tab.use) {
         static_assert(kMaxBatch <= kColZB, "per-item tables");
         cz.nb = nb;
@@ -438,10 +431,7 @@ static bool try_col_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
             for (int b = 0; b < nb; b++) cz.b_sta[b] = tab.st_a[b];
         }
     }
-    const int rc = col_transform(h, logn, c, cz, (int)W, nb, st);
-    if (rc == -1) return false;
-    *rc_out = rc;
-    return true;
+    return c;
 }
 
 
@@ -467,17 +457,10 @@ static int single_store_window(RowPassArgs& r, hipStream_t st, void** tmp) {
     return 0;
 }
 
-// Lean path for long complex64 transforms along the contiguous axis (one
-// workgroup per row): swiftly_rowpass.h.  Returns false when the call does not
-// fit (generic kernel handles it).
-static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, const OffTab& tab, hipStream_t st,
-                         int* rc_out) {
-    if (a.rowfast || a.in_cs != 1 || a.out_cs != 1 || tab.use != 0 || (a.nbatch > 1)) return false;
-    if (logn < kRowPassMinLog || logn > kRowPassMaxLog + 1) return false;
-    if (a.ld.win2 || a.st_win_bs != 0) return false;
-    const int n = 1 << logn;
-    const bool ident_ld = a.ld.a == 0 && a.ld.len == n && a.ld.c == 0 && !a.ld.win;
-    const bool ident_st = a.st.a == 0 && a.st.len == n && a.st.c == 0 && !a.st.win && !a.st.win2;
+// Routes Lean, Split32k and the three band routes (long complex64 transforms along the contiguous axis, one or two
+// workgroups per row: swiftly_rowpass.h): the argument block of the call.  (These kernels take no st_rowmap, no second load
+// window and no per-item window: choose_row_route sends such calls elsewhere.)
+static RowPassArgs row_pass_of(const RowsArgs<float>& a) {
     RowPassArgs r;
     std::memset(&r, 0, sizeof r);
     r.in = a.in; r.out = a.out;
@@ -487,69 +470,25 @@ static bool try_row_pass(swiftly_hip* h, int logn, const RowsArgs<float>& a, con
     r.in_rowmap = a.in_rowmap;
     r.in_real = a.real_in;
     r.out_real = a.real_out;
-    if (a.st_rowmap) return false;
     r.row_win = a.row_win;
-    if (a.row_win && logn > kRowPassMaxLog) return false;  // the two-workgroup kernels take it through prepare_facet_band only
     r.ld_a = a.ld.a; r.ld_len = a.ld.len; r.ld_c = a.ld.c; r.ld_mod = a.ld.mod; r.ld_win = a.ld.win;
     r.st_a = a.st.a; r.st_len = a.st.len; r.st_c = a.st.c; r.st_mod = a.st.mod; r.st_win = a.st.win; r.st_win2 = a.st.win2;
-    r.tw = twiddles<float>(h, logn);
-    if (!r.tw) return false;
+    r.tw = a.tw;
     r.scale = a.scale; r.conj_ld = a.conj_ld; r.conj_st = a.conj_st; r.accumulate = a.accumulate;
-    const int mode = ident_st ? 0 : (ident_ld ? 1 : 2);
-    if (a.real_in) {  // real input: 8192-point rows of the plain band layout only (longer ones: prepare_facet_k1)
-        if (logn != kRowPassMinLog || mode != 0) return false;
-        *rc_out = launch_status(launch_row_pass(logn, mode, r, st));
-        return true;
+    return r;
+}
+// Routes Band32kPlain, Band32kMapped and Band64k: the two-workgroup band kernel at 32768 / 65536 points, for the load map
+// of a prepare_* primitive or -- mapped store, one window -- the store map of a finish_* primitive.
+static int launch_band_route(swiftly_hip* h, const RowRoute& route, int logn, RowPassArgs r, hipStream_t st) {
+    void* tmp = nullptr;
+    if (route.single_store_window) {
+        r.band_len = -1;  // selects the mapped-store variant
+        if (int rc = single_store_window(r, st, &tmp)) return rc;
     }
-    // N = 32768: the two-workgroup band kernel for the load map of a prepare_* primitive, else the r1 split kernel
-    const bool prep_ld = r.ld_c == 0 && r.ld_mod == r.ld_len;    // load map of a prepare_* primitive (or identity)
-    const bool fin_st = r.st_c == 0 && r.st_mod == r.st_len;     // store map of a finish_* primitive
-    if (logn == 15 && mode == 0 && !a.accumulate) {
-        const cx<float>* tw14 = twiddles<float>(h, 14);
-        const cx<float>* tw13 = twiddles<float>(h, 13);
-        if (tw14 && prep_ld) {
-            *rc_out = launch_status(launch_row_pass_band(r, tw14, r.tw, st));
-            return true;
-        }
-        if (tw14 && tw13) {
-            *rc_out = launch_status(launch_row_pass_split(r, tw14, tw13, r.tw, st));
-            return true;
-        }
-    }
-    if (logn == 15 && mode != 0 && fin_st && prep_ld && !r.ld_win) {  // finish_* along the contiguous axis
-        const cx<float>* tw14 = twiddles<float>(h, 14);
-        if (tw14) {
-            r.band_len = -1;  // selects the mapped-store variant
-            void* tmp = nullptr;
-            if (int rc = single_store_window(r, st, &tmp)) {
-                *rc_out = rc;
-                return true;
-            }
-            int e2 = launch_row_pass_band(r, tw14, r.tw, st, &h->win4);
-            if (tmp) (void)hipFreeAsync(tmp, st);
-            *rc_out = launch_status(e2);
-            return true;
-        }
-    }
-    if (logn == 16) {  // 65536-point rows: only the two-workgroup kernel exists (prepare_* loads / finish_* stores)
-        const cx<float>* tw15 = twiddles<float>(h, 15);
-        const bool ok0 = mode == 0 && prep_ld && !a.accumulate, ok1 = mode != 0 && fin_st && prep_ld && !r.ld_win;
-        if (!tw15 || !(ok0 || ok1)) return false;
-        void* tmp = nullptr;
-        if (ok1) {
-            r.band_len = -1;
-            if (int rc = single_store_window(r, st, &tmp)) {
-                *rc_out = rc;
-                return true;
-            }
-        }
-        int e2 = launch_row_pass_band_n(16, r, tw15, r.tw, st);
-        if (tmp) (void)hipFreeAsync(tmp, st);
-        *rc_out = launch_status(e2);
-        return true;
-    }
-    *rc_out = launch_status(launch_row_pass(logn, mode, r, st));
-    return true;
+    const int e = launch_row_pass_band_n(logn, r, twiddles<float>(h, logn - 1), r.tw, st,
+                                         route.kind == kRouteBand32kMapped ? &h->win4 : nullptr);
+    if (tmp) (void)hipFreeAsync(tmp, st);
+    return launch_status(e);
 }
 
 
@@ -632,66 +571,11 @@ static int run_rows_long(swiftly_hip* h, int logn, RowsArgs<double>& a, const Of
     return rc;
 }
 
-// Launch the mapped row FFT for `a` (batch of a.nbatch <= kMaxBatch items with
-// per-item offsets in `tab`).  Transforms of length >= 2^kTwoPassMinLog along
-// a strided axis are decomposed (four-step) through a stream-ordered scratch.
-// Sub-transform form (swiftly_mixed.h): qmul = Q > 1 says that `a` is sub-transform j = qadd of a length-Q*2^logn
-// transform whose radix-Q pass has run: the input is the plain scratch of that pass (a.raw_ld set by the caller, element
-// e at in + e*in_cs), the store map refers to the full length a.full_n with plain output index Q*e + j.
+// The four-step of a transform of length >= 2^kTwoPassMinLog along a strided axis (route FourStep), through a
+// stream-ordered scratch.  Sub-transform form: see run_rows_chunk.
 template <typename R>
-static int run_rows_chunk(swiftly_hip* h, int logn, RowsArgs<R>& a, const OffTab& tab, hipStream_t st, int qmul = 1,
-                          int qadd = 0) {
-    a.tw = twiddles<R>(h, logn);
-    if (!a.tw) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle table for 2^%d", logn);
+static int run_rows_four_step(swiftly_hip* h, int logn, RowsArgs<R>& a, const OffTab& tab, hipStream_t st, int qmul, int qadd) {
     const bool sub = qmul > 1;
-    const bool all_j = sub && qadd < 0;  // all Q sub-transforms in this launch: outer index = j, input at in + j*in_os
-    a.full_logn = logn;
-    if (!sub) a.full_n = 0;
-    a.ld_mul = 1;
-    a.st_mul = qmul;
-    a.st_add0 = all_j ? 0 : qadd;
-    a.ld_addmul = 0;
-    a.st_addmul = all_j ? 1 : 0;
-    a.outer = all_j ? qmul : 1;
-    // the Q sub-transforms of a row write interleaved elements of the same lines: their workgroups are enumerated 8 block
-    // ids apart = on one XCD, whose L2 merges the partial lines (K1 of 24k[1]-n12k-1k 1.52 -> 0.88 ms per facet, r3)
-    a.outer_group = all_j ? 1 : 0;
-    if (!all_j) a.in_os = 0;
-    a.out_os = 0;
-    a.tw_full = nullptr;
-    a.tw_on_store = 0;
-    a.raw_st = 0;
-    if (!sub) a.raw_ld = 0;
-    if constexpr (std::is_same<R, float>::value) {
-        int rc = 0;
-        if (!sub && try_col_pass(h, logn, a, tab, st, &rc)) return rc;
-        if (!sub && try_row_pass(h, logn, a, tab, st, &rc)) return rc;
-        // real input: only the single-launch generic kernel is left (launch_fft_rows refuses lengths without a real instance)
-        if (a.real_in && (sub || a.rowfast || a.raw_ld))
-            return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: real input reaches a decomposed transform of 2^%d points", logn);
-        // ... and so for real output (every lean row kernel that takes it has launched above)
-        if (a.real_out && (sub || a.rowfast || a.raw_st || a.st_rowmap || a.accumulate || logn >= kRowPassMinLog))
-            return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: real output reaches a transform of 2^%d points without a real store", logn);
-    }
-    if (logn > kMaxLogNFloat && sizeof(R) == 4)
-        return fail(SWIFTLY_ERR_UNSUPPORTED, "transform length 65536 is only supported for complex64 prepare_* / finish_* "
-                    "calls with unit stride along the transform axis or along a strided axis of contiguous rows");
-    if constexpr (sizeof(R) == 8) {
-        // float64 rows: the single-workgroup instances of the generic kernel (launch_fft_rows refuses lengths without one) and
-        // the long-row pair below, which hands real_in to its pass A and real_out to its pass B
-        if (a.real_in && (sub || a.rowfast || a.raw_ld))
-            return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: float64 input reaches a decomposed transform of 2^%d points", logn);
-        if (a.real_out && (sub || a.rowfast || a.raw_st || a.st_rowmap || a.accumulate))
-            return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: float64 output reaches a transform of 2^%d points without a real store", logn);
-        if (!a.rowfast && logn > kMaxLogNDouble) {  // 16384 / 32768 complex128 points along the contiguous axis
-            if (sub || a.raw_ld)
-                return fail(SWIFTLY_ERR_UNSUPPORTED, "complex128 transform length %d along the contiguous axis: only the "
-                            "mapped-load form of the primitives is supported (no raw / sub-transform input)", 1 << logn);
-            return run_rows_long(h, logn, a, tab, st);
-        }
-    }
-    if (!(a.rowfast && logn >= kTwoPassMinLog)) return launch_checked(logn, a, tab, st);
-
     // ---- four-step: N = n1 * n2, input index y = y1*n2 + y2, output index k = k1 + n1*k2
     //   pass A (length n1 over y1, one per y2): scratch[k1*n2 + y2] = W_N^(y2 k1) * sum_y1 x[y1 n2 + y2] W_n1^(y1 k1)
     //   pass B (length n2 over y2, one per k1): X[k1 + n1 k2]       = sum_y2 scratch[k1*n2 + y2] W_n2^(y2 k2)
@@ -759,6 +643,10 @@ static int run_rows_chunk(swiftly_hip* h, int logn, RowsArgs<R>& a, const OffTab
     return rc;
 }
 
+template <typename R>
+static int run_rows_chunk(swiftly_hip* h, int64_t nlen, int logn, RowsArgs<R>& a, const OffTab& tab, hipStream_t st, int qmul = 1,
+                          int qadd = 0);
+
 // Transform length n that is NOT a power of two: Bluestein through two power-of-two transforms of length
 // L >= 2n - 1 on a stream-ordered work buffer (swiftly_bluestein.h).
 template <typename R>
@@ -777,11 +665,7 @@ static int run_rows_bluestein(swiftly_hip* h, int64_t n, RowsArgs<R>& a, const O
             spec = it->second.spec_d;
         }
     }
-    if (!chirp || !spec)
-        return fail(SWIFTLY_ERR_UNSUPPORTED,
-                    "transform length %lld (not a power of two) needs a convolution of length >= %lld, beyond the %s kernels",
-                    (long long)n, (long long)(2 * n - 1),
-                    sizeof(R) == 8 ? "complex128 (8192; Q * 2^k lengths up to Q * 8192)" : "complex64 (65536)");
+    if (!chirp || !spec) return fail(SWIFTLY_ERR_HIP, "internal: missing Bluestein tables");  // (the route has them)
     const int64_t L = int64_t(1) << logL;
     const int nb = a.nbatch > 0 ? a.nbatch : 1;
     const int64_t rows_total = (int64_t)nb * a.nrows;
@@ -818,7 +702,7 @@ static int run_rows_bluestein(swiftly_hip* h, int64_t n, RowsArgs<R>& a, const O
         f.scale = inverse ? (R)(1.0 / (double)L) : (R)1;
         f.conj_ld = f.conj_st = inverse ? 1 : 0;
         f.nbatch = 1;
-        return run_rows_chunk(h, logL, f, none, st);
+        return run_rows_chunk(h, L, logL, f, none, st);
     };
     if (!rc) rc = fft_L(w1, w2, false);
     if (!rc) {
@@ -879,31 +763,159 @@ static int run_rows_mixed(swiftly_hip* h, int64_t n, const swiftly_hip::Mixed& m
         B.in_rowmap = nullptr;
         B.full_n = (int)n;
         B.in_os = X.s_j;      // (used by the one-launch form only)
-        rc = run_rows_chunk(h, logM, B, tab, st, Q, one_launch ? -1 : j);
+        rc = run_rows_chunk(h, M, logM, B, tab, st, Q, one_launch ? -1 : j);
     }
     return lease.release(rc);
 }
 
-// The gates of run_rows, shared with swiftly_hip_supports_dtype: largest power-of-two length, and whether a length
-// (power of two: logn >= 0) has a route in precision R -- for other lengths the radix-Q tables (as run_rows picks them)
-// or the Bluestein tables of the handle, which exist only where their kernels do.
-template <typename R>
-static constexpr int max_log_rows() {
-    return sizeof(R) == 8 ? kMaxLogNDoubleRows : kMaxLogNFloat + 1;  // 2^16: lean complex64 kernels only
-}
+// The radix-Q tables of a length as run_rows picks them, and the Bluestein tables of the handle (which exist only where
+// their kernels do): facts of choose_row_route, and with row_length_supported the gate of swiftly_hip_supports_dtype.
 static bool use_mixed(const swiftly_hip* h, int64_t n, bool dbl) {
     const char* no_mixed = getenv("SWIFTLY_NO_MIXED");  // read per call: Bluestein for every such length (A/B, tests)
     auto it = h->mixed.find(n);
     const bool have = it != h->mixed.end() && (dbl ? it->second.tw_d != nullptr : it->second.tw_f != nullptr);
     return have && !(no_mixed && atoi(no_mixed));
 }
-template <typename R>
-static bool rows_length_supported(const swiftly_hip* h, int64_t n, int logn) {
-    constexpr bool dbl = sizeof(R) == 8;
-    if (logn >= 0) return logn >= kMinLogN && logn <= max_log_rows<R>();
-    if (use_mixed(h, n, dbl)) return true;
+static bool have_bluestein(const swiftly_hip* h, int64_t n, bool dbl) {
     auto it = h->blu.find(n);
     return it != h->blu.end() && (dbl ? it->second.chirp_d != nullptr : it->second.chirp_f != nullptr);
+}
+
+// What choose_row_route (swiftly_rowroute.h) reads of a call: `a` after run_rows_chunk has set its transform fields.
+template <typename R>
+static RowCall row_call_of(const swiftly_hip* h, int64_t nlen, int logn, const RowsArgs<R>& a, const OffTab& tab, int qmul, int qadd) {
+    constexpr bool dbl = sizeof(R) == 8;
+    RowCall c;
+    c.dbl = dbl; c.n = nlen; c.logn = logn;
+    c.sub = qmul > 1; c.all_j = c.sub && qadd < 0;
+    c.rowfast = a.rowfast != 0; c.in_rs1 = a.in_rs == 1; c.out_rs1 = a.out_rs == 1;
+    c.nrows = a.nrows; c.in_cs = a.in_cs; c.out_cs = a.out_cs;
+    c.tab_use = tab.use; c.nbatch = a.nbatch; c.rm = a.rm_mod > 0;
+    c.in_rowmap = a.in_rowmap != nullptr; c.st_rowmap = a.st_rowmap != nullptr; c.row_win = a.row_win != nullptr;
+    c.ld_win = a.ld.win != nullptr; c.ld_win2 = a.ld.win2 != nullptr;
+    c.st_win = a.st.win != nullptr; c.st_win2 = a.st.win2 != nullptr; c.st_win_bs = a.st_win_bs != 0;
+    c.ld_a = a.ld.a; c.ld_len = a.ld.len; c.ld_c = a.ld.c; c.ld_mod = a.ld.mod;
+    c.st_a = a.st.a; c.st_len = a.st.len; c.st_c = a.st.c; c.st_mod = a.st.mod;
+    c.accumulate = a.accumulate != 0; c.real_in = a.real_in != 0; c.real_out = a.real_out != 0;
+    c.raw_ld = a.raw_ld != 0; c.raw_st = a.raw_st != 0;
+    if (logn >= 0) {
+        c.tw = a.tw != nullptr;
+        if (!dbl) {
+            c.tw_m1 = twiddles<float>(h, logn - 1); c.tw_m2 = twiddles<float>(h, logn - 2);
+            c.tw_h1 = twiddles<float>(h, logn / 2); c.tw_h2 = twiddles<float>(h, logn - logn / 2);
+        }
+    } else {
+        c.mixed = use_mixed(h, nlen, dbl);
+        c.blu = have_bluestein(h, nlen, dbl);
+    }
+    return c;  // (c.col stays empty: the primitives ask nothing of the column passes)
+}
+
+// The one place where a refused route becomes a status and a text.
+static int refuse_route(int why, bool dbl, int64_t n, int logn) {
+    switch (why) {
+    case kRowLength:
+        return fail(SWIFTLY_ERR_UNSUPPORTED,
+                    "transform length %lld is not supported by the HIP backend (power of two in [8, %d], or a length "
+                    "whose Bluestein convolution or Q * 2^k sub-transform fits, for %s)",
+                    (long long)n, 1 << max_log_rows(dbl), dbl ? "complex128: Bluestein and Q * 2^k up to 8192" : "complex64");
+    case kRowStride:
+        return fail(SWIFTLY_ERR_PARAM, "transform length * column stride must be < 2^32");
+    case kRowNoConvolution:
+        return fail(SWIFTLY_ERR_UNSUPPORTED,
+                    "transform length %lld (not a power of two) needs a convolution of length >= %lld, beyond the %s kernels",
+                    (long long)n, (long long)(2 * n - 1), dbl ? "complex128 (8192; Q * 2^k lengths up to Q * 8192)" : "complex64 (65536)");
+    case kRowNoTable:
+        return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle table for 2^%d", logn);
+    case kRowRealInDecomposed:
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: %s input reaches a decomposed transform of 2^%d points", dbl ? "float64" : "real", logn);
+    case kRowRealOutNoStore:
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "internal: %s output reaches a transform of 2^%d points without a real store",
+                    dbl ? "float64" : "real", logn);
+    case kRow64kLeanOnly:
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "transform length 65536 is only supported for complex64 prepare_* / finish_* "
+                    "calls with unit stride along the transform axis or along a strided axis of contiguous rows");
+    case kRowLongMappedLoadOnly:
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "complex128 transform length %d along the contiguous axis: only the "
+                    "mapped-load form of the primitives is supported (no raw / sub-transform input)", 1 << logn);
+    case kRowNoGenericInstance:
+        return launch_status(-1);  // the status of a launcher without an instance
+    }
+    return fail(SWIFTLY_ERR_HIP, "internal: refused route %d", why);
+}
+
+// Launch the mapped row FFT for `a` (batch of a.nbatch <= kMaxBatch items with per-item offsets in `tab`) on the route
+// choose_row_route names for it.  `nlen` = transform length, `logn` = its log2 or -1.
+// Sub-transform form (swiftly_mixed.h): qmul = Q > 1 says that `a` is sub-transform j = qadd of a length-Q*2^logn
+// transform whose radix-Q pass has run: the input is the plain scratch of that pass (a.raw_ld set by the caller, element
+// e at in + e*in_cs), the store map refers to the full length a.full_n with plain output index Q*e + j.
+template <typename R>
+static int run_rows_chunk(swiftly_hip* h, int64_t nlen, int logn, RowsArgs<R>& a, const OffTab& tab, hipStream_t st, int qmul, int qadd) {
+    const bool sub = qmul > 1;
+    const bool all_j = sub && qadd < 0;  // all Q sub-transforms in this launch: outer index = j, input at in + j*in_os
+    if (logn >= 0) {
+        a.tw = twiddles<R>(h, logn);
+        a.full_logn = logn;
+        if (!sub) a.full_n = 0;
+        a.ld_mul = 1;
+        a.st_mul = qmul;
+        a.st_add0 = all_j ? 0 : qadd;
+        a.ld_addmul = 0;
+        a.st_addmul = all_j ? 1 : 0;
+        a.outer = all_j ? qmul : 1;
+        // the Q sub-transforms of a row write interleaved elements of the same lines: their workgroups are enumerated 8 block
+        // ids apart = on one XCD, whose L2 merges the partial lines (K1 of 24k[1]-n12k-1k 1.52 -> 0.88 ms per facet, r3)
+        a.outer_group = all_j ? 1 : 0;
+        if (!all_j) a.in_os = 0;
+        a.out_os = 0;
+        a.tw_full = nullptr;
+        a.tw_on_store = 0;
+        a.raw_st = 0;
+        if (!sub) a.raw_ld = 0;
+    }
+    const RowRoute route = choose_row_route(row_call_of(h, nlen, logn, a, tab, qmul, qadd));
+    switch (route.kind) {
+    case kRouteEmpty:
+        return 0;
+    case kRouteMixed:
+        return run_rows_mixed(h, nlen, h->mixed.find(nlen)->second, a, tab, st);
+    case kRouteBluestein:
+        return run_rows_bluestein(h, nlen, a, tab, st);
+    case kRouteLongRowsF64:
+        if constexpr (sizeof(R) == 8) return run_rows_long(h, logn, a, tab, st);
+        break;
+    case kRouteGeneric:
+        return launch_checked(logn, a, tab, st);
+    case kRouteFourStep:
+        return run_rows_four_step(h, logn, a, tab, st, qmul, qadd);
+    case kRouteRefused:
+        return refuse_route(route.refusal, sizeof(R) == 8, nlen, logn);
+    default:
+        break;
+    }
+    if constexpr (sizeof(R) == 4) {  // the lean complex64 routes
+        switch (route.kind) {
+        case kRouteColPass: {
+            ColZ cz;
+            const ColPassArgs c = col_pass_of(logn, a, tab, cz);
+            const int rc = col_transform(h, logn, c, cz, a.nrows, a.nbatch > 0 ? a.nbatch : 1, st);
+            return rc == -1 ? fail(SWIFTLY_ERR_HIP, "internal: the column passes refuse a call of their route") : rc;
+        }
+        case kRouteLean:
+            return launch_status(launch_row_pass(logn, route.mode, row_pass_of(a), st));
+        case kRouteSplit32k: {
+            const RowPassArgs r = row_pass_of(a);
+            return launch_status(launch_row_pass_split(r, twiddles<float>(h, 14), twiddles<float>(h, 13), r.tw, st));
+        }
+        case kRouteBand32kPlain:
+        case kRouteBand32kMapped:
+        case kRouteBand64k:
+            return launch_band_route(h, route, logn, row_pass_of(a), st);
+        default:
+            break;
+        }
+    }
+    return fail(SWIFTLY_ERR_HIP, "internal: route %d in the wrong precision", route.kind);
 }
 
 // `fill(b, tab_index)` sets the per-item offsets of batch item b into the
@@ -911,22 +923,11 @@ static bool rows_length_supported(const swiftly_hip* h, int64_t n, int logn) {
 template <typename R, class Fill>
 static int run_rows(swiftly_hip* h, int64_t nlen, int logn, RowsArgs<R>& a, const Batch& bt, int use_bits, Fill&& fill,
                     hipStream_t st) {
-    constexpr int maxlog = max_log_rows<R>();
-    if (logn >= 0 && !rows_length_supported<R>(h, nlen, logn))
-        return fail(SWIFTLY_ERR_UNSUPPORTED,
-                    "transform length %lld is not supported by the HIP backend (power of two in [8, %d], or a length "
-                    "whose Bluestein convolution or Q * 2^k sub-transform fits, for %s)",
-                    (long long)nlen, 1 << maxlog, sizeof(R) == 8 ? "complex128: Bluestein and Q * 2^k up to 8192"
-                                                                  : "complex64");
-    const uint64_t n = (uint64_t)nlen;
-    if (n * (uint64_t)a.in_cs >= (uint64_t(1) << 32) || n * (uint64_t)a.out_cs >= (uint64_t(1) << 32))
-        return fail(SWIFTLY_ERR_PARAM, "transform length * column stride must be < 2^32");
-    if (a.nrows <= 0 || bt.n <= 0) return 0;
     const cx<R>* in0 = a.in;
     cx<R>* out0 = a.out;
     const R* win0 = a.st.win;
-    for (int64_t b0 = 0; b0 < bt.n; b0 += kMaxBatch) {
-        const int nb = (int)std::min<int64_t>(kMaxBatch, bt.n - b0);
+    for (int64_t b0 = 0; b0 == 0 || b0 < bt.n; b0 += kMaxBatch) {  // (an empty batch: one chunk without items, for the refusals)
+        const int nb = (int)std::min<int64_t>(kMaxBatch, std::max<int64_t>(bt.n, 0) - b0);
         OffTab tab;
         tab.use = bt.offs ? use_bits : 0;
         if (tab.use)
@@ -939,14 +940,7 @@ static int run_rows(swiftly_hip* h, int64_t nlen, int logn, RowsArgs<R>& a, cons
         c.nbatch = nb;
         c.st_win_bs = bt.mask_bs;
         if (win0) c.st.win = win0 + b0 * bt.mask_bs;
-        int rc;
-        if (logn >= 0) {
-            rc = run_rows_chunk(h, logn, c, tab, st);
-        } else {
-            rc = use_mixed(h, nlen, sizeof(R) == 8) ? run_rows_mixed(h, nlen, h->mixed.find(nlen)->second, c, tab, st)
-                                                     : run_rows_bluestein(h, nlen, c, tab, st);
-        }
-        if (rc) return rc;
+        if (int rc = run_rows_chunk(h, nlen, logn, c, tab, st)) return rc;
     }
     return 0;
 }
@@ -1079,7 +1073,8 @@ extern "C" {
 int swiftly_hip_supports_dtype(const swiftly_hip_t* h, int dtype) {
     if (!h || (dtype != SWIFTLY_C64 && dtype != SWIFTLY_C128)) return 0;
     for (const auto& [n, logn] : {std::pair<int64_t, int>{h->yN, h->log_yN}, {h->xM, h->log_xM}, {h->m, h->log_m}}) {
-        const bool ok = dtype == SWIFTLY_C64 ? rows_length_supported<float>(h, n, logn) : rows_length_supported<double>(h, n, logn);
+        const bool dbl = dtype == SWIFTLY_C128;
+        const bool ok = row_length_supported(dbl, logn, use_mixed(h, n, dbl), have_bluestein(h, n, dbl));
         if (!ok) return 0;
     }
     return 1;

@@ -32,28 +32,18 @@ struct ColPlan {
     const cx<double> *twd1, *twd2, *twdf;
     int a_i_rows, a_o_rows, b_i_rows, b_o_rows;  // row factors of the intermediate
 };
-// Returns -1 when the length is outside the column-pass range or a table is missing (the caller falls back), else 0.
+// The split, the range and the precision of each stage are col_split's (swiftly_rowroute.h; r3 bug behind its gather-sum
+// rule: a 1024-point gather-sum transform ran the plain 32-column kernel, which read the encoded table as a row map); the
+// tables are the handle's.  Returns -1 when the length is outside the column-pass range or a table is missing, else 0.
 static int make_plan(const swiftly_hip* h, int logn, const ColPassArgs& c, int W, ColPlan& p) {
-    // single pass up to 1024 points; the gather-sum load (c.gs, backward pass) has complex64 instances for 64-column tiles
-    // only, i.e. up to 512 points: longer gather-sum transforms go through the four-step, whose pass A carries the load (r3
-    // bug: a 1024-point gather-sum transform ran the plain 32-column kernel, which read the encoded table as a row map)
-    // complex128 storage (c.c128): float64 arithmetic in every pass, single pass up to 512 points -- with the gather-sum
-    // load too (32-column tiles at 128, 256 and 512 points), and pass A of its four-steps at 32 .. 128 points
+    const ColSplit s = col_split(logn, ColAsk{c.gs != 0, c.c128 != 0, c.f64 != 0, h->col_f64_stages}, W);
+    if (s.status) return -1;
     p.c128 = c.c128 != 0;
     p.esz = p.c128 ? sizeof(cx<double>) : sizeof(cx<float>);
-    p.two = logn > (c.gs ? 9 : p.c128 ? kColPassMaxLogF64 : kColPassMaxLog);
-    p.l1 = p.two ? logn / 2 : logn;  // (32768 = 128 x 256; 256 x 128 and 64 x 512 measured slower, r4)
-    p.l2 = logn - p.l1;
-    if (p.l1 < kColPassMinLog || p.l1 > kColPassMaxLog || (p.two && (p.l2 < kColPassMinLog || p.l2 > kColPassMaxLog))) return -1;
+    p.two = s.two; p.l1 = s.l1; p.l2 = s.l2;
     p.n = uint64_t(1) << logn;
     p.n1 = 1 << p.l1; p.n2 = 1 << p.l2;
-    // float64 arithmetic where the caller asks for it and the instances exist (else float32, silently: same results to
-    // float32 rounding)
-    p.f64 = (c.f64 || p.c128) && (p.two ? (col_pass_f64_supported(p.l1) && col_pass_f64_supported(p.l2))
-                                         : (col_pass_f64_supported(logn) && !(c.gs && !p.c128 && logn > 8)));
-    if (p.c128 && !p.f64) return -1;
-    auto stage = [&](int bit) { return (p.f64 && (p.c128 || (h->col_f64_stages & bit))) ? 1 : 0; };
-    p.f64_one = stage(4); p.f64_a = stage(1); p.f64_b = stage(2);
+    p.f64 = s.f64; p.f64_one = s.f64_one; p.f64_a = s.f64_a; p.f64_b = s.f64_b;
     p.tw1 = twiddles<float>(h, p.l1);
     p.tw2 = p.two ? twiddles<float>(h, p.l2) : p.tw1;
     p.twf = p.two ? twiddles<float>(h, logn) : p.tw1;
@@ -62,7 +52,6 @@ static int make_plan(const swiftly_hip* h, int logn, const ColPassArgs& c, int W
     p.twd2 = p.f64 && p.two ? twiddles<double>(h, p.l2) : p.twd1;
     p.twdf = p.f64 && p.two ? twiddles<double>(h, logn) : p.twd1;
     if (p.f64 && (!p.twd1 || !p.twd2 || !p.twdf)) return -1;
-    if (p.two && p.n * (uint64_t)W >= (uint64_t(1) << 32)) return -1;
     // Layout of the intermediate (r4): row y2 * n1 + k1 -- a pass-A workgroup (one y2) WRITES n1 consecutive rows and a
     // pass-B workgroup (one k1) reads a comb -- instead of row k1 * n2 + y2 (comb written, consecutive rows read).  HBM
     // writes are the expensive direction on this chip (tools/mall_pipe.hip: a comb costs 7 % on the write side and nothing
@@ -249,7 +238,8 @@ static int run_plain(const ColPlan& p, const ColPassArgs& c, const ColZ& cz, int
 //   pass B (length n2 over y2, one per k1): X[k1 + n1 k2]       = sum_y2 scratch[k1*n2 + y2] W_n2^(y2 k2)
 // `c` carries the load / store maps, windows, conjugation flags, scale, batch strides, column gather and row
 // maps of the whole transform; in/out pitches and pointers are given separately.  Returns -1 when the length
-// is outside the column-pass range (caller falls back), else a status code.
+// is outside the column-pass range (col_split, swiftly_rowroute.h: the row primitives ask it before they come here), else
+// a status code.
 // Sub-transform form (qmul = Q > 0, swiftly_mixed.h): the input is the plain scratch of the radix-Q pass (element y of
 // the length-2^logn sub-transform j = qadd at row y of `c.in`), the store map of `c` refers to the full length full_n
 // with plain output index Q*k + j.

@@ -196,9 +196,7 @@ struct DeviceGuard {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
-// Transforms of length >= 2^kTwoPassMinLog along a STRIDED axis (rows contiguous) are decomposed into
-// two passes of short transforms so that every access is >= 128 B contiguous.
-static const int kTwoPassMinLog = 9;
+// (kTwoPassMinLog, where a strided-axis transform becomes a four-step: swiftly_rowroute.h)
 
 // element k of a complex array of either storage type (complex128 arrays travel through the cx<float> pointers of the
 // column-pass and sum_finish argument blocks)

@@ -12,6 +12,7 @@
 // one 8-byte global access per point and the LDS exchange.
 #pragma once
 #include "swiftly_caps.h"  // col_pass_f64_supported
+#include "swiftly_rowroute.h"  // the lengths of the column passes
 #include "swiftly_fft.h"
 
 namespace swf {
@@ -215,7 +216,7 @@ struct CGeoFor {
 };
 // double arithmetic: 16 points per lane (64 VGPRs of data), re / im exchanged separately; 128 points: 512 threads and
 // 64 KiB (two workgroups per CU), 256 points: 1024 threads and 128 KiB, 512 points: 32-column tiles, 1024 threads, 128 KiB
-constexpr int kColPassMaxLogF64 = 9;
+// (kColPassMaxLogF64: swiftly_rowroute.h)
 template <int LOGN>
 struct CGeoFor<LOGN, double> {
     static constexpr int LOGP = LOGN < 4 ? LOGN : 4;
@@ -551,8 +552,7 @@ __global__ __launch_bounds__(G::NT, G::MINW) void col_pass2_kernel(const ColPass
                                                             &S2);
 }
 
-constexpr int kColPassMinLog = 2;
-constexpr int kColPassMaxLog = 10;  // 1024 points: 32-column tiles
+// (kColPassMinLog, kColPassMaxLog: swiftly_rowroute.h)
 
 // src2 (optional): the piece-aware load of a single pass (mode 2); hipErrorInvalidConfiguration without launching anything
 // when the case has no such instance (col_pass_pieces_supported)

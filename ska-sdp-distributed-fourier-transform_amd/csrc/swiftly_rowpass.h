@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "swiftly_caps.h"  // row_pass_whole_stage_columns
+#include "swiftly_rowroute.h"  // kRowPassMinLog, kRowPassMaxLog
 #include "swiftly_fft.h"
 
 // groups of three loads the W4 instances of the band row kernel request before the first one is consumed (0: the
@@ -859,8 +860,7 @@ __global__ __launch_bounds__(G::NT, 4) void row_pass_band_kernel(const RowPassAr
 #endif
 }
 
-constexpr int kRowPassMinLog = 13;
-constexpr int kRowPassMaxLog = 15;
+// (kRowPassMinLog, kRowPassMaxLog: swiftly_rowroute.h)
 int launch_row_pass(int logn, int mode, const RowPassArgs& a, hipStream_t s);
 int row_pass_half_occupancy(int lds_bytes);
 // multi-workgroup form for N = 32768 (MODE 0 only); tw14 / tw13 = tables of length 16384 / 8192, tw_full of length N

@@ -9,6 +9,7 @@
 // reference's core.py:189-484 onto it).
 #pragma once
 #include "swiftly_caps.h"  // kMinLogN, kMaxLogNFloat
+#include "swiftly_rowroute.h"  // kMaxLogNDouble, kMaxLogNDoubleRows
 #include "swiftly_fft.h"
 
 namespace swf {
@@ -296,11 +297,6 @@ struct GeoFor {
     static constexpr bool SPLIT = (!DBL && LOGN == 15);
     using type = Geo<R, LOGN, LOGP, NT, SPLIT>;
 };
-
-constexpr int kMaxLogNDouble = 13;  // single-workgroup double kernels, Bluestein and radix-Q double tables
-// power-of-two complex128 transforms of the primitives (run_rows): 2^14 / 2^15 as four-steps -- along a strided axis
-// through two fft_rows_kernel passes, along the contiguous axis through swiftly_rowslong.h
-constexpr int kMaxLogNDoubleRows = 15;
 
 // implemented in fft_rows_f32.hip / fft_rows_f64.hip
 int launch_fft_rows(int logn, const RowsArgs<float>& a, const OffTab& tab, hipStream_t s);

@@ -16,7 +16,7 @@
 
 namespace swf {
 
-constexpr int kLongLogN1 = 7;   // n1 = 128 points per column of pass A
+// (kLongLogN1, n1 = 128 points per column of pass A: swiftly_rowroute.h)
 constexpr int kLongTileY2 = 32;  // RB: consecutive y2 per workgroup = 512-byte runs per load / store
 
 // Pass A geometry: radix 8 (double register budget, as fft_rows_kernel), T = n1 / 8 = 16 lanes per column
