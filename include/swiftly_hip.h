@@ -132,10 +132,17 @@ enum {
                                                    complex128 K1 -- the sizes of BAND_PIPELINE_EXPLICIT in complex128 (n_facets
                                                    not counted); complex64 is answered no (float32 facets: REAL_FACETS).  The
                                                    gate the entry point refuses through ("real facets, float64: ...") */
-    SWIFTLY_FEATURE_REAL_FACETS_OUT_F64 = 15    /* finish_facet_band_real64 (dtype = the INPUT type): FLOAT64 facets out of the
+    SWIFTLY_FEATURE_REAL_FACETS_OUT_F64 = 15,   /* finish_facet_band_real64 (dtype = the INPUT type): FLOAT64 facets out of the
                                                    complex128 backward band -- the sizes of BACKWARD_BAND_EXPLICIT in
                                                    complex128; complex64 is answered no (float32 facets: REAL_FACETS_OUT).  The
                                                    gate the entry point refuses through ("real facet output, float64: ...") */
+    SWIFTLY_FEATURE_REAL_FACETS_RFFT_64K = 16,  /* prepare_facet_band_rfft / prepare_facet_band_rows_rfft on 65536-point rows
+                                                   (one 32768-point transform per row), size part: the sizes of REAL_FACETS with
+                                                   yN_size 65536.  The entry points take a handle that REAL_FACETS_RFFT or this
+                                                   feature supports ("real facets, half-length: ...") */
+    SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R_64K = 17 /* finish_facet_band_c2r on 65536-point band rows, size part: the sizes of
+                                                   REAL_FACETS_OUT with yN_size 65536.  The entry point takes a handle that
+                                                   REAL_FACETS_OUT_C2R or this feature supports ("real facets out, half-length: ...") */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -420,7 +427,8 @@ int swiftly_hip_prepare_facet_band_real64(swiftly_hip_t* h, int dtype, const voi
  * yN_size / 2-point complex transform of z[n] = x[2n] + i x[2n+1] and the recombination
  * S[k] = E[k] + W^k O[k], S[k + yN_size/2] = E[k] - W^k O[k] (csrc/swiftly_rowreal.h).  The values ROUND DIFFERENTLY from
  * those of the _real entry points (same bound against the exact transform, not the same bits), which is why this is a door
- * of its own that nothing else routes to.  Sizes: SWIFTLY_FEATURE_REAL_FACETS_RFFT (REAL_FACETS with yN_size 32768).  Per
+ * of its own that nothing else routes to.  Sizes: SWIFTLY_FEATURE_REAL_FACETS_RFFT (REAL_FACETS with yN_size 32768) or
+ * SWIFTLY_FEATURE_REAL_FACETS_RFFT_64K (REAL_FACETS with yN_size 65536: one 32768-point transform per row).  Per
  * call the adjacent reals are fetched with 8-byte loads, so an odd facet_size, an odd position of the facet in the padded
  * row (facet_off + yN_size/2 - facet_size/2 odd), an odd in_row_stride or an `in` that is not 8-byte aligned is REFUSED with
  * SWIFTLY_ERR_UNSUPPORTED ("real facets, half-length: ..."): nothing is written and no other kernel runs instead.  Parameter
@@ -732,7 +740,8 @@ int swiftly_hip_finish_facet_band_real64(swiftly_hip_t* h, int dtype, const void
  * point above runs the whole complex transform in two workgroups per row and drops the imaginary half.  Same arguments, same
  * quantity, the same error bound against the exact transform -- NOT the same bits: the rounding differs.  A kernel and a door
  * of its own that nothing else routes to (not an instance of the band row kernel: swiftly_hip_last_band_instance does not
- * count it).  Sizes: SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R (REAL_FACETS_OUT with yN_size 32768).  Per call, an odd facet_size, a
+ * count it).  Sizes: SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R (REAL_FACETS_OUT with yN_size 32768) or
+ * SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R_64K (yN_size 65536: one 32768-point transform per row).  Per call, an odd facet_size, a
  * facet at an odd position of the padded row (yN_size / 2 - facet_size / 2 + facet_off odd), an odd out_row_stride or an `out`
  * that is not 8-byte aligned is SWIFTLY_ERR_UNSUPPORTED ("real facets out, half-length: ...") and nothing is written -- a
  * refusal is not a copy through the entry point above; out_row_stride < facet_size is SWIFTLY_ERR_PARAM as there.  The

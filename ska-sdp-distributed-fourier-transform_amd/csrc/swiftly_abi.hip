@@ -278,6 +278,8 @@ int swiftly_hip_create(swiftly_hip_t** out, int64_t N, int64_t yN, int64_t xM, d
         rc = make_compact_twiddles(h, 14, 5);
         if (!rc) h->win4.twc = compact_twiddles(h, 14, 5);
     }
+    // ... and of the 32768-point table for the half-length forms of 65536-point rows (RowRealGeo64k / RowC2RGeo64k)
+    if (!rc && h->log_yN == 16) rc = make_compact_twiddles(h, 15, 5);
     if (!rc && sum_finish_supported(h->log_m, h->log_xM)) {
         rc = make_compact_twiddles(h, h->log_m, h->log_m - 6);
         if (!rc) rc = make_compact_twiddles(h, h->log_xM, h->log_xM - (h->log_xM >= 12 ? 8 : 6));
@@ -1294,7 +1296,8 @@ int swiftly_hip_finish_facet(swiftly_hip_t* h, int dtype, const void* in, int64_
 enum class K1Form {
     Band,            // the band row kernel (or, for short rows and complex128, the generic contiguous-axis prepare_facet)
     RealBand,        // ... loading float32 rows: SWIFTLY_FEATURE_REAL_FACETS
-    HalfLengthBand,  // one half-length transform per real row (swiftly_rowreal.h), SWIFTLY_FEATURE_REAL_FACETS_RFFT: its own
+    HalfLengthBand,  // one half-length transform per real row (swiftly_rowreal.h), SWIFTLY_FEATURE_REAL_FACETS_RFFT or
+                     // _RFFT_64K (the compact section and the launcher's instance follow log_yN): its own
                      // kernel and its own refusals -- a call the kernel does not take is refused before anything is written,
                      // never handed to the band row kernel
     WindowRows,      // the whole-row kernel storing complete window rows (swiftly_rowwhole.h)
@@ -1319,7 +1322,7 @@ static int prepare_facet_k1(K1Form form, swiftly_hip_t* h, int dtype, const void
     if (real_in) {  // float32 (RealBand64: float64) rows: the capability rule of the form's feature
         const std::string why = form == K1Form::RealWindowRows ? why_not_real_window_rows(*h, dtype)
                                 : form == K1Form::RealBand64   ? why_not_real_facets_f64(*h, dtype)
-                                : half                         ? why_not_real_facets_rfft(*h, dtype)
+                                : half                         ? why_not_half_length_k1(*h, dtype)
                                                                : why_not_real_facets(*h, dtype);
         if (!why.empty())
             return fail(SWIFTLY_ERR_UNSUPPORTED, "%s: %s", form == K1Form::RealWindowRows ? "prepare_facet_window_rows_real"
@@ -1364,7 +1367,7 @@ static int prepare_facet_k1(K1Form form, swiftly_hip_t* h, int dtype, const void
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band_rfft: real facets, half-length: input is not 8-byte aligned");
     }
     if (rows == 0) return 0;
-    if (!band_is_split(h)) {  // (never the half-length form: its capability rule needs yN_size 32768)
+    if (!band_is_split(h)) {  // (never the half-length form: its capability rules need yN_size 32768 or 65536)
         // short rows: the generic contiguous-axis prepare_facet, whole padded axis, plain column order
         if (band_start != 0 || band_len != yN)
             return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_band: yN_size %d keeps the whole padded axis (band must be (0, yN_size))", yN);
@@ -1386,11 +1389,15 @@ static int prepare_facet_k1(K1Form form, swiftly_hip_t* h, int dtype, const void
     r.conj_ld = r.conj_st = 1;
     r.row_win = fold_other_axis_window ? h->invp_f + (facet_lo(*h, other_axis_size) + (int)other_axis_row0) : nullptr;
     r.band_start = (int)band_start; r.band_len = (int)band_len; r.band_half = (int)band_half_columns(band_len);
-    if (half) r.twc = compact_twiddles(h, 14, 5);
+    if (half) r.twc = compact_twiddles(h, h->log_yN - 1, 5);  // 32 points per lane of the half-length transform
     const cx<float>* twh = twiddles<float>(h, h->log_yN - 1);
     const cx<float>* twf = twiddles<float>(h, h->log_yN);
     if (!twh || !twf || (half && !r.twc)) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
-    if (half) return launch_status(launch_row_real_band(r, twh, twf, (hipStream_t)stream));
+    if (half) {
+        const int e = launch_row_real_band(h->log_yN, r, twh, twf, (hipStream_t)stream);
+        if (e == -1) return fail(SWIFTLY_ERR_HIP, "internal: prepare_facet_band_rfft: the half-length kernel does not take this call");
+        return launch_status(e);
+    }
     if (windows) {  // complete window rows (whole-row kernel)
         r.win_full = 1;
         r.win_pitch = win_stride;
@@ -1497,7 +1504,8 @@ int swiftly_hip_prepare_facet_window_rows_real(swiftly_hip_t* h, int dtype, cons
 enum class B8Form {
     Complex,
     RealStore,       // the real-store instances of the row kernels: SWIFTLY_FEATURE_REAL_FACETS_OUT
-    HalfLengthReal,  // one half-length transform per row (swiftly_rowc2r.h), SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R: its own kernel
+    HalfLengthReal,  // one half-length transform per row (swiftly_rowc2r.h), SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R or _C2R_64K
+                     // (the compact section and the launcher's instance follow log_yN): its own kernel
                      // and its own refusals -- a call the kernel does not take is refused before anything is written, never
                      // handed to the real-store form
     RealStore64,     // complex128 band rows in, FLOAT64 rows out: SWIFTLY_FEATURE_REAL_FACETS_OUT_F64 (a door of its own: the
@@ -1511,7 +1519,7 @@ static int finish_facet_band_impl(B8Form form, swiftly_hip_t* h, int dtype, cons
     const char* name = half ? "finish_facet_band_c2r" : form == B8Form::RealStore64 ? "finish_facet_band_real64" : "finish_facet_band_real";
     CHECK_COMMON();
     if (real_out) {  // float32 (RealStore64: float64) rows out: the capability rule of the form's feature
-        const std::string why = half                          ? why_not_real_facets_out_c2r(*h, dtype)
+        const std::string why = half                          ? why_not_half_length_finish(*h, dtype)
                                 : form == B8Form::RealStore64 ? why_not_real_facets_out_f64(*h, dtype)
                                                               : why_not_real_facets_out(*h, dtype);
         if (!why.empty()) return fail(SWIFTLY_ERR_UNSUPPORTED, "%s: %s", name, why.c_str());
@@ -1552,14 +1560,15 @@ static int finish_facet_band_impl(B8Form form, swiftly_hip_t* h, int dtype, cons
         // the mask and the PSWF window of finish_facet as the ONE window the mapped store of the band row kernel takes
         r.st_win = (const float*)mask; r.st_win2 = h->invp_f + facet_lo(*h, facet_size);
         r.scale = 1.f;
-        r.twc = compact_twiddles(h, 14, 5);
+        r.twc = compact_twiddles(h, h->log_yN - 1, 5);  // 32 points per lane of the half-length transform
         const cx<float>* twh = twiddles<float>(h, h->log_yN - 1);
         const cx<float>* twf = twiddles<float>(h, h->log_yN);
         if (!twh || !twf || !r.twc) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle tables");
         void* tmp = nullptr;
         if (int rc = single_store_window(r, st, &tmp)) return rc;
-        const int e = launch_row_c2r_band(r, twh, twf, st);
+        const int e = launch_row_c2r_band(h->log_yN, r, twh, twf, st);
         if (tmp) (void)hipFreeAsync(tmp, st);
+        if (e == -1) return fail(SWIFTLY_ERR_HIP, "internal: finish_facet_band_c2r: the half-length kernel does not take this call");
         return launch_status(e);
     }
     Batch bt{1, 0, 0, nullptr, 0};

@@ -309,6 +309,35 @@ inline std::string why_not_real_facets_out_c2r(const Sizes& s, int dtype) {
         return reason("real facets out, half-length: needs yN %d; got yN %lld", 1 << kRealOutC2RLogYN, (long long)s.yN);
     return {};
 }
+// the same two forms on 65536-point rows (one 32768-point transform, 1024 threads x 32 points: RowRealGeo64k / RowC2RGeo64k):
+// features of their own, SWIFTLY_FEATURE_REAL_FACETS_RFFT_64K / _OUT_C2R_64K, so that the two above answer as they always
+// did.  The entry points take a handle either feature of their pair supports and name both lengths when neither does.
+constexpr int kRealRfftLogYN64k = 16;
+inline std::string why_not_real_facets_rfft_64k(const Sizes& s, int dtype) {
+    if (std::string why = why_not_real_facets(s, dtype); !why.empty()) return "real facets, half-length: " + why;
+    if (s.log_yN != kRealRfftLogYN64k)
+        return reason("real facets, half-length: needs yN %d; got yN %lld", 1 << kRealRfftLogYN64k, (long long)s.yN);
+    return {};
+}
+constexpr int kRealOutC2RLogYN64k = 16;
+inline std::string why_not_real_facets_out_c2r_64k(const Sizes& s, int dtype) {
+    if (std::string why = why_not_real_facets_out(s, dtype); !why.empty()) return "real facets out, half-length: " + why;
+    if (s.log_yN != kRealOutC2RLogYN64k)
+        return reason("real facets out, half-length: needs yN %d; got yN %lld", 1 << kRealOutC2RLogYN64k, (long long)s.yN);
+    return {};
+}
+// what the entry points of the half-length forms refuse through: feature 12 or 16 (13 or 17)
+inline std::string why_not_half_length_k1(const Sizes& s, int dtype) {
+    if (why_not_real_facets_rfft(s, dtype).empty() || why_not_real_facets_rfft_64k(s, dtype).empty()) return {};
+    if (std::string why = why_not_real_facets(s, dtype); !why.empty()) return "real facets, half-length: " + why;
+    return reason("real facets, half-length: needs yN %d or %d; got yN %lld", 1 << kRealRfftLogYN, 1 << kRealRfftLogYN64k, (long long)s.yN);
+}
+inline std::string why_not_half_length_finish(const Sizes& s, int dtype) {
+    if (why_not_real_facets_out_c2r(s, dtype).empty() || why_not_real_facets_out_c2r_64k(s, dtype).empty()) return {};
+    if (std::string why = why_not_real_facets_out(s, dtype); !why.empty()) return "real facets out, half-length: " + why;
+    return reason("real facets out, half-length: needs yN %d or %d; got yN %lld", 1 << kRealOutC2RLogYN, 1 << kRealOutC2RLogYN64k,
+                  (long long)s.yN);
+}
 // size part of prepare_facet_window_rows (the band, the facets and the windows are per call)
 inline std::string why_not_window_rows(const Sizes& s) {
     if (s.log_yN == kWindowRowsLogYN && s.log_m == kWindowRowsLogM && s.xM <= (int64_t(1) << kPlacedMaxLogXM)) return {};

@@ -9,6 +9,10 @@
 // kernel of swiftly_rowpass.h runs two, each loading the whole band row): 512 threads x 32 points, phases 32 . 32 . 16 of the
 // engine in swiftly_fft.h, the split re/im exchange buffer (66 KB, two workgroups = two ROWS per CU at <= 128 VGPRs),
 // preloaded twiddles from the compact sections.
+// N = 65536 (RowC2RGeo64k): the same kernel on T = 1024 threads x 32 points, phases 32 . 32 . 32, a 132 KB exchange buffer
+// (one workgroup per CU).  Everything below holds with T for 512 (runs of T consecutive indices are workgroup-uniform
+// questions, a wave stores 512 contiguous bytes): the kernel needs 32 points per lane and N / T = 64, nothing else of the
+// geometry.
 //
 // Load: the band row is [ld_len] complex64 in plain column order -- element d is centred column (band_start + d) mod N, i.e.
 // plain k sits at d = (k + N/2 + ld_a) mod N with ld_a = -band_start mod N (band_as_load_map) -- read through buffer loads
@@ -36,6 +40,7 @@
 namespace swf {
 
 using RowC2RGeo = RGeoPreC<14, 5, true>;
+using RowC2RGeo64k = RGeoPreC<15, 5, true>;  // 65536-point rows
 
 template <class G>
 __global__ __launch_bounds__(G::NT, 4) void row_c2r_band_kernel(const RowPassArgs A, const cx<float>* __restrict__ gin,
@@ -45,9 +50,8 @@ __global__ __launch_bounds__(G::NT, 4) void row_c2r_band_kernel(const RowPassArg
                                                                 const cx<float>* __restrict__ tw_full) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int P = G::P, T = G::T, M = G::N, N = 2 * G::N;
-    static_assert(P == 32 && T == 512 && G::SPLIT, "512 threads x 32 points, split exchange");
-    static_assert(last_phase_logr<G>() == 4, "phases 32 . 32 . 16");
-    static_assert(N / T == 64, "W_N^(T r) = W_64^r");
+    static_assert(P == 32 && G::SPLIT, "32 points per lane, split exchange");
+    static_assert(N / T == 64, "W_N^(T r) = W_64^r (mul_w64)");
     const int t = threadIdx.x;
     const int row = blockIdx.x;  // uniform; row r on XCD r mod 8
     int in_row = row;
@@ -138,11 +142,12 @@ __global__ __launch_bounds__(G::NT, 4) void row_c2r_band_kernel(const RowPassArg
     }
 }
 
-// B8 of `a.nrows` band rows ([a.ld_len] complex64 at a.in, a.in_pitch in elements, a.ld_a = -band_start mod 32768) into
-// float32 facet rows (a.out float32, a.out_pitch in reals, a.out_real set): a.st_a / a.st_len / a.out_pitch even and a.out
-// 8-byte aligned (caller-checked), a.st_win the ONE combined window of st_len entries, a.twc = the compact twiddle sections
-// of the 16384-point table for 32 points per lane.  Returns the launch status; -1: not this kernel's call.
-int launch_row_c2r_band(const RowPassArgs& a, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s);
-int row_c2r_band_occupancy();  // workgroups per CU
+// B8 of `a.nrows` band rows of 2^log_yN = 32768 or 65536 points ([a.ld_len] complex64 at a.in, a.in_pitch in elements,
+// a.ld_a = -band_start mod 2^log_yN) into float32 facet rows (a.out float32, a.out_pitch in reals, a.out_real set): a.st_a /
+// a.st_len / a.out_pitch even and a.out 8-byte aligned (caller-checked), a.st_win the ONE combined window of st_len entries,
+// tw_half / tw_full = the tables of length 2^(log_yN - 1) / 2^log_yN, a.twc = the compact twiddle sections of the half-length
+// table for 32 points per lane.  Returns the launch status; -1: not this kernel's call (another row length included).
+int launch_row_c2r_band(int log_yN, const RowPassArgs& a, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s);
+int row_c2r_band_occupancy(int log_yN = 15);  // workgroups per CU
 
 }  // namespace swf

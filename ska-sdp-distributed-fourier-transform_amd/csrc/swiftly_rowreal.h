@@ -8,6 +8,9 @@
 // ONE workgroup per row (the band row kernel of swiftly_rowpass.h runs two, each loading and windowing the whole row):
 // 512 threads x 32 points, phases 32 . 32 . 16 of the engine in swiftly_fft.h, the split re/im exchange buffer (66 KB,
 // two workgroups per CU at <= 128 VGPRs), preloaded twiddles from the compact sections.
+// N = 65536 (RowRealGeo64k): the same kernel on T = 1024 threads x 32 points, phases 32 . 32 . 32, a 132 KB exchange buffer
+// (one workgroup per CU).  Everything below holds with T for 512: the kernel needs 32 points per lane, N / T = 64 and
+// padded exchange positions that are affine in the register, nothing else of the geometry.
 //
 // Load: the map of a prepare_* primitive as the PAIR / REAL = 1 instances read it -- plain index p is element
 // q = ((p + N/2) mod N + ld_a) mod N of the row, window ld_win[q], zero for q >= ld_len -- through buffer loads whose
@@ -35,6 +38,7 @@
 namespace swf {
 
 using RowRealGeo = RGeoPreC<14, 5, true>;
+using RowRealGeo64k = RGeoPreC<15, 5, true>;  // 65536-point rows
 
 template <class G>
 __global__ __launch_bounds__(G::NT, 4) void row_real_band_kernel(const RowPassArgs A, const float* __restrict__ gin,
@@ -44,8 +48,8 @@ __global__ __launch_bounds__(G::NT, 4) void row_real_band_kernel(const RowPassAr
                                                                  const cx<float>* __restrict__ tw_full) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int P = G::P, T = G::T, M = G::N, N = 2 * G::N;
-    static_assert(P == 32 && T == 512 && G::SPLIT, "512 threads x 32 points, split exchange");
-    static_assert(last_phase_logr<G>() == 4, "phases 32 . 32 . 16");
+    static_assert(P == 32 && G::SPLIT, "32 points per lane (registers v and 31 - v mirror each other), split exchange");
+    static_assert(N / T == 64, "W_N^(T v) = W_64^v (mul_w64)");
     constexpr int VSTEP = T + (T >> G::LOGPAD);  // exchange-buffer distance of e and e + T
     static_assert((T & ((1 << G::LOGPAD) - 1)) == 0 && (size_t)G::PITCH * 4 == G::LDS_BYTES, "padded positions are affine in the register");
     const int t = threadIdx.x;
@@ -103,11 +107,37 @@ __global__ __launch_bounds__(G::NT, 4) void row_real_band_kernel(const RowPassAr
     const int pw = t + (t >> G::LOGPAD);               // position of e = t (+ VSTEP v)
     const int mb = T - t;                              // mirror of e = t + T v: mb + T (31 - v); t = 0: T (32 - v), 0 for v = 0
     const int pm = mb + (mb >> G::LOGPAD);
-    const int pm0 = t == 0 ? 0 : pm + VSTEP * (P - 1);  // v = 0
+    // An LDS instruction carries a 16-bit byte offset.  Positions further than that from the lane's base -- none in the
+    // 66 KB buffer of T = 512, registers 16 .. 31 in the 132 KB buffer of T = 1024 -- are addressed from a SECOND base,
+    // VFAR registers on, which an empty asm statement keeps in one register: left alone the compiler holds an address
+    // register per far position through the exchange (T = 1024: 40 bytes of scratch).
+    constexpr int VFAR = (size_t)VSTEP * (P - 1) * 4 > 0xffff ? P / 2 : P;
+    static_assert(VSTEP * (VFAR - 1) * 4 <= 0xffff && VSTEP * (P - 1 - VFAR) * 4 <= 0xffff, "LDS offsets");
+    int pw_far = 0, pm_far = 0;
+    if constexpr (VFAR < P) {
+        pw_far = pw + VSTEP * VFAR;
+        pm_far = pm + VSTEP * VFAR;
+        asm("" : "+v"(pw_far), "+v"(pm_far));
+    }
+    auto own = [&](auto vI) {  // position of e = t + T v
+        constexpr int v = decltype(vI)::value;
+        if constexpr (v < VFAR)
+            return pw + VSTEP * v;
+        else
+            return pw_far + VSTEP * (v - VFAR);
+    };
+    auto mirror = [&](auto vI) {  // position of M - e for t > 0 (and of T (32 - v) for t = 0, v > 0)
+        constexpr int k = P - 1 - decltype(vI)::value;
+        if constexpr (k < VFAR)
+            return pm + VSTEP * k;
+        else
+            return pm_far + VSTEP * (k - VFAR);
+    };
+    const int pm0 = t == 0 ? 0 : mirror(std::integral_constant<int, 0>{});  // v = 0
     // (the last gather of fft_phases ends with a barrier: the buffer is free)
     static_for<0, P>([&](auto vI) {
         constexpr int v = decltype(vI)::value;
-        buf[pw + VSTEP * v] = z[v].x;
+        buf[own(vI)] = z[v].x;
     });
     __syncthreads();
     float dm[P];  // a - c
@@ -117,14 +147,14 @@ __global__ __launch_bounds__(G::NT, 4) void row_real_band_kernel(const RowPassAr
         if constexpr (v == 0)
             c = buf[pm0];
         else
-            c = buf[pm + VSTEP * (P - 1 - v)];
+            c = buf[mirror(vI)];
         dm[v] = z[v].x - c;
         z[v].x += c;
     });
     __syncthreads();
     static_for<0, P>([&](auto vI) {
         constexpr int v = decltype(vI)::value;
-        buf[pw + VSTEP * v] = z[v].y;
+        buf[own(vI)] = z[v].y;
     });
     __syncthreads();
 
@@ -156,7 +186,7 @@ __global__ __launch_bounds__(G::NT, 4) void row_real_band_kernel(const RowPassAr
             if constexpr (v == 0)
                 dmir[0] = buf[pm0];
             else
-                dmir[v - c0] = buf[pm + VSTEP * (P - 1 - v)];
+                dmir[v - c0] = buf[mirror(std::integral_constant<int, v>{})];
         });
         static_for<0, CH>([&](auto iI) {
             constexpr int v = c0 + decltype(iI)::value;
@@ -171,10 +201,11 @@ __global__ __launch_bounds__(G::NT, 4) void row_real_band_kernel(const RowPassAr
     });
 }
 
-// K1 of `a.nrows` real rows of 32768 points into the parity-split band (a.band_len > 0): a.in float32, a.in_pitch in reals,
-// a.ld_a / a.ld_len / a.in_pitch even and a.in 8-byte aligned (caller-checked), a.twc = the compact twiddle sections of
-// the 16384-point table for 32 points per lane.  Returns the launch status.
-int launch_row_real_band(const RowPassArgs& a, const cx<float>* tw14, const cx<float>* tw_full, hipStream_t s);
-int row_real_band_occupancy();  // workgroups per CU
+// K1 of `a.nrows` real rows of 2^log_yN = 32768 or 65536 points into the parity-split band (a.band_len > 0): a.in float32,
+// a.in_pitch in reals, a.ld_a / a.ld_len / a.in_pitch even and a.in 8-byte aligned (caller-checked), tw_half / tw_full = the
+// tables of length 2^(log_yN - 1) / 2^log_yN, a.twc = the compact twiddle sections of the half-length table for 32 points
+// per lane.  Returns the launch status; -1: not this kernel's call (another row length included).
+int launch_row_real_band(int log_yN, const RowPassArgs& a, const cx<float>* tw_half, const cx<float>* tw_full, hipStream_t s);
+int row_real_band_occupancy(int log_yN = 15);  // workgroups per CU
 
 }  // namespace swf

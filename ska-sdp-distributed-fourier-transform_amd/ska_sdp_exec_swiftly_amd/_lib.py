@@ -19,7 +19,8 @@ ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
 (FEATURE_FUSED_SUBGRID, FEATURE_BAND_PIPELINE, FEATURE_BAND_PIPELINE_EXPLICIT, FEATURE_BACKWARD_BAND, FEATURE_SPLIT_BAND,
  FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE, FEATURE_REAL_FACETS,
  FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH, FEATURE_REAL_WINDOW_ROWS, FEATURE_REAL_FACETS_RFFT,
- FEATURE_REAL_FACETS_OUT_C2R, FEATURE_REAL_FACETS_F64, FEATURE_REAL_FACETS_OUT_F64) = range(16)
+ FEATURE_REAL_FACETS_OUT_C2R, FEATURE_REAL_FACETS_F64, FEATURE_REAL_FACETS_OUT_F64, FEATURE_REAL_FACETS_RFFT_64K,
+ FEATURE_REAL_FACETS_OUT_C2R_64K) = range(18)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None

@@ -233,7 +233,8 @@ class SwiftlyBackward:
         construction when ``dtype`` is given, else at the first data.
     :param half_length_finish: (``facet_dtype=torch.float32`` only, else ``ValueError``) finish the float32 facets through
         the half-length form of the contiguous-axis kernel (``core.finish_facet_band(..., real=True, half_length=True)``):
-        one 16384-point transform per 32768-point band row.  The same facets within the same error bound, not the same
+        one 16384-point transform per 32768-point band row (``_lib.FEATURE_REAL_FACETS_OUT_C2R``), one 32768-point
+        transform per 65536-point band row (``_lib.FEATURE_REAL_FACETS_OUT_C2R_64K``).  The same facets within the same error bound, not the same
         bits as without it.  Taken where :py:attr:`half_length_finish` says so; everywhere else the pass runs exactly
         what it runs without the keyword.
     """

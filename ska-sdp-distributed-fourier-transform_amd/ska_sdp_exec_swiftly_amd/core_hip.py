@@ -590,10 +590,12 @@ class SwiftlyCoreHip:
 
     def supports_real_facets_rfft(self):
         """True when the half-length K1 of real-valued facets exists for these sizes (``prepare_facet_band(...,
-        half_length=True)``; ``swiftly_hip_prepare_facet_band_rfft``): :py:meth:`supports_real_facets` at ``yN_size`` 32768.
+        half_length=True)``; ``swiftly_hip_prepare_facet_band_rfft``): :py:meth:`supports_real_facets` at ``yN_size`` 32768
+        (``FEATURE_REAL_FACETS_RFFT``) or 65536 (``FEATURE_REAL_FACETS_RFFT_64K``).
         Per call it also needs an even facet size, an even position of the facet in the padded row, an even row pitch and
         8-byte-aligned rows.  After a False ``_lib.last_error()`` says why."""
-        return self._supports(_lib.FEATURE_REAL_FACETS_RFFT, _torch().complex64)
+        c64 = _torch().complex64
+        return self._supports(_lib.FEATURE_REAL_FACETS_RFFT_64K, c64) or self._supports(_lib.FEATURE_REAL_FACETS_RFFT, c64)
 
     def _real_rows_match_promoted(self, facet_size):
         """Does the real-load K1 give a row of ``facet_size`` reals bit for bit the values of the promoted row?  Not at
@@ -613,10 +615,12 @@ class SwiftlyCoreHip:
     def supports_real_facets_out_c2r(self):
         """True when the half-length form of the real-output backward finish exists for these sizes
         (``finish_facet_band(..., real=True, half_length=True)``; ``swiftly_hip_finish_facet_band_c2r``):
-        :py:meth:`supports_real_facets_out` at ``yN_size`` 32768.  Per call it also needs an even facet size, an even position
+        :py:meth:`supports_real_facets_out` at ``yN_size`` 32768 (``FEATURE_REAL_FACETS_OUT_C2R``) or 65536
+        (``FEATURE_REAL_FACETS_OUT_C2R_64K``).  Per call it also needs an even facet size, an even position
         of the facet in the padded row, an even output row pitch and 8-byte-aligned output rows.  After a False
         ``_lib.last_error()`` says why."""
-        return self._supports(_lib.FEATURE_REAL_FACETS_OUT_C2R, _torch().complex64)
+        c64 = _torch().complex64
+        return self._supports(_lib.FEATURE_REAL_FACETS_OUT_C2R_64K, c64) or self._supports(_lib.FEATURE_REAL_FACETS_OUT_C2R, c64)
 
     def supports_real_facets_f64(self):
         """True when the complex128 forward K1 takes real-valued float64 facets as they are

@@ -70,7 +70,8 @@ class SwiftlyForward(WavePrefetch):
         Any other value: ``ValueError``
     :param half_length_k1: ``True`` (with ``facet_dtype=float32``, ``ValueError`` without): K1 of the real facets as ONE
         half-length transform per row (``core.prepare_facet_band(..., half_length=True)``) where that form exists
-        (``core.supports_real_facets_rfft()``: ``yN_size`` 32768) and every facet can be loaded as pairs -- an even facet
+        (``core.supports_real_facets_rfft()``: ``yN_size`` 32768, ``_lib.FEATURE_REAL_FACETS_RFFT``, or 65536,
+        ``_lib.FEATURE_REAL_FACETS_RFFT_64K``) and every facet can be loaded as pairs -- an even facet
         size, even positions in the padded row, device rows 8-byte aligned at an even pitch -- in the modes that store the
         band (axis-1-first mode 2 keeps its window-rows K1).  The results are those of the promoted facets within the same
         bound, not bit for bit; such facets stay float32 whatever their size.  Where the form is not available the object
