@@ -140,9 +140,13 @@ enum {
                                                    (one 32768-point transform per row), size part: the sizes of REAL_FACETS with
                                                    yN_size 65536.  The entry points take a handle that REAL_FACETS_RFFT or this
                                                    feature supports ("real facets, half-length: ...") */
-    SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R_64K = 17 /* finish_facet_band_c2r on 65536-point band rows, size part: the sizes of
+    SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R_64K = 17, /* finish_facet_band_c2r on 65536-point band rows, size part: the sizes of
                                                    REAL_FACETS_OUT with yN_size 65536.  The entry point takes a handle that
                                                    REAL_FACETS_OUT_C2R or this feature supports ("real facets out, half-length: ...") */
+    SWIFTLY_FEATURE_AXIS1_COLUMNS = 18          /* prepare_facet_columns_axis1 (dtype): complex64, the parity-split band layout,
+                                                   (yN_size, m) = (32768, 512) or (16384, 256), a sum_finish instance for
+                                                   (m, xM_size) and xM_size <= 2048.  The gate the entry point refuses through
+                                                   ("axis-1 columns: ...") */
 };
 int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int64_t xM_size, int64_t n_facets);
 enum {
@@ -624,6 +628,29 @@ int swiftly_hip_wave_subgrid_side_placed(swiftly_hip_t* h, int dtype, const void
                                          int64_t subgrid_size, const void* mask0, int64_t mask0_bs, const void* mask1,
                                          int64_t mask1_bs, void* tmp_work, void* out, void* scratch, int64_t scratch_bytes,
                                          void* stream);
+/* AXIS-1-FIRST pipeline with the contiguous-axis finish INSIDE K2 (SwiftlyConfig(axis1_first="k2")): finish_axis1_rows for
+ * the wave `wave_off1` and prepare_facet_columns on its output, in one call that never writes the finished rows.  The
+ * strided-axis transform of K2 is a four-step yN = n1 * n2 with n1 = 16384 / m; a workgroup of its first pass holds the n1
+ * band-buffer rows {y1*n2 + y2} across the whole m-column window in LDS, finishes every row that lies inside the facet
+ * along the contiguous axis (gather in window order, m-point transform, Fn, rotation by the facet's s'1 -- the rows of the
+ * zero padding are neither read nor transformed), THEN does the n1-point step of the strided axis over them; the second
+ * pass is the n2-point column pass of prepare_facet_columns, with its row map.
+ *   out + f*out_facet_stride = [rows kept, m], element for element in meaning what prepare_facet_columns returns for
+ *   `bands` = the output of finish_axis1_rows(wave_off1) and the band (window start, m) -- the same values up to float32
+ *   rounding, not the same bits (another split of the strided axis).  out_rowmap as prepare_facet_columns: rows with a
+ *   negative entry are not written (null: all yN rows, out_row_stride >= m).
+ * bands: K1 band buffers [rows, band columns] per facet, parity-split; the window of wave_off1 has to lie inside the band
+ * (SWIFTLY_ERR_PARAM).  facet_off0s, facet_off1s: host arrays, 1 .. 64 facets.  workspace: 8 * yN * m bytes per facet of a
+ * group of up to 32 facets, else the stream-ordered pool (as prepare_facet_columns_waves); everything runs on `stream`.
+ * float32 arithmetic whatever swiftly_hip_set_column_precision says.  complex64 and the sizes of
+ * swiftly_hip_supports(SWIFTLY_FEATURE_AXIS1_COLUMNS); SWIFTLY_ERR_UNSUPPORTED with its text otherwise, nothing written.
+ * (No reference counterpart: api_helper.py:81-99 allows either order of the axes.) */
+int swiftly_hip_prepare_facet_columns_axis1(swiftly_hip_t* h, int dtype, const void* bands, int64_t rows,
+                                            int64_t band_row_stride, int64_t band_facet_stride, int64_t nfacets,
+                                            const int64_t* facet_off0s, const int64_t* facet_off1s, int64_t band_start,
+                                            int64_t band_len, int64_t wave_off1, void* out, int64_t out_row_stride,
+                                            int64_t out_facet_stride, const int32_t* out_rowmap, void* workspace,
+                                            int64_t workspace_bytes, void* stream);
 
 /* AXIS-1-FIRST pipeline with the contiguous-axis finish FUSED INTO THE FORWARD K1 (r6): prepare_facet_band_rows as one
  * persistent workgroup per CU that owns whole rows -- both output parities -- stages the band of a row in LDS (it never

@@ -2,6 +2,7 @@
 // host code only.  Plan -> single pass, or lease the scratch -> chunked (K2, two streams) or plain schedule -> release.
 #include <hip/hip_runtime.h>
 #include "swiftly_abi_internal.h"
+#include "swiftly_colaxis1.h"
 
 ColZ plain_colz() {
     ColZ z;
@@ -259,4 +260,36 @@ int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz
         return lease.release(run_chunked(h, p, c, cz, W, nb, st, lease.p, Wc, zc));
     if (!lease.own) h->ws_plain_pending.store(lease.p);  // `ws` is written on `st` below: a later chained chunked call has to wait for it
     return lease.release(run_plain(p, c, cz, W, nb, st, lease.p, scratch_bytes, qmul, qadd, full_n));
+}
+
+// K2 with the contiguous-axis finish inside the first pass of its four-step (swiftly_colaxis1.h): pass A' of `x` over `nb`
+// facets into the scratch [nb][yN][m], then pass B -- the store side of `c`, as col_transform runs it, with n1 = 16384 / m
+// instead of col_split's halves -- both on the caller's stream and in float32.  Returns -1 without launching anything when
+// (yN, m) has no instance, else a status code.
+int col_transform_axis1(swiftly_hip* h, const ColPassArgs& c, const ColZ& cz, ColAxis1Args x, int nb, hipStream_t st, void* ws,
+                        size_t ws_bytes) {
+    if (!col_axis1_instance(h->log_yN, h->log_m)) return -1;
+    const int m = (int)h->m;
+    ColPlan p{};
+    p.two = true;
+    p.l1 = kColAxis1LogTile - h->log_m; p.l2 = h->log_yN - p.l1;
+    p.n1 = 1 << p.l1; p.n2 = 1 << p.l2;
+    p.esz = sizeof(cx<float>); p.n = (uint64_t)h->yN;
+    p.tw2 = twiddles<float>(h, p.l2); p.twf = twiddles<float>(h, h->log_yN);
+    if (!p.tw2 || !p.twf) return fail(SWIFTLY_ERR_HIP, "internal: missing twiddle table");
+    p.b_i_rows = p.n1; p.b_o_rows = 1;  // the intermediate of make_plan: row y2 * n1 + k1
+    const size_t scratch_bytes = (size_t)nb * p.n * (size_t)m * p.esz;
+    ScratchLease lease;
+    if (int rc = lease.acquire(ws, ws_bytes, scratch_bytes, st, "hipMallocAsync(two-pass scratch)")) return rc;
+    if (!lease.own) h->ws_plain_pending.store(lease.p);  // (as col_transform's plain schedule: `ws` is written on `st`)
+    const int scratch_nt = scratch_bytes > (size_t(192) << 20) ? 1 : 0;  // (run_plain)
+    x.out = (cx<float>*)lease.p; x.out_fs = (long long)(p.n * (uint64_t)m); x.scratch_nt = scratch_nt; x.tw_full = p.twf;
+    int rc = launch_status(launch_col_axis1(h->log_yN, h->log_m, x, nb, st), "axis-1 pass A'", "no instance");
+    if (!rc) {
+        ColPassArgs B = pass_b_args(c, p);
+        B.scratch_nt = scratch_nt; B.ncols = m;
+        B.in = (const cx<float>*)lease.p; B.in_pitch = (unsigned)m; B.in_bs = x.out_fs;
+        rc = launch_col_checked(p.l2, 1, B, pass_b_colz(cz), p.n1, nb, st);
+    }
+    return lease.release(rc);
 }

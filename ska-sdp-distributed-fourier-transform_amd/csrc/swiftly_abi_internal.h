@@ -243,6 +243,10 @@ struct CallWorkspace {
 };
 int col_transform(swiftly_hip* h, int logn, const ColPassArgs& c, const ColZ& cz, int W, int nb, hipStream_t st,
                   void* ws = nullptr, size_t ws_bytes = 0, int qmul = 0, int qadd = 0, int full_n = 0);
+// the same transform with the contiguous-axis finish inside its first pass (swiftly_colaxis1.h; swiftly_abi_coltransform.hip)
+namespace swf { struct ColAxis1Args; }
+int col_transform_axis1(swiftly_hip* h, const ColPassArgs& c, const ColZ& cz, swf::ColAxis1Args x, int nb, hipStream_t st,
+                        void* ws, size_t ws_bytes);
 
 // Facet tables of the row-wise fused kernels (swiftly_sumfinish.h), grouped by off1: entries of one group are adjacent.
 template <class Args>

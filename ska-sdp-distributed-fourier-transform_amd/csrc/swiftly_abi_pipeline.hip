@@ -4,6 +4,7 @@
 // row-wise fused kernels (swiftly_sumfinish.h).
 #include "swiftly_abi_internal.h"
 #include "swiftly_groupfinish.h"
+#include "swiftly_colaxis1.h"
 
 // touched[d] = 1 for the band columns d of one wave's window (see accumulate_facet_columns)
 __global__ void mark_columns_kernel(unsigned char* __restrict__ touched, int m, int rot, int base, int yN, int band_start,
@@ -639,6 +640,70 @@ int swiftly_hip_finish_axis1_rows(swiftly_hip_t* h, int dtype, const void* bands
     for (int64_t f = 0; f < nfacets; f++) a.sp[f] = pmod(facet_shift(*h, facet_off1s[f]), m);
     if (int rc = fill_sum_finish_tables(h, false, &a.fn, &a.tw_m, nullptr, &a.twc_m, nullptr)) return rc;
     return launch_status(launch_axis1_rows(h->log_m, a, (int)nfacets, (hipStream_t)stream), nullptr, "no instance");
+}
+
+/* AXIS-1-FIRST pipeline, the finish inside K2: finish_axis1_rows + prepare_facet_columns for one wave in two launches that
+ * never write the finished rows (swiftly_colaxis1.h: pass A' of the four-step; pass B is prepare_facet_columns' own).  The
+ * argument checks of the two calls it replaces. */
+int swiftly_hip_prepare_facet_columns_axis1(swiftly_hip_t* h, int dtype, const void* bands, int64_t rows,
+                                            int64_t band_row_stride, int64_t band_facet_stride, int64_t nfacets,
+                                            const int64_t* facet_off0s, const int64_t* facet_off1s, int64_t band_start,
+                                            int64_t band_len, int64_t wave_off1, void* out, int64_t out_row_stride,
+                                            int64_t out_facet_stride, const int32_t* out_rowmap, void* workspace,
+                                            int64_t workspace_bytes, void* stream) {
+    if (!h || !bands || !out || !facet_off0s || !facet_off1s) return fail(SWIFTLY_ERR_PARAM, "null argument");
+    DeviceGuard device_guard_(h->device);
+    CHECK_DTYPE();
+    if (std::string why = why_not_axis1_columns(*h, dtype); !why.empty())
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns_axis1: %s", why.c_str());
+    if (nfacets <= 0 || nfacets > kSumFinishMaxFacets)
+        return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns_axis1: 1..%d facets supported", kSumFinishMaxFacets);
+    const int yN = (int)h->yN, m = (int)h->m;
+    if (rows <= 0 || rows >= yN) return fail(SWIFTLY_ERR_PARAM, "facet size %lld must be in [1, yN_size - 1]", (long long)rows);
+    CHECK_BAND();
+    const Window w = window_of(*h, wave_off1);
+    if (window_in_band(*h, w, 0, m, band_start, band_len) >= 0)
+        return fail(SWIFTLY_ERR_PARAM, "prepare_facet_columns_axis1: the window of off1 = %lld is not inside the band",
+                    (long long)wave_off1);
+    const int64_t band_half = band_half_columns(band_len);
+    if (out_row_stride < m || band_row_stride < 2 * band_half)
+        return fail(SWIFTLY_ERR_PARAM, "prepare_facet_columns_axis1: out_row_stride %lld below m = %d, or band_row_stride %lld "
+                    "below the band's %lld physical columns", (long long)out_row_stride, m, (long long)band_row_stride,
+                    (long long)(2 * band_half));
+    CHECK_OFFSETS_32(offsets_fit_32(yN, out_row_stride) && offsets_fit_32(yN, m));
+    // pass B: the store side of prepare_facet_columns (whole(yN), the wave's row map, 1 / yN, conjugated back)
+    ColPassArgs c = col_pass_args(whole(rows), whole(yN));
+    c.ncols = m;
+    c.full_logn = h->log_yN;
+    c.out_pitch = (unsigned)out_row_stride;
+    c.scale = (float)(1.0 / yN);
+    c.conj_ld = c.conj_st = 1;
+    c.st_rowmap = out_rowmap;
+    // pass A': the row finish of finish_axis1_rows behind the load map of prepare_facet_columns
+    ColAxis1Args a;
+    std::memset(&a, 0, sizeof a);
+    a.in_fs = band_facet_stride; a.in_rs = band_row_stride;
+    a.rows = (int)rows; a.yN = yN;
+    a.band_start = (int)band_start; a.band_len = (int)band_len; a.band_half = (int)band_half;
+    a.c0 = w.base;
+    a.s = pmod(w.s, m);
+    if (int rc = fill_sum_finish_tables(h, false, &a.fn, &a.tw_m, nullptr, &a.twc_m, nullptr)) return rc;
+    const size_t ws_bytes = workspace ? (size_t)std::max<int64_t>(0, workspace_bytes) : 0;
+    for (int64_t f0 = 0; f0 < nfacets; f0 += kColZF) {
+        const int nf = (int)std::min<int64_t>(kColZF, nfacets - f0);
+        for (int f = 0; f < nf; f++) {
+            a.sp[f] = pmod(facet_shift(*h, facet_off1s[f0 + f]), m);
+            a.ld_a[f] = facet_in_padded_facet(*h, rows, facet_off0s[f0 + f]).a;
+        }
+        a.in = (const cx<float>*)bands + f0 * band_facet_stride;
+        // item z = facet: reads its slot of the scratch, writes out[f]
+        c.out = (cx<float>*)out + f0 * out_facet_stride;
+        c.out_bdiv = 1; c.out_bs_hi = out_facet_stride; c.out_bs = 0;
+        const int rc = col_transform_axis1(h, c, plain_colz(), a, nf, (hipStream_t)stream, workspace, ws_bytes);
+        if (rc == -1) return fail(SWIFTLY_ERR_UNSUPPORTED, "prepare_facet_columns_axis1: no instance for yN %d, m %d", yN, m);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 /* Backward subgrid side, contiguous-axis half + axis-0 remainder (see swiftly_sumfinish.h): in[b] = [xM, xA] =

@@ -81,6 +81,7 @@ int swiftly_hip_supports(int feature, int dtype, int64_t N, int64_t yN_size, int
             case SWIFTLY_FEATURE_REAL_FACETS_OUT_F64: why = why_not_real_facets_out_f64(s, dtype); break;
             case SWIFTLY_FEATURE_REAL_FACETS_RFFT_64K: why = why_not_real_facets_rfft_64k(s, dtype); break;
             case SWIFTLY_FEATURE_REAL_FACETS_OUT_C2R_64K: why = why_not_real_facets_out_c2r_64k(s, dtype); break;
+            case SWIFTLY_FEATURE_AXIS1_COLUMNS: why = why_not_axis1_columns(s, dtype); break;
             default: why = reason("unknown feature %d", feature);
         }
     }

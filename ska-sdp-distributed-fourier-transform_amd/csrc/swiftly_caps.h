@@ -344,6 +344,35 @@ inline std::string why_not_window_rows(const Sizes& s) {
     return reason("window rows: needs yN %d, m %d and xM <= %d; got yN %lld, m %lld, xM %lld", 1 << kWindowRowsLogYN,
                   1 << kWindowRowsLogM, 1 << kPlacedMaxLogXM, (long long)s.yN, (long long)s.m, (long long)s.xM);
 }
+// prepare_facet_columns_axis1 (K2 with the contiguous-axis finish inside pass A' of its four-step, swiftly_colaxis1.h):
+// complex64, the parity-split band layout, an instance of pass A' for (yN, m) -- n1 = 16384 / m rows of the window in LDS
+// and a pass B of n2 = yN / n1 <= 1024 points -- a sum_finish pair for (m, xM), and the placed sum_finish_facets behind it
+#define CA1_PAIRS(X) X(15, 9) X(14, 8)  // (log2 yN, log2 m) instances of col_axis1.hip
+inline bool col_axis1_instance(int log_yN, int logm) {
+#define CA1_HAS(L, M) \
+    if (log_yN == L && logm == M) return true;
+    CA1_PAIRS(CA1_HAS)
+#undef CA1_HAS
+    return false;
+}
+inline std::string why_not_axis1_columns(const Sizes& s, int dtype) {
+    const auto got = [&] { return reason("; got yN %lld, m %lld, xM %lld", (long long)s.yN, (long long)s.m, (long long)s.xM); };
+    if (dtype != SWIFTLY_C64) return "axis-1 columns: complex64 only" + got();
+    if (!band_is_split(&s))
+        return reason("axis-1 columns: needs the parity-split band layout (yN %d .. %d)", 1 << kSplitBandMinLogYN,
+                      1 << kSplitBandMaxLogYN) + got();
+    if (!col_axis1_instance(s.log_yN, s.log_m)) {
+        std::string have;
+#define CA1_NAME(L, M) have += (have.empty() ? "(" : ", (") + std::to_string(1 << L) + ", " + std::to_string(1 << M) + ")";
+        CA1_PAIRS(CA1_NAME)
+#undef CA1_NAME
+        return "axis-1 columns: instances exist for (yN, m) = " + have + got();
+    }
+    if (s.log_xM < 0 || !sum_finish_supported(s.log_m, s.log_xM) || s.log_xM > kPlacedMaxLogXM)
+        return reason("axis-1 columns: needs a sum_finish instance for (m, xM) with xM <= %d (the placed mode)", 1 << kPlacedMaxLogXM) +
+               got();
+    return {};
+}
 // size part of prepare_facet_window_rows_real (float32 rows into the whole-row K1; dtype = the output type): the sizes both
 // the window rows and the real-load K1 exist for
 inline std::string why_not_real_window_rows(const Sizes& s, int dtype) {

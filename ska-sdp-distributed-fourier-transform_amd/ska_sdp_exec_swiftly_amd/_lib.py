@@ -20,7 +20,7 @@ ERR_PARAM, ERR_UNSUPPORTED, ERR_HIP = 1, 2, 3
  FEATURE_WINDOW_ROWS, FEATURE_BACKWARD_BAND_EXPLICIT, FEATURE_SPLIT_PREPARE, FEATURE_REAL_FACETS,
  FEATURE_REAL_FACETS_OUT, FEATURE_GROUP_FINISH, FEATURE_REAL_WINDOW_ROWS, FEATURE_REAL_FACETS_RFFT,
  FEATURE_REAL_FACETS_OUT_C2R, FEATURE_REAL_FACETS_F64, FEATURE_REAL_FACETS_OUT_F64, FEATURE_REAL_FACETS_RFFT_64K,
- FEATURE_REAL_FACETS_OUT_C2R_64K) = range(18)
+ FEATURE_REAL_FACETS_OUT_C2R_64K, FEATURE_AXIS1_COLUMNS) = range(19)
 LIMIT_FUSED_FACETS, LIMIT_WINDOW_ROWS_STAGE_COLUMNS, LIMIT_WINDOW_ROWS_WINDOWS = range(3)
 
 _lib = None
@@ -177,6 +177,9 @@ def _declare(lib):
     lib.swiftly_hip_prepare_facet_window_rows_real.argtypes = list(lib.swiftly_hip_prepare_facet_window_rows.argtypes)
     lib.swiftly_hip_finish_axis1_rows.restype = c_int
     lib.swiftly_hip_finish_axis1_rows.argtypes = [vp, c_int, vp, i64, i64, i64, i64, pi64, i64, i64, i64, vp, i64, i64, vp]
+    lib.swiftly_hip_prepare_facet_columns_axis1.restype = c_int
+    lib.swiftly_hip_prepare_facet_columns_axis1.argtypes = [vp, c_int, vp, i64, i64, i64, i64, pi64, pi64, i64, i64, i64, vp,
+                                                            i64, i64, vp, vp, i64, vp]
     lib.swiftly_hip_accumulate_facet_columns.restype = c_int
     lib.swiftly_hip_accumulate_facet_columns.argtypes = [
         vp, c_int, vp, i64, i64, pi64, pi64, vp, i64, pi64, i64, vp, i64, vp, i64, i64, i64, i64, vp, vp, i64, vp,

@@ -140,8 +140,9 @@ class SwiftlyCoreHip:
     def __init__(self, W, N, xM_size, yN_size, device=None, column_precision=None, axis1_first=False):
         # (r6) axis-1-first forward band pipeline (finish_axis1_rows): the streaming classes read this switch
         # False / True / "rows" (SwiftlyConfig): the axis-1-first order of the band pipeline -- True: with the contiguous-axis
-        # finish fused into K1 where the configuration allows (else as "rows"); "rows": always a row pass per wave
-        self.axis1_first = "rows" if axis1_first == "rows" else bool(axis1_first)
+        # finish fused into K1 where the configuration allows (else as "rows"); "rows": always a row pass per wave; "k2": the
+        # finish inside K2's first four-step pass where the library has it (supports_axis1_columns; else as "rows")
+        self.axis1_first = axis1_first if axis1_first in ("rows", "k2") else bool(axis1_first)
         self.W = W
         self.N = N
         self.xM_size = xM_size
@@ -1046,6 +1047,44 @@ class SwiftlyCoreHip:
         )
         s = int(wave_off1) * yN // self.N
         return out, ((yN // 2 - m // 2 + s) % yN, m)
+
+    def supports_axis1_columns(self, dtype=None):
+        """True when :py:meth:`prepare_facet_columns_axis1` exists for these sizes (``FEATURE_AXIS1_COLUMNS``: complex64,
+        the parity-split band layout, ``(yN_size, m)`` = (32768, 512) or (16384, 256), the placed subgrid side behind it)."""
+        return self._supports(_lib.FEATURE_AXIS1_COLUMNS, dtype)
+
+    def prepare_facet_columns_axis1(self, bands, facet_off0s, facet_off1s, band, wave_off1, rowmap=None, n_rows=None, out=None):
+        """K2 of the axis-1-first order with the contiguous-axis finish inside its first pass
+        (``swiftly_hip_prepare_facet_columns_axis1``): what :py:meth:`prepare_facet_columns` gives for the output of
+        :py:meth:`finish_axis1_rows` ``(bands, facet_off1s, band, wave_off1)`` and its window band, from the K1 band buffers
+        ``bands[F, yB, band columns]`` themselves -- the finished rows stay on chip.  Keeps the rows ``rowmap`` selects ->
+        ``[F, n_rows, xM_yN_size]``.  Refused (nothing written) for other sizes or dtypes: ``supports_axis1_columns``."""
+        torch = _torch()
+        if bands.dtype not in (torch.complex64, torch.complex128):
+            raise TypeError(f"prepare_facet_columns_axis1: band buffers must be complex, not {bands.dtype}")
+        F, yB = bands.shape[0], bands.shape[1]
+        m = self.xM_yN_size
+        n_rows = self.yN_size if rowmap is None else int(n_rows)
+        if out is None:
+            out = torch.empty((F, n_rows, m), dtype=bands.dtype, device=self._device)
+        elif out.dim() != 3 or out.shape[0] != F or out.shape[1] < n_rows or out.shape[2] != m or out.stride(2) != 1:
+            raise ValueError(f"Output array has shape {tuple(out.shape)}, expected {(F, n_rows, m)}!")
+        scr = self.scratch("k2", self._k2_scratch_bytes(min(F, 32)))
+        cvp = ctypes.c_void_p
+        _lib.check(
+            self._lib.swiftly_hip_prepare_facet_columns_axis1(
+                self._handle, self._code(bands), cvp(bands.data_ptr()), int(yB), bands.stride(1), bands.stride(0), F,
+                self._i64(facet_off0s), self._i64(facet_off1s), int(band[0]), int(band[1]), int(wave_off1),
+                cvp(out.data_ptr()), out.stride(1), out.stride(0), cvp(rowmap.data_ptr()) if rowmap is not None else None,
+                cvp(scr.data_ptr()), scr.numel(), self._stream(),
+            )
+        )
+        self.k2_columns_issued += m
+        self.axis1_columns_issued += 1
+        return out
+
+    #: calls of :py:meth:`prepare_facet_columns_axis1` that ran (the tests read it)
+    axis1_columns_issued = 0
 
     def sum_finish_facets(self, G, facet_off0s, facet_off1s, out, subgrid_off1s, subgrid_size, mask=None):
         """K4b + K5a: sum over facets + axis-1 finish of ``G[F, S, m, m]`` (transform_contributions) ->

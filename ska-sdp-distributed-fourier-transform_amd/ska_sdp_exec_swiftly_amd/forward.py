@@ -606,6 +606,26 @@ class SwiftlyForward(WavePrefetch):
             return bands[:, w], (start, m)
         return self.core.finish_axis1_rows(bands, [cfg.off1 for cfg in self.facet_configs], self._band, off1)
 
+    def _k2_finishes_axis1(self):
+        """does K2 itself finish the contiguous axis (``SwiftlyConfig(axis1_first="k2")`` in the row-pass mode, on a core
+        that has ``prepare_facet_columns_axis1`` for its sizes)?  Else ``"k2"`` runs as ``"rows"`` does.  The gate is asked
+        only for the value ``"k2"``."""
+        core = self.core
+        return (getattr(core, "axis1_first", False) == "k2" and self._axis1() == 1
+                and core.supports_axis1_columns(self.dtype))
+
+    def _k2_wave(self, off1, rowmap, n_rows, out=None):
+        """K2 of wave ``off1`` on the current stream, the one call both K2 call sites make (here and ``_prefetch_wave``):
+        ``core.prepare_facet_columns`` on :py:meth:`_k2_source` -- or, with ``axis1_first="k2"``, ONE call of
+        ``core.prepare_facet_columns_axis1`` on the K1 band buffers and the pass's band, which finishes the contiguous axis
+        inside K2's first pass instead of a row pass in front of it."""
+        off0s = [cfg.off0 for cfg in self.facet_configs]
+        if self._k2_finishes_axis1():
+            return self.core.prepare_facet_columns_axis1(self.BF_Fs_persist, off0s, [cfg.off1 for cfg in self.facet_configs],
+                                                         self._band, off1, rowmap, n_rows, out=out)
+        bands, band = self._k2_source(off1)
+        return self.core.prepare_facet_columns(bands, off0s, band, off1, rowmap, n_rows, out=out)
+
     def _get_wave_columns(self, off1):
         """K2: ``(Q[F, rows, m], rowmap)`` for the subgrid wave ``off1`` (LRU cached like the reference's per-off0 columns).  A
         prefetched ``Q`` is taken over; one that has to be computed is checked against the plan first and enters the cache
@@ -617,11 +637,7 @@ class SwiftlyForward(WavePrefetch):
                 raise ValueError(f"subgrid wave off1={off1} was not in the subgrid_configs plan")
             self.prepare_all_facets()
             rowmap, n_rows = self._wave_rows(off1)
-            bands, band = self._k2_source(off1)
-            Q = self.core.prepare_facet_columns(
-                bands, [cfg.off0 for cfg in self.facet_configs], band, off1, rowmap, n_rows
-            )
-            hit = (Q, rowmap)
+            hit = (self._k2_wave(off1, rowmap, n_rows), rowmap)
             self.lru.set(("b", off1), hit)
         return hit
 

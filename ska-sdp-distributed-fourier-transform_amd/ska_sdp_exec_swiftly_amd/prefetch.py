@@ -105,7 +105,7 @@ class WavePredictor:
 
 class WavePrefetch:
     """Side-stream K2 of the next planned waves: the in-flight side.  The host class provides ``_plan`` /
-    ``_planned_keys``, ``lru``, ``core``, ``_wave_rows`` / ``_k2_source`` / ``_axis1`` and the band-lifetime fields
+    ``_planned_keys``, ``lru``, ``core``, ``_wave_rows`` / ``_k2_wave`` / ``_axis1`` and the band-lifetime fields
     ``_bands_ready`` / ``_side_waited`` / ``_k2_chain_forked``, which it resets when band buffers are installed; for the
     slab form of K2 also ``_slab_plan`` / ``_slab_rows`` / ``_compute_slab`` and the slab cache ``_slab_has`` / ``_slab_cached``
     / ``_slab_store``."""
@@ -192,12 +192,9 @@ class WavePrefetch:
         side, chain = self._side_behind_bands()
         with torch.cuda.stream(side):
             Q = torch.empty((len(self.facet_configs), n_rows, core.xM_yN_size), dtype=self.dtype, device=core.device)
-            src, band = self._k2_source(off1)
             core.chain_chunk_streams(chain)
             try:
-                core.prepare_facet_columns(
-                    src, [cfg.off0 for cfg in self.facet_configs], band, off1, rowmap, n_rows, out=Q
-                )
+                self._k2_wave(off1, rowmap, n_rows, out=Q)
             finally:
                 core.chain_chunk_streams(False)
             done = torch.cuda.Event()
